@@ -11,8 +11,13 @@ K timed steps run as ONE persistent launch of the step kernel (the closed loop i
 a rollout; --steps-per-launch 1 gives one launch per step); inputs are resident
 in HBM before the timed region and every step round-trips its state through HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figure, `ms_per_step`, the roofline
+of the timed launch). --full adds everything else: the loaded-clock second pass, the end-of-run statistics gather and
+checks, the side configurations and the CPU baseline. --dump-outputs DIR writes what the timed path handed back after
+its last timed step as DIR/<name>.npy (float32 / float64), so that two builds can be compared output for output.
 
 Robots are independent: ranks shard the batch (weak scaling, 65536 robots per
 GPU, RNG keyed by global robot index), there is no collective on the data path;
@@ -119,6 +124,29 @@ def valu_issue(valu_per_wave_step, B, spl, kern_ms, src, robots_per_wave=64):
             "note": "VALU instructions only (SQ_INSTS_VALU per wave-step, profile-derived). peak / frac = the SIMD-32 issue "
                     "peak, 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 op; *_lone_wave = 1024 SIMDs x 2.4 GHz / 4, the rate "
                     "ONE wave per SIMD can issue at (the kernel's occupancy: 512 registers + 40 KiB LDS per wave)"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path hands back (robots along the last axis), float32 or
+    float64 (integer arrays as float64). This rank's block when world > 1 (DIR/<name>.rank<r>.npy). Above 64 MB in all, a
+    fixed, seeded sample of robot columns is kept, the same for every array, and its indices go to robot_index.npy."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    B = next(iter(host.values())).shape[-1]
+    if total > DUMP_LIMIT_BYTES:
+        n = max(1, DUMP_LIMIT_BYTES * B // (total + 8 * B))      # the sampled arrays plus the float64 index fit the limit
+        idx = np.sort(np.random.default_rng(20201118).choice(B, n, replace=False))
+        host = {k: a[..., idx] for k, a in host.items()}
+        host["robot_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, (name if world == 1 else "%s.rank%d" % (name, rank)) + ".npy"), np.ascontiguousarray(a))
 
 
 class DryRunMPC:
@@ -394,6 +422,9 @@ def main_p5f(args):
     local = time.perf_counter() - t0
     barrier()
     elapsed = shard.max_over_ranks(local, device=dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": mpc.y, "sol_x": mpc.solution(), "sol_y": mpc.qp.sol_y,
+                                         "status": mpc.qp.status, "info": mpc.qp.info}, rank, world)
     s = mpc.qp.s
     esz = 4 if args.dtype == "f32" else 8
     # algorithmic bytes per robot-tick: iterates x, y, z read + written, state 7 + 7, nominal input 1
@@ -410,7 +441,7 @@ def main_p5f(args):
             traffic_src = "%s: %.0f B read + %.0f B written per robot-tick (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at B = %d, " \
                           "gfx950 correction applied; the loop re-reads its read-only stream every iteration) x %d robots" \
                           % (j["_file"], per["read_corrected"], per["written"], j["batch"], B)
-        print(json.dumps({
+        line = {
             "metric": "closed-loop MPC steps/sec (QP+dyn)", "value": world * B * args.steps / elapsed, "unit": "steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
@@ -424,9 +455,11 @@ def main_p5f(args):
                          "kernel": {"tables": "bqp_solve_kernel", "wave": "bqp_wave_kernel"}.get(
                              mpc.qp.kernel_name, "bqp_fixed_%s_asm_kernel" % mpc.qp.kernel_name[:-4] if mpc.qp.kernel_name.endswith("+asm")
                              else "bqp_fixed_%s_kernel" % mpc.qp.kernel_name),
-                         "kernel_ms": kern_ms, "alg_bytes_per_launch": alg * B},
-            "check": {"nonfinite_state_values": int((~torch.isfinite(mpc.y)).sum().item()),
-                      "status_solved_frac": float((mpc.qp.status > 0).float().mean().item())}}), flush=True)
+                         "kernel_ms": kern_ms, "alg_bytes_per_launch": alg * B}}
+        if args.full:
+            line["check"] = {"nonfinite_state_values": int((~torch.isfinite(mpc.y)).sum().item()),
+                             "status_solved_frac": float((mpc.qp.status > 0).float().mean().item())}
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -466,7 +499,12 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=100)
     ap.add_argument("--dry-run", action="store_true",
                     help="TEST ONLY (tests/test_shard_gloo.py): run the launcher, rendezvous (gloo), sharding, barriers, "
-                         "max-over-ranks timing and the statistics gather on CPU with NO kernel; the line says dry_run")
+                         "max-over-ranks timing and (with --full) the statistics gather on CPU with NO kernel; the line says dry_run")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: the loaded-clock pass, the end-of-run statistics and checks, the side "
+                         "configurations and the CPU baseline (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -568,6 +606,12 @@ def main():
     coll_err = []      # collective failures after the timed region: recorded in the line, never fatal to it
     local, elapsed, per_rank_s, kern_ms = protocol()
     nsteps_done = args.warmup + args.steps
+    if args.dump_outputs:
+        # the pass of record's results, before --full runs anything more on the same batch
+        arrays = {"state": mpc.state, "status": mpc.status}
+        if not args.dry_run:
+            arrays.update(out=mpc.out, stats=mpc.stats, info=mpc.info)
+        dump_outputs(args.dump_outputs, arrays, rank, world)
     loaded, precond = None, None
     # `value` / `ms_per_step` are ALWAYS this first pass: the literal --warmup W / --steps K protocol, nothing run before it.
     # The chip needs ~25 ms of sustained load to reach its loaded clock (measured: profiles/r03_clock_ramp.txt -- behind a
@@ -575,8 +619,9 @@ def main():
     # ramp for ~22 ms), and W + K steps of 0.12 ms are far shorter than that ramp. So when the whole protocol took < 25 ms
     # the same W + K pass is run a SECOND time behind >= 30 ms of the same step kernel on the same batch and reported
     # BESIDE the value of record, under `loaded_clocks` (compare loaded with loaded and first-pass with first-pass across
-    # rounds). --no-precondition skips the second pass.
-    if not args.no_precondition and not args.dry_run and not coll_err and elapsed * (1 + args.warmup / max(1, args.steps)) < 25e-3:
+    # rounds). Only under --full; --no-precondition skips the second pass there.
+    if (args.full and not args.no_precondition and not args.dry_run and not coll_err
+            and elapsed * (1 + args.warmup / max(1, args.steps)) < 25e-3):
         P = int(np.ceil(30e-3 / (elapsed / args.steps)))
         t0 = time.perf_counter()
         mpc.rollout(P)
@@ -591,19 +636,21 @@ def main():
                           "NOT the value of record"}
         nsteps_done = 2 * (args.warmup + args.steps) + P
 
-    # end-of-run trajectory statistics: the only exchange of the path (RCCL all_gather over xGMI,
+    # end-of-run trajectory statistics (--full): the only exchange of the path (RCCL all_gather over xGMI,
     # outside the timed region; 2 floats per robot)
-    local_metric = mpc.metrics(nsteps_done)
-    try:
-        metric = shard.gather_stats(local_metric)
-    except Exception as ex:     # noqa: BLE001 -- the headline measurement is already taken: report it with rank 0's own statistics
-        coll_err.append("gather_stats: " + repr(ex)[:300])
-        metric = local_metric
-    status = mpc.status
-    nbad = int((~torch.isfinite(mpc.state)).sum().item())
-    if args.dry_run and rank == 0 and not coll_err:
-        # the gather returned every rank's block in global robot order
-        assert metric.shape[1] == world * B and torch.equal(metric[0], torch.arange(world * B, dtype=metric.dtype))
+    metric = None
+    if args.full:
+        local_metric = mpc.metrics(nsteps_done)
+        try:
+            metric = shard.gather_stats(local_metric)
+        except Exception as ex:     # noqa: BLE001 -- the headline measurement is already taken: report it with rank 0's own statistics
+            coll_err.append("gather_stats: " + repr(ex)[:300])
+            metric = local_metric
+        status = mpc.status
+        nbad = int((~torch.isfinite(mpc.state)).sum().item())
+        if args.dry_run and rank == 0 and not coll_err:
+            # the gather returned every rank's block in global robot order
+            assert metric.shape[1] == world * B and torch.equal(metric[0], torch.arange(world * B, dtype=metric.dtype))
 
     if rank == 0:
         total_steps = world * B * args.steps
@@ -668,10 +715,11 @@ def main():
                                  "note": "76 ds_read_b128 per ADMM iteration per lane (asmstep.py's loop) + hand-off; peak 128 B/clk/CU"},
                          "valu_issue": valu_issue(valu_per_wave_step, B, spl, kern_ms, valu_src, robots_per_wave) if valu_per_wave_step else None,
                          "note": "path is VALU-issue bound, not HBM bound (DESIGN.md): ~1.1e5 flop per 1208 B"},
-            "check": {"nonfinite_state_values": nbad,
-                      "mean_pos_err_mm2": float(metric[0].mean().item()),
-                      "status_solved_frac": float((status > 0).float().mean().item())},
         }
+        if args.full:
+            line["check"] = {"nonfinite_state_values": nbad,
+                             "mean_pos_err_mm2": float(metric[0].mean().item()),
+                             "status_solved_frac": float((status > 0).float().mean().item())}
         if args.dry_run:
             line["dry_run"] = True
             # no kernel ran: nothing was measured. What the line WOULD carry (from the ranks' sleeps) is kept beside it so that
@@ -681,15 +729,16 @@ def main():
             line["roofline"] = None
         default_headline = (args.dtype == "f32" and B == 65536 and args.max_iter == 50 and args.nsub == 25
                             and args.plant == "rk4" and not args.monte_carlo and not args.gain_sweep)
-        if world == 1 and not args.dry_run and not args.no_side_configs and default_headline:
+        if args.full and world == 1 and not args.dry_run and not args.no_side_configs and default_headline:
             del mpc
             torch.cuda.empty_cache()
             line["configs"] = side_configs(dev, args.side_steps, args.side_warmup)
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run:
             line["cpu_baseline"] = cpu_baseline(args, plant_mode)
         if dist.is_initialized():
-            line["collectives"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                                   "gathered_robots": int(metric.shape[1])}
+            line["collectives"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
+            if metric is not None:
+                line["collectives"]["gathered_robots"] = int(metric.shape[1])
             if coll_err:
                 # `value` then is rank 0's own time over world x B robots (weak scaling: every rank ran the same launch)
                 line["collectives"]["error"] = coll_err

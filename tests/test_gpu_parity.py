@@ -696,12 +696,43 @@ def test_bench_rccl_path_rehearsal_one_rank(torch_cuda):
     env = dict(os.environ, UMPC_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(shard.free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-           "--batch", "4096", "--no-cpu-baseline"]
+           "--batch", "4096", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["collectives"] == {"backend": "nccl", "world_size": 1, "gathered_robots": 4096}
     assert line["n_gpus"] == 1 and line["value"] > 1e6 and line["check"]["nonfinite_state_values"] == 0
+
+
+def test_bench_dump_outputs_are_the_timed_path_results(torch_cuda, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run writes what the timed rollout handed back, and it is what the same
+    W + K steps return in this process (bit for bit), and K sets the number of timed steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    torch = torch_cuda
+    from robobee3d_amd.batch import BatchUprightMPC, hover_initial_conditions_device
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, K, W = 4096, 3, 2
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+           "--batch", str(B), "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0
+    assert "check" not in line and "configs" not in line and "cpu_baseline" not in line and line["loaded_clocks"] is None
+    m = BatchUprightMPC(B, torch.float32, global_batch=B, plant_mode=1, maxIter=50, nsub=25)     # bench.py's defaults
+    st, ref, _ = hover_initial_conditions_device(B, 20201118, torch.float32)
+    m.set_state(st, ref)
+    m.rollout(W)            # the warm-up launch, then the timed launch, as bench.py issues them
+    m.rollout(K)
+    for name, t in (("state", m.state), ("out", m.out), ("stats", m.stats), ("info", m.info), ("status", m.status)):
+        a = np.load(d / ("%s.npy" % name))
+        assert a.dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a, t.cpu().numpy().astype(a.dtype), err_msg=name)
+    assert np.all(np.isfinite(np.load(d / "state.npy")))
 
 
 def test_reference_import_line_and_calls_in_a_fresh_process(torch_cuda):

@@ -56,7 +56,7 @@ def test_bench_self_launches_n_ranks():
     before touching any device. --dry-run keeps the kernel out (no GPU here): launcher, gloo rendezvous, sharding,
     barriers, max-over-ranks and the statistics gather in global robot order all run; rank 0 prints ONE line."""
     import json
-    r = _bench(["--gpus", "2", "--steps", "4", "--warmup", "3", "--batch", "96", "--dry-run", "--monte-carlo"])
+    r = _bench(["--gpus", "2", "--steps", "4", "--warmup", "3", "--batch", "96", "--dry-run", "--monte-carlo", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -69,13 +69,58 @@ def test_bench_self_launches_n_ranks():
     assert j["collectives"] == {"backend": "gloo", "world_size": 2, "gathered_robots": 192}
 
 
+def test_plain_bench_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline figure only: no loaded-clock pass, no statistics gather, no checks.
+    --dump-outputs writes each rank's block of what the timed path returned (the dry run leaves the inputs untouched, so
+    the state is the seeded start state of that block)."""
+    import json
+    from robobee3d_amd.batch import hover_initial_conditions
+    d = tmp_path / "dump"
+    r = _bench(["--gpus", "2", "--steps", "4", "--warmup", "3", "--batch", "96", "--dry-run", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j["steps"] == 4 and j["warmup"] == 3 and len(j["ms_per_step_per_rank"]) == 2
+    assert "check" not in j and "configs" not in j and "cpu_baseline" not in j and j["loaded_clocks"] is None
+    assert j["collectives"] == {"backend": "gloo", "world_size": 2}
+    for rank in range(2):
+        st, _ = hover_initial_conditions(96, 20201118, np.float32, index_offset=96 * rank)
+        a = np.load(d / ("state.rank%d.npy" % rank))
+        assert a.dtype == np.float32
+        np.testing.assert_array_equal(a, st)
+        s = np.load(d / ("status.rank%d.npy" % rank))
+        assert s.dtype == np.float64 and s.shape == (96,)
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_size_limit(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    B = 1000
+    a = np.arange(3 * B, dtype=np.float32).reshape(3, B)
+    s = np.arange(B, dtype=np.int32)
+    for k in (1, 2):
+        bench.dump_outputs(str(tmp_path / str(k)), {"a": a, "s": s})
+    idx = np.load(tmp_path / "1" / "robot_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    total = 0
+    for name in ("a", "s", "robot_index"):
+        x, y = np.load(tmp_path / "1" / (name + ".npy")), np.load(tmp_path / "2" / (name + ".npy"))
+        np.testing.assert_array_equal(x, y)       # the same sample every run
+        total += x.nbytes
+    assert total <= 4096
+    np.testing.assert_array_equal(np.load(tmp_path / "1" / "a.npy"), a[:, idx.astype(int)])
+    np.testing.assert_array_equal(np.load(tmp_path / "1" / "s.npy"), s[idx.astype(int)].astype(np.float64))
+
+
 def test_config5_shape_dry_run_on_eight_ranks():
     """BASELINE configs[4]'s exact shape -- 2^17 robots per rank x 8 ranks = 2^20, Monte-Carlo draws keyed
     by the global robot index -- through bench.py's own launcher on eight gloo ranks (CPU, no kernel): ONE line,
     world size 8, 2^20 robots gathered in global order (bench.py asserts the order on rank 0), one time per rank. This
     rehearses the rendezvous / sharding / gather of the 8-GPU run; it measures nothing and claims nothing about hardware."""
     import json
-    r = _bench(["--gpus", "8", "--monte-carlo", "--batch", "131072", "--steps", "2", "--warmup", "1", "--dry-run"], timeout=600)
+    r = _bench(["--gpus", "8", "--monte-carlo", "--batch", "131072", "--steps", "2", "--warmup", "1", "--dry-run", "--full"],
+               timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -131,7 +176,8 @@ def test_failed_statistics_gather_does_not_cost_the_measurement():
     must leave ONE line with the figure the ranks had already measured, the failure recorded under collectives.error, and
     a clean exit (the timing itself went through its own collectives)."""
     import json
-    r = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "64", "--dry-run"], env={"UMPC_TEST_FAIL_GATHER": "1"})
+    r = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "64", "--dry-run", "--full"],
+               env={"UMPC_TEST_FAIL_GATHER": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -7,7 +7,7 @@ set -o pipefail
 OUT=${1:-gpurun_out/nt}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python3 bench.py --no-cpu-baseline --no-side-configs"
+CMD="python3 bench.py --full --no-cpu-baseline --no-side-configs"
 for v in base nt ntld ntst base nt; do
   if [ $v = base ]; then unset UMPC_LIB; else export UMPC_LIB=$PWD/robobee3d_amd/variants/libumpc_$v.so; fi
   $CMD > "$OUT/time_$v.$RANDOM.json" 2>"$OUT/err.log" || exit 1
