@@ -871,153 +871,20 @@ def write(path=None, N=3, perm=None):
 # ---------------------------------------------------------------------------
 # CPU interpreter of the emitted instruction list (one lane), for the tests
 # ---------------------------------------------------------------------------
+WS_BASE, CTRL_BASE, STRIDE = 1 << 20, 1 << 30, 4096       # simulated addresses of the two [row][B] arrays
+
+
 def simulate(ins, mem_ws, mem_ctrl, iters, lds=None):
     """mem_ws: float32[WS_ROWS], mem_ctrl: float32[127], lds: float32[160] (one robot / one lane).
     Runs the program; memories are updated in place (lds holds L[0..160) on entry, x,y,z on exit).
-    Branch targets are the numeric local labels used above. Returns the executed instruction count."""
+    Returns the executed instruction count."""
     import numpy as np
-    f32 = np.float32
-    V = np.zeros(256, f32)
-    A = np.zeros(256, f32)
-    S = {}
-    if lds is None:
-        lds = np.zeros(40 * 4, f32)
-    scc = 0
-    labels = {}
-    for k, t in enumerate(ins):
-        if t[0] == "label":
-            labels.setdefault(t[1], []).append(k)
-
-    def sval(x):
-        if isinstance(x, int):
-            return x
-        if x.startswith("s["):
-            lo = int(x[2:x.index(":")])
-            return S.get(lo, 0) | (S.get(lo + 1, 0) << 32)
-        return S.get(int(x[1:]), 0)
-
-    def sf(n):
-        return np.frombuffer(struct.pack("<I", S[n] & 0xFFFFFFFF), f32)[0]
-
-    def fval(x):
-        neg = x.startswith("-")
-        if neg:
-            x = x[1:]
-        if x[0] == "v":
-            val = V[int(x[1:])]
-        elif x[0] == "s":
-            val = sf(int(x[1:]))
-        else:
-            raise ValueError(x)
-        return -val if neg else val
-
-    def half(x, sel):  # one half of a 64-bit packed operand
-        lo = int(x[2:x.index(":")])
-        return V[lo + sel] if x[0] == "v" else sf(lo + sel)
-
-    STRIDE = 4096
-    S[S_WS], S[S_WS + 1] = 1 << 20, 0          # workspace "address"
-    S[S_CTRL], S[S_CTRL + 1] = 1 << 30, 0
-    S[S_STRIDE], S[S_ITERS] = STRIDE, iters
-
-    def mem(addr):
-        if addr >= (1 << 30):
-            return mem_ctrl, (addr - (1 << 30)) // STRIDE
-        return mem_ws, (addr - (1 << 20)) // STRIDE
-
-    pc = 0
-    nexec = 0
-    while pc < len(ins):
-        t = ins[pc]
-        m = t[0]
-        nexec += 1
-        assert nexec < 400000, "runaway program"
-        if m == "label" or m == "s_waitcnt":
-            pass
-        elif m == "s_mov_b32":
-            S[int(t[1][1:])] = t[2] if isinstance(t[2], int) else sval(t[2])
-        elif m == "s_mov_b64":
-            lo = int(t[1][2:t[1].index(":")])
-            val = sval(t[2])
-            S[lo], S[lo + 1] = val & 0xFFFFFFFF, val >> 32
-        elif m == "s_mul_i32":
-            S[int(t[1][1:])] = (sval(t[2]) * sval(t[3])) & 0xFFFFFFFF
-        elif m == "s_mul_hi_u32":
-            S[int(t[1][1:])] = ((sval(t[2]) * sval(t[3])) >> 32) & 0xFFFFFFFF
-        elif m == "s_add_u32":
-            r = sval(t[2]) + sval(t[3])
-            S[int(t[1][1:])] = r & 0xFFFFFFFF
-            scc = r >> 32
-        elif m == "s_addc_u32":
-            r = sval(t[2]) + sval(t[3]) + scc
-            S[int(t[1][1:])] = r & 0xFFFFFFFF
-            scc = r >> 32
-        elif m == "s_sub_i32":
-            S[int(t[1][1:])] = (sval(t[2]) - sval(t[3])) & 0xFFFFFFFF
-        elif m in ("s_cmp_lt_i32", "s_cmp_gt_i32"):
-            a, b = sval(t[1]), sval(t[2])
-            a = a - (1 << 32) if a & 0x80000000 else a
-            scc = int(a < b) if m == "s_cmp_lt_i32" else int(a > b)
-        elif m == "s_branch" or m == "s_cbranch_scc1":
-            if m == "s_branch" or scc:
-                lab, d = t[1][:-1], t[1][-1]
-                cands = labels[lab]
-                pc = min(c for c in cands if c > pc) if d == "f" else max(c for c in cands if c < pc)
-        elif m == "global_load_dword":
-            arr, row = mem(sval(t[3]))
-            if t[1][0] == "a":
-                A[int(t[1][1:])] = arr[row]
-            else:
-                V[int(t[1][1:])] = arr[row]
-        elif m == "global_store_dword":
-            arr, row = mem(sval(t[3]))
-            arr[row] = V[int(t[2][1:])]
-        elif m == "ds_write_b128":
-            lo = int(t[2][2:t[2].index(":")])
-            lds[t[3] // 1024 * 4:t[3] // 1024 * 4 + 4] = V[lo:lo + 4]
-        elif m == "ds_write_b32":
-            lds[t[3] // 1024 * 4 + (t[3] % 1024) // 4] = V[int(t[2][1:])]
-        elif m == "ds_read_b128":
-            lo = int(t[1][2:t[1].index(":")])
-            V[lo:lo + 4] = lds[t[3] // 1024 * 4:t[3] // 1024 * 4 + 4]
-        elif m == "v_accvgpr_read_b32":
-            V[int(t[1][1:])] = A[int(t[2][1:])]
-        elif m == "v_mov_b32":
-            V[int(t[1][1:])] = fval(t[2])
-        elif m == "v_fma_f32":
-            V[int(t[1][1:])] = f32(np.float64(fval(t[2])) * np.float64(fval(t[3])) + np.float64(fval(t[4])))
-        elif m == "v_fmac_f32":
-            V[int(t[1][1:])] = f32(np.float64(fval(t[2])) * np.float64(fval(t[3])) + np.float64(V[int(t[1][1:])]))
-        elif m == "v_mul_f32":
-            V[int(t[1][1:])] = f32(fval(t[2]) * fval(t[3]))
-        elif m == "v_add_f32":
-            V[int(t[1][1:])] = f32(fval(t[2]) + fval(t[3]))
-        elif m == "v_sub_f32":
-            V[int(t[1][1:])] = f32(fval(t[2]) - fval(t[3]))
-        elif m == "v_max_f32":
-            V[int(t[1][1:])] = max(fval(t[2]), fval(t[3]))
-        elif m == "v_min_f32":
-            V[int(t[1][1:])] = min(fval(t[2]), fval(t[3]))
-        elif m in ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32"):
-            d = t[-1]
-            srcs = t[2:-1]
-            dlo = int(t[1][2:t[1].index(":")])
-            res = []
-            for hi in (0, 1):
-                sel = d["op_sel_hi"] if hi else d["op_sel"]
-                ng = d["neg_hi"] if hi else d["neg_lo"]
-                vals = [np.float64(half(x, sel[q])) * (-1 if ng[q] else 1) for q, x in enumerate(srcs)]
-                if m == "v_pk_fma_f32":
-                    res.append(f32(vals[0] * vals[1] + vals[2]))
-                elif m == "v_pk_mul_f32":
-                    res.append(f32(f32(vals[0]) * f32(vals[1])))
-                else:
-                    res.append(f32(f32(vals[0]) + f32(vals[1])))
-            V[dlo], V[dlo + 1] = res  # both halves are computed from the OLD register contents
-        else:
-            raise ValueError("unknown instruction %r" % (t,))
-        pc += 1
-    return nexec
+    from . import isasim
+    lds = np.zeros(NLDS, np.float32) if lds is None else lds
+    m = isasim.Machine(ins, regions=[(WS_BASE, STRIDE, mem_ws), (CTRL_BASE, STRIDE, mem_ctrl)],
+                       sgpr={S_WS: WS_BASE, S_CTRL: CTRL_BASE, S_STRIDE: STRIDE, S_ITERS: iters}, vgpr={0: 0},
+                       lds=lds.view(np.uint32).reshape(1, -1), max_exec=400000)
+    return isasim.run(m)
 
 
 if __name__ == "__main__":

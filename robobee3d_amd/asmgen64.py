@@ -816,229 +816,49 @@ def write(path=None, N=3, perm=None):
 # ---------------------------------------------------------------------------
 # CPU interpreter (one lane), exact-rounded float64
 # ---------------------------------------------------------------------------
+def _dwords(words):
+    """the uint32 halves of fp64 LDS words"""
+    return [2 * w + h for w in words for h in (0, 1)]
+
+
+# What the one-robot-per-quad section (asmquad64.py) hands back: the four slices must agree on the LDS words up to LW_END
+# but for the words CW0..NNZL, and on the registers the epilogue reads; everything else is poisoned. (Words LW_END.. are
+# scratch: the quad loop's compact coefficient array ends there; the C++ side writes what the residual block reads from
+# them before it runs. The array's first words overlay the last words of L: whatever the exit does not rewrite there is
+# per-lane data, dead -- the epilogue writes the thrust-row bounds over it -- and poisoned where the lanes differ so that
+# a read before that write shows up.)
+_KEEP_V = {0, 1, V_B1, V_B2} | set(range(V_C, V_RING))
+QUAD = {None: None}
+
+
+def _quad():
+    from . import asmquad64, isasim
+    if QUAD[None] is None:
+        QUAD[None] = isasim.Quad(v=_KEEP_V, dead_v=set(range(256)) - _KEEP_V, dead_a=range(A_H),
+                                 lds=_dwords(list(range(asmquad64.CW0)) + list(range(NNZL, LW_END))),
+                                 dead_lds=_dwords(range(LW_END, LDS_BYTES_PER_LANE // 8)))
+    return QUAD
+
+
+WS_BASE, CTRL_BASE, TAB_BASE, STRIDE = 1 << 20, 1 << 30, 1 << 44, 4096
+
+
 def simulate(ins, mem_ws, mem_ctrl, iters, lds, perm=None):
     """mem_ws: float64[WS_ROWS], mem_ctrl: float64[123], lds: float64[320] (L in words 0..212, 1/D in 213..296 on entry).
     Updates the memories in place; returns the executed instruction count. perm: the KKT permutation of the program (only
-    the quad form needs it, for its plan)."""
-    quad_perm_ = perm
+    the quad form needs it, for its table of coefficient addresses)."""
     import numpy as np
-    from fractions import Fraction
-    V = np.zeros(256, np.uint32)
-    A = np.zeros(256, np.uint32)
-    S = {}
-    scc = 0
-    labels = {}
-    for k, t in enumerate(ins):
-        if t[0] == "label":
-            labels.setdefault(t[1], []).append(k)
-    STRIDE = 4096
-    S[S_WS], S[S_WS + 1] = 1 << 20, 0
-    S[S_CTRL], S[S_CTRL + 1] = 1 << 30, 0
-    S[S_STRIDE], S[S_ITERS] = STRIDE, iters
-    V[1] = 0
-
-    def lohi(x):
-        return int(x[2:x.index(":")])
-
-    def sval(x):
-        if isinstance(x, int):
-            return x
-        if x.startswith("s["):
-            lo = lohi(x)
-            return S.get(lo, 0) | (S.get(lo + 1, 0) << 32)
-        return S.get(int(x[1:]), 0)
-
-    def getd(x):
-        if isinstance(x, float):
-            return x                      # inline constant (1.0, 0.5)
-        neg = x.startswith("-")
-        if neg:
-            x = x[1:]
-        if x.startswith("|"):
-            return (-1.0 if neg else 1.0) * abs(getd(x[1:-1]))
-        lo = lohi(x)
-        bits = (int(V[lo]) | (int(V[lo + 1]) << 32)) if x[0] == "v" else (S[lo] | (S[lo + 1] << 32))
-        val = struct.unpack("<d", struct.pack("<Q", bits))[0]
-        return -val if neg else val
-
-    def setd(x, val, file=None):
-        file = V if file is None else file
-        lo = lohi(x)
-        b = f64bits(float(val))
-        file[lo], file[lo + 1] = b & 0xFFFFFFFF, b >> 32
-
-    def fma(a, b, c):
-        if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
-            return a * b + c
-        return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-    def mem(addr):
-        if addr >= (1 << 30):
-            return mem_ctrl, (addr - (1 << 30)) // STRIDE
-        return mem_ws, (addr - (1 << 20)) // STRIDE
-
-    def ldsword(basereg, off):
-        byte = int(V[int(basereg[1:])]) + off
-        return (byte // 1024) * 2 + (byte % 1024) // 8
-
-    # completion model (as asmqp.simulate): LDS operations and VMEM loads complete in issue order; a register that an
-    # outstanding load will write must not be read or written before an s_waitcnt has retired that load
-    pend = {"lgkmcnt": [], "vmcnt": []}
-
-    def regs_of(x):
-        if not isinstance(x, str):
-            return set()
-        x = x.lstrip("-").strip("|")
-        if x[:2] in ("v[", "a["):
-            lo_, hi_ = x[2:-1].split(":")
-            return {(x[0], r) for r in range(int(lo_), int(hi_) + 1)}
-        if x[0] in "va" and x[1:].isdigit():
-            return {(x[0], int(x[1:]))}
-        return set()
-
-    pc = nexec = 0
-    simulate.last_quad_instructions = 0
-    while pc < len(ins):
-        t = ins[pc]
-        m = t[0]
-        if m == "quad_begin":
-            # the one-robot-per-quad section (asmquad64.py): the four lanes of a quad ran everything so far redundantly, so
-            # each starts from this lane's registers, AGPRs and LDS slice; afterwards the four slices and the thrust-row
-            # words must agree, and the other registers are poisoned (the epilogue may only read what the exit restored)
-            from . import asmquad64
-            assert ins[pc + 1] == ("s_waitcnt", "vmcnt(0) lgkmcnt(0)")      # the section starts by draining the one-lane body's LDS writes
-            pend["lgkmcnt"].clear(); pend["vmcnt"].clear()
-            s_ = symbolic.analyse(3, quad_perm_)
-            V4, A4 = np.tile(V, (4, 1)), np.tile(A, (4, 1))
-            L4 = np.tile(np.asarray(lds, np.float64), (4, 1))
-            pc, nq = asmquad64.simulate(ins, pc, V4, A4, L4, S, asmquad64.table(asmquad64.plan_for(s_)))
-            nexec += nq
-            simulate.last_quad_instructions = nq
-            # (words LW_END.. are scratch: the quad loop's compact coefficient array ends there; the C++ side writes what the
-            # residual block reads from them before it runs. The array's first words overlay the last words of L: whatever the
-            # exit does not rewrite there is per-lane data, dead -- the epilogue writes the thrust-row bounds over it --
-            # and poisoned here so that a read before that write shows up)
-            differ = np.zeros(LW_END, bool)
-            for ln in range(1, 4):
-                differ |= ~((L4[ln, :LW_END] == L4[0, :LW_END]) | (np.isnan(L4[ln, :LW_END]) & np.isnan(L4[0, :LW_END])))
-            assert set(np.nonzero(differ)[0]) <= set(range(asmquad64.CW0, NNZL)), "LDS slices of the quad disagree"
-            lds[:LW_END] = L4[0, :LW_END]
-            lds[:LW_END][differ] = np.nan
-            lds[LW_END:] = np.nan
-            keep = {0, 1, V_B1, V_B2} | set(range(V_C, V_RING))
-            for r in range(256):
-                if r in keep:
-                    assert (V4[1:, r] == V4[0, r]).all(), r
-                    V[r] = V4[0, r]
-                else:
-                    V[r] = 0x7ff8dead if r % 2 else 0xdeadbeef      # a NaN pattern in every pair
-            A[:] = A4[0]
-            A[:A_H] = 0x7ff8dead
-            continue
-        nexec += 1
-        assert nexec < 2000000, "runaway program"
-        if m == "s_waitcnt":
-            for part in t[1].split():
-                name, val = part[:-1].split("(")
-                del pend[name][:max(0, len(pend[name]) - int(val))]
-        elif m[0] == "v" or m.startswith("ds_") or m.startswith("global_"):
-            used = set().union(*[regs_of(x) for x in t[1:]])
-            for q_ in pend.values():
-                for dst in q_:
-                    assert not (dst & used), ("register used before its load was waited for", pc, t, sorted(dst & used))
-            if m.startswith("ds_read"):
-                pend["lgkmcnt"].append(regs_of(t[1]))
-            elif m.startswith("ds_write"):
-                pend["lgkmcnt"].append(set())
-            elif m.startswith("global_load"):
-                pend["vmcnt"].append(regs_of(t[1]))
-            elif m.startswith("global_store"):
-                pend["vmcnt"].append(set())
-        if m in ("label", "s_waitcnt", "s_nop"):
-            pass
-        elif m == "v_mov_b32":
-            V[int(t[1][1:])] = t[2] if isinstance(t[2], int) else V[int(t[2][1:])]
-        elif m == "v_cmp_nlt_f64":
-            S["vcc"] = int(not (getd(t[2]) < getd(t[3])))
-        elif m == "v_cndmask_b32":
-            src0 = t[2] if isinstance(t[2], int) else int(V[int(t[2][1:])])
-            V[int(t[1][1:])] = int(V[int(t[3][1:])]) if S["vcc"] else src0
-        elif m == "v_rsq_f64":
-            setd(t[1], 1.0 / np.sqrt(getd(t[2])))
-        elif m == "v_rcp_f64":
-            setd(t[1], 1.0 / getd(t[2]))
-        elif m == "ds_read_b64":
-            lo = lohi(t[1])
-            b = f64bits(float(lds[ldsword(t[2], t[3])]))
-            V[lo], V[lo + 1] = b & 0xFFFFFFFF, b >> 32
-        elif m == "s_mov_b32":
-            S[int(t[1][1:])] = t[2] if isinstance(t[2], int) else sval(t[2])
-        elif m == "s_mov_b64":
-            lo = lohi(t[1])
-            val = sval(t[2])
-            S[lo], S[lo + 1] = val & 0xFFFFFFFF, val >> 32
-        elif m == "s_mul_i32":
-            S[int(t[1][1:])] = (sval(t[2]) * sval(t[3])) & 0xFFFFFFFF
-        elif m == "s_mul_hi_u32":
-            S[int(t[1][1:])] = ((sval(t[2]) * sval(t[3])) >> 32) & 0xFFFFFFFF
-        elif m == "s_add_u32":
-            r = sval(t[2]) + sval(t[3])
-            S[int(t[1][1:])] = r & 0xFFFFFFFF
-            scc = r >> 32
-        elif m == "s_addc_u32":
-            r = sval(t[2]) + sval(t[3]) + scc
-            S[int(t[1][1:])] = r & 0xFFFFFFFF
-            scc = r >> 32
-        elif m == "s_sub_i32":
-            S[int(t[1][1:])] = (sval(t[2]) - sval(t[3])) & 0xFFFFFFFF
-        elif m in ("s_cmp_lt_i32", "s_cmp_gt_i32"):
-            a, b = sval(t[1]), sval(t[2])
-            a = a - (1 << 32) if a & 0x80000000 else a
-            scc = int(a < b) if m == "s_cmp_lt_i32" else int(a > b)
-        elif m in ("s_branch", "s_cbranch_scc1"):
-            if m == "s_branch" or scc:
-                lab, d = t[1][:-1], t[1][-1]
-                cands = labels[lab]
-                pc = min(c for c in cands if c > pc) if d == "f" else max(c for c in cands if c < pc)
-        elif m == "v_add_u32":
-            V[int(t[1][1:])] = (t[2] + int(V[int(t[3][1:])])) & 0xFFFFFFFF
-        elif m == "global_load_dwordx2":
-            arr, row = mem(sval(t[3]))
-            setd(t[1], arr[row], A if t[1][0] == "a" else V)
-        elif m == "global_store_dwordx2":
-            arr, row = mem(sval(t[3]))
-            arr[row] = getd(t[2])
-        elif m == "ds_read_b128":
-            lo = lohi(t[1])
-            w = ldsword(t[2], t[3])
-            for h in range(2):
-                b = f64bits(float(lds[w + h]))
-                V[lo + 2 * h], V[lo + 2 * h + 1] = b & 0xFFFFFFFF, b >> 32
-        elif m == "ds_write_b128":
-            w = ldsword(t[1], t[3])
-            lo = lohi(t[2])
-            for h in range(2):
-                lds[w + h] = getd(vp(lo + 2 * h))
-        elif m == "ds_write_b64":
-            lds[ldsword(t[1], t[3])] = getd(t[2])
-        elif m == "v_accvgpr_read_b32":
-            V[int(t[1][1:])] = A[int(t[2][1:])]
-        elif m == "v_accvgpr_write_b32":
-            A[int(t[1][1:])] = V[int(t[2][1:])]
-        elif m == "v_fma_f64":
-            setd(t[1], fma(getd(t[2]), getd(t[3]), getd(t[4])))
-        elif m == "v_mul_f64":
-            setd(t[1], getd(t[2]) * getd(t[3]))
-        elif m == "v_add_f64":
-            setd(t[1], getd(t[2]) + getd(t[3]))
-        elif m == "v_max_f64":
-            setd(t[1], max(getd(t[2]), getd(t[3])))
-        elif m == "v_min_f64":
-            setd(t[1], min(getd(t[2]), getd(t[3])))
-        else:
-            raise ValueError("unknown instruction %r" % (t,))
-        pc += 1
-    return nexec
+    from . import asmquad64, isasim
+    regions = [(WS_BASE, STRIDE, mem_ws), (CTRL_BASE, STRIDE, mem_ctrl)]
+    sgpr = {S_WS: WS_BASE, S_CTRL: CTRL_BASE, S_STRIDE: STRIDE, S_ITERS: iters}
+    if ("quad_begin",) in ins:
+        regions.append((TAB_BASE, 4, asmquad64.table(asmquad64.plan_for(symbolic.analyse(3, perm))).ravel()))
+        sgpr.update({asmquad64.S_TAB: TAB_BASE & 0xFFFFFFFF, asmquad64.S_TAB + 1: TAB_BASE >> 32})
+    m = isasim.Machine(ins, regions=regions, sgpr=sgpr, vgpr={0: 0}, lds=lds.view(np.uint32).reshape(1, -1),
+                       max_exec=2000000, quad=_quad())
+    isasim.run(m)
+    simulate.last_quad_instructions = m.sections.get(None, 0)
+    return m.nexec
 
 
 if __name__ == "__main__":

@@ -49,6 +49,7 @@ import struct
 import numpy as np
 
 from .asmgen import Emit, f32bits, pk as _pk
+from .isasim import AddressFault  # noqa: F401  (raised by the interpreter; the tests catch it from here)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -1974,10 +1975,6 @@ def fmt(t):
 # ---------------------------------------------------------------------------
 # CPU interpreter (one lane) and a numpy statement of the same iteration
 # ---------------------------------------------------------------------------
-class AddressFault(Exception):
-    """A simulated global access outside every array handed to the interpreter (on the GPU: a memory access fault)."""
-
-
 # Simulated device addresses: like real ones, the low word of a base has bit 31 set, so a 32-bit half that is
 # sign-extended somewhere on its way into an SGPR pair (the bug fixed in 37f012f: `readfirstlane` returns int) lands
 # 4 GiB below the array and is caught by the bounds check of every access.
@@ -1995,107 +1992,29 @@ def uni_scalar_operand(v, sign_extend_bug=False):
     return (hi << 32) | lo
 
 
-def simulate(*args, **kw):
-    """One wave: runs _simulate to the end (an s_barrier of a lone wave is a no-op). See _simulate for the arguments."""
-    g = _simulate(*args, **kw)
-    while True:
-        try:
-            next(g)
-        except StopIteration as stop:
-            return stop.value
-
-
-def simulate_group(ins, nw, W, S, iters, consts, wave_sgpr, **kw):
-    """nw waves of one workgroup run `ins` on the same LDS slots and the same global arrays (wave w gets SGPR `wave_sgpr` = w),
-    each up to its next s_barrier in turn. Checks that every wave meets every barrier, and that between two barriers no LDS
-    word is written by one wave and read or written by another (the data races a barrier-phased schedule can have). Returns
-    the shared LDS words and the per-wave executed instruction counts."""
-    lds = np.zeros(640, np.float32)
-    lds0 = kw.pop("lds0", None)
-    if lds0 is not None:
-        lds[:len(lds0)] = lds0
-    logs = [dict(r=set(), w=set()) for _ in range(nw)]
-    counts = [[] for _ in range(nw)]
-    gens = []
-    for w in range(nw):
-        sg = dict(kw.get("sgpr") or {})
-        sg[wave_sgpr] = w
-        gens.append(_simulate(ins, W, S, iters, consts, **dict(kw, sgpr=sg, lds_shared=lds, access_log=logs[w], count=counts[w])))
-    live = [True] * nw
-    nbar = 0
-    hist = []                           # per barrier phase: the words each wave wrote
-    while any(live):
-        for w in range(nw):
-            if live[w]:
-                try:
-                    next(gens[w])
-                except StopIteration:
-                    live[w] = False
-        assert all(live) or not any(live), ("the waves disagree about barrier %d" % nbar, live)
-        for a_ in range(nw):
-            for b_ in range(nw):
-                if a_ != b_:
-                    clash = (logs[a_]["w"] & (logs[b_]["r"] | logs[b_]["w"] | logs[b_].get("a", set()))) | \
-                            (logs[a_].get("a", set()) & logs[b_]["r"])
-                    assert not clash, ("LDS race before barrier %d: words written by wave %d and touched by wave %d" % (nbar, a_, b_),
-                                       sorted(clash)[:8], {k_: sorted(clash & v_)[:4] for k_, v_ in logs[b_].items()})
-        hist.append([set(lg["w"]) | set(lg.get("a", set())) for lg in logs])
-        for b_ in range(nw):
-            for (ph, word) in logs[b_].get("late", set()):
-                for a_ in range(nw):
-                    assert a_ == b_ or ph >= len(hist) or word not in hist[ph][a_], \
-                        ("LDS race: word %d fetched by wave %d in phase %d (looked at later) was written by wave %d in that phase" % (word, b_, ph, a_))
-        for lg in logs:
-            for st_ in lg.values():
-                st_.clear()
-        nbar += 1
-    return lds, [c[0] for c in counts], nbar - 1
-
-
-def _simulate(ins, W, S, iters, consts, regions=None, sgpr=None, lds0=None, ret_agpr=False, base_xform=None, count=None,
-              lds_shared=None, access_log=None):
-    """W: float32[rows] row workspace (one robot), S: float32[items] stream block (one lane); consts = (alpha, sigma, rinv_eq).
-    Runs the program and returns the lane's LDS words (x, y, z, x_prev, delta_y are left there).
-    Addresses are formed as the ISA does for global_* with an SGPR base: SGPR pair (64 bits) + zero-extended 32-bit VGPR
-    offset + immediate; every access must fall on an element of an array handed in (AddressFault otherwise). base_xform
-    models what the C++ glue does to a base pointer before it reaches the SGPR pair (uni_scalar_operand)."""
+def _machine(ins, W, S, iters, consts, regions=None, sgpr=None, lds0=None, base_xform=None, lds=None):
+    """W: float32[rows] row workspace (one robot), S: float32[items] stream block (one lane); consts = (alpha, sigma,
+    rinv_eq[, rho0]). The lane is lane 0 (v0, v4 and the Ruiz block's v210 hold 0). regions (the Ruiz block's inputs): [(SGPR pair, array)], row-major with the simulated stride, 8 GiB
+    apart. sgpr: initial SGPRs ("S" / "W": the base of that array). base_xform models what the C++ glue does to a base
+    pointer before it reaches the SGPR pair (uni_scalar_operand)."""
+    from . import isasim
     f32 = np.float32
-    V = np.zeros(256, np.uint32)
-    A = np.zeros(256, np.uint32)
-    lds = np.zeros(640, f32) if lds_shared is None else lds_shared
-    SG = {}
-    scc = 0
-    labels = {}
-    log_r = access_log["r"] if access_log is not None else set()
-    log_w = access_log["w"] if access_log is not None else set()
-    log_a = access_log.setdefault("a", set()) if access_log is not None else set()
-    src_word = {}
-    src_phase = {}                      # register -> barrier phase in which its LDS read executed
-    phase = [0]
-    log_late = access_log.setdefault("late", set()) if access_log is not None else set()
-    for k, t in enumerate(ins):
-        if t[0] == "label":
-            labels.setdefault(t[1], []).append(k)
     STRIDE = 4096
     base_xform = base_xform or (lambda a: a)
     space = [(SIM_BASE_W, STRIDE, W), (SIM_BASE_S, 256, S)]          # (true base, bytes between elements, array)
+    sg = {}
 
     def setbase(sreg, base):
         val = base_xform(base)
-        SG[sreg], SG[sreg + 1] = val & 0xFFFFFFFF, (val >> 32) & 0xFFFFFFFF
+        sg[sreg], sg[sreg + 1] = val & 0xFFFFFFFF, (val >> 32) & 0xFFFFFFFF
     setbase(S_W, SIM_BASE_W)
     setbase(S_S, SIM_BASE_S)
-    SG[S_STRIDE], SG[S_ITERS] = STRIDE, iters
-    # regions (the Ruiz block's inputs): [(SGPR pair, array)], row-major with the simulated stride, 8 GiB apart
+    sg[S_STRIDE], sg[S_ITERS] = STRIDE, iters
     for k_, v_ in (sgpr or {}).items():
-        if v_ == "S":
-            setbase(k_, SIM_BASE_S)
-        elif v_ == "W":
-            setbase(k_, SIM_BASE_W)
+        if v_ in ("S", "W"):
+            setbase(k_, SIM_BASE_S if v_ == "S" else SIM_BASE_W)
         else:
-            SG[k_] = v_
-    if lds0 is not None:
-        lds[:len(lds0)] = lds0
+            sg[k_] = v_
     for q, (sreg, arr) in enumerate(regions or []):
         base = SIM_BASE_REGION + (q << 33)
         space.append((base, STRIDE, arr))
@@ -2104,274 +2023,40 @@ def _simulate(ins, W, S, iters, consts, regions=None, sgpr=None, lds0=None, ret_
     rho0 = f32(consts[3] if len(consts) > 3 else 0.1)
     for reg, val in ((S_ALPHA, f32(alpha)), (S_OMA, f32(f32(1.0) - f32(alpha))), (S_SIGMA, f32(sigma)), (S_RINVEQ, f32(rinv_eq)),
                      (S_RHO0, rho0), (S_RINV0, f32(1.0 / float(rho0))), (S_RHOEQ, f32(1e3 * float(rho0)))):
-        SG.setdefault(reg, f32bits(float(val)))
+        sg.setdefault(reg, f32bits(float(val)))
+    if lds is None:
+        lds = np.zeros(640, np.float32)
+    if lds0 is not None:
+        lds[:len(lds0)] = lds0
+    return isasim.Machine(ins, regions=space, sgpr=sg, vgpr={0: 0, V_LANE: 0, V_RLANE: 0}, lds=lds.view(np.uint32).reshape(1, -1)), lds
 
-    def sval(x):
-        if isinstance(x, int):
-            return x
-        if x.startswith("s["):
-            lo = int(x[2:x.index(":")])
-            return SG.get(lo, 0) | (SG.get(lo + 1, 0) << 32)
-        return SG.get(int(x[1:]), 0)
 
-    def bits2f(b):
-        return np.frombuffer(struct.pack("<I", int(b) & 0xFFFFFFFF), f32)[0]
-
-    def fval(x):
-        if isinstance(x, float):
-            return f32(x)                       # inline constant
-        neg = x.startswith("-")
-        if neg:
-            x = x[1:]
-        if x.startswith("|"):
-            val = abs(fval(x[1:-1]))
-        else:
-            val = bits2f(V[int(x[1:])]) if x[0] == "v" else bits2f(SG[int(x[1:])])
-        return -val if neg else val
-
-    def setf(x, val):
-        V[int(x[1:])] = f32bits(float(f32(val)))
-
-    def gaddr(t):
-        """(array, index) of a global access (mnemonic, data, v_off, s[base:base+1], imm): base + zext(v_off) + imm"""
-        addr = (sval(t[3]) + int(V[int(t[2][1:])]) + t[4]) & 0xFFFFFFFFFFFFFFFF
-        for base, stride, arr in space:
-            if base <= addr < base + len(arr) * stride and (addr - base) % stride == 0:
-                return arr, (addr - base) // stride
-        raise AddressFault("%r touches 0x%016x, outside every array of the call" % (ins[pc], addr))
-
-    def ldsword(basereg, off):
-        byte = int(V[int(basereg[1:])]) + off
-        return (byte // 1024) * 4 + (byte % 1024) // 4
-
-    # completion model: LDS operations and VMEM loads complete in issue order; a register that an outstanding load will
-    # write must not be read or written before an s_waitcnt has retired that load
-    pend = {"lgkmcnt": [], "vmcnt": []}
-
-    def regs_of(x):
-        if not isinstance(x, str):
-            return set()
-        x = x.lstrip("-").strip("|")
-        if x.startswith("v["):
-            lo, hi = x[2:-1].split(":")
-            return {("v", r) for r in range(int(lo), int(hi) + 1)}
-        if x[0] in "va" and x[1:].isdigit():
-            return {(x[0], int(x[1:]))}
-        return set()
-
-    def check(used):
-        for q in pend.values():
-            for dst in q:
-                assert not (dst & used), ("register used before its load was waited for", ins[pc], sorted(dst & used))
-
-    pc = nexec = 0
-    while pc < len(ins):
-        t = ins[pc]
-        m = t[0]
-        nexec += 1
-        assert nexec < 3000000, "runaway program"
-        if m == "s_waitcnt":
-            for part in t[1].split():
-                name, val = part[:-1].split("(")
-                del pend[name][:max(0, len(pend[name]) - int(val))]
-        elif m[0] == "v" or m.startswith("ds_") or m.startswith("global_"):
-            used = set().union(*[regs_of(x) for x in t[1:]])
-            check(used)
-            if m not in ("ds_read_b128", "ds_read_b32"):   # (a word fetched from LDS counts as READ when its register is consumed: a
-                wr_only = regs_of(t[1]) if m in ("global_load_dword", "v_mov_b32", "v_accvgpr_read_b32") else set()
-                for r_ in wr_only:            # quad may carry a neighbour's words that this wave never looks at; a register
-                    src_word.pop(r_, None)    # that is overwritten no longer stands for the word)
-                for r_ in used - wr_only:
-                    if r_ in src_word:
-                        if src_phase.get(r_, phase[0]) == phase[0]:
-                            log_r.add(src_word[r_])
-                        else:                 # fetched before a barrier, looked at behind it: the access belongs to THAT phase
-                            log_late.add((src_phase[r_], src_word[r_]))
-            if m in ("ds_read_b128", "ds_read_b32"):
-                pend["lgkmcnt"].append(regs_of(t[1]))
-            elif m.startswith("ds_write") or m == "ds_min_f32":
-                pend["lgkmcnt"].append(set())
-            elif m == "global_load_dword":
-                pend["vmcnt"].append(regs_of(t[1]))
-            elif m == "global_store_dword":
-                pend["vmcnt"].append(set())
-        if m in ("label", "s_waitcnt", "s_nop"):
-            pass
-        elif m == "s_barrier":
-            assert not pend["lgkmcnt"], ("s_barrier with LDS operations in flight: another wave may not see them", pc)
-            yield pc
-            phase[0] += 1
-        elif m == "v_mov_b32":
-            V[int(t[1][1:])] = (t[2] if isinstance(t[2], int) else f32bits(t[2]) if isinstance(t[2], float)
-                                else SG[int(t[2][1:])] if t[2][0] == "s" else V[int(t[2][1:])])
-        elif m == "v_cmp_nlt_f32":
-            SG["vcc"] = int(not (fval(t[2]) < fval(t[3])))
-        elif m == "v_cmp_lt_f32":
-            SG["vcc"] = int(fval(t[2]) < fval(t[3]))
-        elif m == "v_cmp_gt_f32":
-            SG["vcc"] = int(fval(t[2]) > fval(t[3]))
-        elif m == "v_cmp_eq_f32":
-            SG["vcc"] = int(fval(t[2]) == fval(t[3]))
-        elif m == "v_cmp_neq_f32":
-            SG["vcc"] = int(not (fval(t[2]) == fval(t[3])))
-        elif m == "v_cndmask_b32_e64":
-            bits = lambda x: f32bits(x) if isinstance(x, float) else x if isinstance(x, int) else int(V[int(x[1:])])
-            V[int(t[1][1:])] = bits(t[3]) if SG["vcc"] else bits(t[2])
-        elif m == "v_cvt_f32_i32":
-            setf(t[1], float(sval(t[2])))
-        elif m == "v_cndmask_b32":
-            src0 = f32bits(t[2]) if isinstance(t[2], float) else t[2] if isinstance(t[2], int) else int(V[int(t[2][1:])])
-            V[int(t[1][1:])] = int(V[int(t[3][1:])]) if SG["vcc"] else src0
-        elif m == "v_rsq_f32":
-            setf(t[1], 1.0 / np.sqrt(np.float64(fval(t[2]))))
-        elif m == "v_rcp_f32":
-            setf(t[1], 1.0 / np.float64(fval(t[2])))
-        elif m == "v_accvgpr_write_b32":
-            A[int(t[1][1:])] = V[int(t[2][1:])]
-        elif m == "s_mov_b32":
-            SG[int(t[1][1:])] = t[2] if isinstance(t[2], int) else sval(t[2])
-        elif m == "s_mov_b64":
-            lo = int(t[1][2:t[1].index(":")])
-            val = sval(t[2])
-            SG[lo], SG[lo + 1] = val & 0xFFFFFFFF, val >> 32
-        elif m == "s_mul_i32":
-            SG[int(t[1][1:])] = (sval(t[2]) * sval(t[3])) & 0xFFFFFFFF
-        elif m == "s_mul_hi_u32":
-            SG[int(t[1][1:])] = ((sval(t[2]) * sval(t[3])) >> 32) & 0xFFFFFFFF
-        elif m == "s_add_u32":
-            r = sval(t[2]) + sval(t[3])
-            SG[int(t[1][1:])] = r & 0xFFFFFFFF
-            scc = r >> 32
-        elif m == "s_addc_u32":
-            r = sval(t[2]) + sval(t[3]) + scc
-            SG[int(t[1][1:])] = r & 0xFFFFFFFF
-            scc = r >> 32
-        elif m == "s_sub_i32":
-            SG[int(t[1][1:])] = (sval(t[2]) - sval(t[3])) & 0xFFFFFFFF
-        elif m in ("s_cmp_gt_i32", "s_cmp_lt_i32"):
-            a = sval(t[1])
-            a = a - (1 << 32) if a & 0x80000000 else a
-            scc = int(a > sval(t[2])) if m == "s_cmp_gt_i32" else int(a < sval(t[2]))
-        elif m == "s_cmp_lg_u32":
-            scc = int(sval(t[1]) != sval(t[2]))
-        elif m == "s_branch":
-            lab = t[1][:-1]
-            pc = min(c for c in labels[lab] if c > pc)
-        elif m == "s_cbranch_scc1":
-            if scc:
-                lab, d = t[1][:-1], t[1][-1]
-                cands = labels[lab]
-                pc = min(c for c in cands if c > pc) if d == "f" else max(c for c in cands if c < pc)
-        elif m == "v_add_u32":
-            V[int(t[1][1:])] = (t[2] + int(V[int(t[3][1:])])) & 0xFFFFFFFF
-        elif m == "v_and_b32":
-            V[int(t[1][1:])] = t[2] & int(V[int(t[3][1:])])
-        elif m == "v_readfirstlane_b32":
-            SG[int(t[1][1:])] = int(V[int(t[2][1:])])
-        elif m == "v_or_b32":
-            V[int(t[1][1:])] = int(V[int(t[2][1:])]) | int(V[int(t[3][1:])])
-        elif m == "v_cmp_ne_u32":
-            SG["vcc"] = int(t[2] != int(V[int(t[3][1:])]))
-        elif m == "s_cbranch_vccz":
-            if not SG["vcc"]:
-                lab, d = t[1][:-1], t[1][-1]
-                cands = labels[lab]
-                pc = min(c for c in cands if c > pc) if d == "f" else max(c for c in cands if c < pc)
-        elif m == "s_cbranch_vccnz":
-            if SG["vcc"]:
-                lab, d = t[1][:-1], t[1][-1]
-                cands = labels[lab]
-                pc = min(c for c in cands if c > pc) if d == "f" else max(c for c in cands if c < pc)
-        elif m == "v_lshrrev_b32":
-            V[int(t[1][1:])] = int(V[int(t[3][1:])]) >> t[2]
-        elif m == "global_load_dword":
-            arr, row = gaddr(t)
-            b = f32bits(float(arr[row]))
-            if t[1][0] == "a":
-                A[int(t[1][1:])] = b
-            else:
-                V[int(t[1][1:])] = b
-        elif m == "global_store_dword":
-            arr, row = gaddr((t[0], None, t[1], t[3], t[4]))
-            arr[row] = bits2f(V[int(t[2][1:])])
-        elif m == "ds_read_b128":
-            lo = int(t[1][2:t[1].index(":")])
-            w = ldsword(t[2], t[3])
-            for h in range(4):
-                V[lo + h] = f32bits(float(lds[w + h]))
-                src_word[("v", lo + h)] = w + h
-                src_phase[("v", lo + h)] = phase[0]
-        elif m == "ds_read_b32":
-            w = ldsword(t[2], t[3])
-            V[int(t[1][1:])] = f32bits(float(lds[w]))
-            src_word[("v", int(t[1][1:]))] = w
-            src_phase[("v", int(t[1][1:]))] = phase[0]
-        elif m == "ds_write_b128":
-            lo = int(t[2][2:t[2].index(":")])
-            w = ldsword(t[1], t[3])
-            for h in range(4):
-                lds[w + h] = bits2f(V[lo + h])
-            log_w.update(range(w, w + 4))
-        elif m == "ds_write_b32":
-            lds[ldsword(t[1], t[3])] = bits2f(V[int(t[2][1:])])
-            log_w.add(ldsword(t[1], t[3]))
-        elif m == "ds_min_f32":               # LDS float-min atomic (no return): other waves may do the same to the word
-            w = ldsword(t[1], t[3])
-            lds[w] = min(lds[w], bits2f(V[int(t[2][1:])]))
-            log_a.add(w)
-        elif m == "ds_write_b64":
-            lo = int(t[2][2:t[2].index(":")])
-            w = ldsword(t[1], t[3])
-            lds[w], lds[w + 1] = bits2f(V[lo]), bits2f(V[lo + 1])
-            log_w.update((w, w + 1))
-        elif m in ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32"):
-            d = t[-1]
-            srcs = t[2:-1]
-            dlo = int(t[1][2:t[1].index(":")])
-
-            def half(x, sel):
-                lo_ = int(x[2:x.index(":")])
-                return bits2f(V[lo_ + sel]) if x[0] == "v" else bits2f(SG[lo_ + sel])
-            out2 = []
-            for hi in (0, 1):
-                sel = d["op_sel_hi"] if hi else d["op_sel"]
-                ng = d["neg_hi"] if hi else d["neg_lo"]
-                vals = [np.float64(half(x, sel[q])) * (-1 if ng[q] else 1) for q, x in enumerate(srcs)]
-                if m == "v_pk_fma_f32":
-                    out2.append(f32(vals[0] * vals[1] + vals[2]))
-                elif m == "v_pk_mul_f32":
-                    out2.append(f32(f32(vals[0]) * f32(vals[1])))
-                else:
-                    out2.append(f32(f32(vals[0]) + f32(vals[1])))
-            V[dlo], V[dlo + 1] = f32bits(float(out2[0])), f32bits(float(out2[1]))     # both halves from the OLD registers
-        elif m == "v_accvgpr_read_b32":
-            V[int(t[1][1:])] = A[int(t[2][1:])]
-        elif m == "v_fma_f32":
-            setf(t[1], np.float64(fval(t[2])) * np.float64(fval(t[3])) + np.float64(fval(t[4])))
-        elif m == "v_fmac_f32":
-            setf(t[1], np.float64(fval(t[2])) * np.float64(fval(t[3])) + np.float64(fval(t[1])))
-        elif m == "v_mul_f32":
-            setf(t[1], f32(fval(t[2])) * f32(fval(t[3])))
-        elif m == "v_sub_f32":
-            setf(t[1], f32(fval(t[2])) - f32(fval(t[3])))
-        elif m == "v_add_f32":
-            setf(t[1], f32(fval(t[2])) + f32(fval(t[3])))
-        elif m == "v_max_f32":
-            setf(t[1], max(fval(t[2]), fval(t[3])))
-        elif m == "v_min_f32":
-            setf(t[1], min(fval(t[2]), fval(t[3])))
-        elif m == "v_max3_f32":
-            setf(t[1], max(fval(t[2]), fval(t[3]), fval(t[4])))
-        elif m == "v_min3_f32":
-            setf(t[1], min(fval(t[2]), fval(t[3]), fval(t[4])))
-        else:
-            raise ValueError("unknown instruction %r" % (t,))
-        pc += 1
+def simulate(ins, W, S, iters, consts, ret_agpr=False, count=None, **kw):
+    """One wave (see _machine for the arguments). Runs the program and returns the lane's LDS words (x, y, z, x_prev,
+    delta_y are left there), and the AGPRs with ret_agpr; count: a list that gets the executed instruction count."""
+    from . import isasim
+    m, lds = _machine(ins, W, S, iters, consts, **kw)
+    isasim.run(m)
     if count is not None:
-        count.append(nexec)          # instructions executed (which variant of a loop ran)
+        count.append(m.nexec)          # instructions executed (which variant of a loop ran)
     if ret_agpr:
-        return lds, np.array([bits2f(b) for b in A], np.float32)
+        return lds, m.A[0].view(np.float32).copy()
     return lds
+
+
+def simulate_group(ins, nw, W, S, iters, consts, wave_sgpr, **kw):
+    """nw waves of one workgroup run `ins` on the same LDS slots and the same global arrays (wave w gets SGPR `wave_sgpr` =
+    w), each up to its next s_barrier in turn, with the race checks of isasim.run_group. Returns the shared LDS words,
+    the per-wave executed instruction counts and the number of barriers."""
+    from . import isasim
+    lds = np.zeros(640, np.float32)
+    lds0 = kw.pop("lds0", None)
+    if lds0 is not None:
+        lds[:len(lds0)] = lds0
+    ms = [_machine(ins, W, S, iters, consts, **dict(kw, sgpr={**(kw.get("sgpr") or {}), wave_sgpr: w}, lds=lds))[0]
+          for w in range(nw)]
+    nbar = isasim.run_group(ms)
+    return lds, [m.nexec for m in ms], nbar
 
 
 def reference_iterations(p, d, iters, alpha, sigma):

@@ -33,7 +33,6 @@ differs from QDLDL's column sweep); every other operation is the one-lane iterat
 
 Reference mapping: template/uprightmpc2/osqp.c:354-370, auxil.c:164-228, qdldl.c:250-293 (through asmgen.body).
 """
-import numpy as np
 
 from . import symbolic
 from .asmgen import (A_D, A_L, A_LO, A_M, A_Q, NLDS, S_ALPHA, S_CNT, S_ITERS, S_OMA, S_RINV, S_SIGMA, V_W, V_WZ, V_X,
@@ -478,222 +477,12 @@ def section(e, plan, label):
 # ---------------------------------------------------------------------------------------------------------------------
 def simulate(ins, pc, V, A, lds, S, max_exec=400000):
     """ins[pc] is ("quad_begin",). V, A: uint32 [4][256]; lds: uint32 [4][NLDS] (each lane's own slice); S: SGPR dict of
-    the calling interpreter (scalar constants, S_ITERS). Runs to ("quad_end",) and returns (pc behind it, executed count).
-    EXEC is modelled per lane of the quad; a DPP read of a lane that is masked off raises (gfx9: the write would be
-    dropped -- the generator must never rely on it)."""
-    f32, u32 = np.float32, np.uint32
-    asf = lambda b: np.array(b, u32).view(f32)
-    bits = lambda x: np.array(x, f32).view(u32)
-    exec_ = np.ones(4, bool)
-    entry_exec = exec_.copy()
-    masks = {}
-    scc = 0
-    labels = {}
-    for k, t in enumerate(ins):
-        if t[0] == "label":
-            labels.setdefault(t[1], []).append(k)
-    vi = lambda x: int(x[1:])
-
-    def sval(x):
-        if isinstance(x, float):
-            return f32(x)
-        if isinstance(x, int):
-            assert x == 0
-            return f32(0)
-        return asf(u32(S.get(int(x[1:]), 0) & 0xFFFFFFFF))
-
-    def fsrc(x):
-        """float32 [4] of a VALU source operand"""
-        if isinstance(x, (int, float)):
-            return np.full(4, sval(x), f32)
-        neg = x.startswith("-")
-        if neg:
-            x = x[1:]
-        ab = x.startswith("|")
-        if ab:
-            x = x[1:-1]
-        val = asf(V[:, vi(x)]) if x[0] == "v" else np.full(4, sval(x), f32)
-        if ab:
-            val = np.abs(val)
-        return -val if neg else val
-
-    def setv(x, val):
-        r = vi(x)
-        V[exec_, r] = bits(np.asarray(val, f32))[exec_]
-
-    def half(x, sel):
-        lo = int(x[2:x.index(":")])
-        if x[0] == "v":
-            return asf(V[:, lo + sel]).astype(np.float64)
-        return np.full(4, np.float64(asf(u32(S.get(lo + sel, 0)))))
-
-    def dpp_src(reg, mod):
-        """reg: a register number, or an operand string with modifiers ("|v12|")"""
-        neg = ab = False
-        if isinstance(reg, str):
-            neg = reg.startswith("-")
-            reg = reg[1:] if neg else reg
-            ab = reg.startswith("|")
-            reg = vi(reg[1:-1] if ab else reg)
-        qp = [int(c) for c in mod[mod.index("[") + 1:mod.index("]")].split(",")]
-        for ln in range(4):
-            if exec_[ln] and not exec_[qp[ln]]:
-                raise AssertionError("DPP read of a masked-off lane: %r" % (mod,))
-        val = asf(V[qp, reg])
-        if ab:
-            val = np.abs(val)
-        return -val if neg else val
-    vcc = np.zeros(4, bool)
-    nexec = 0
-    pend = []           # outstanding LDS operations in issue order: the registers a read will write (writes: empty)
-    import re as _re
-
-    def regs_of(x):
-        if not isinstance(x, str):
-            return set()
-        x = x.lstrip("-")
-        mm = _re.fullmatch(r"v\[(\d+):(\d+)\]", x)
-        if mm:
-            return set(range(int(mm.group(1)), int(mm.group(2)) + 1))
-        return {int(x[1:])} if _re.fullmatch(r"v\d+", x) else set()
-    assert ins[pc][0] == "quad_begin"
-    pc += 1
-    with np.errstate(all="ignore"):
-        while ins[pc][0] != "quad_end":
-            t = ins[pc]
-            m = t[0]
-            if m in ("label", "kill"):
-                pc += 1
-                continue
-            nexec += 1
-            assert nexec < max_exec, "runaway quad section"
-            if m[0] == "v" or m.startswith("ds_"):
-                used = set().union(*[regs_of(x) for x in t[1:]])
-                for dst in pend:
-                    assert not (dst & used), ("register used before its LDS read was waited for", t)
-                if m.startswith("ds_read"):
-                    pend.append(regs_of(t[1]))
-                elif m.startswith("ds_write"):
-                    pend.append(set())
-            if m == "s_waitcnt":
-                for part in t[1].split():
-                    if part.startswith("lgkmcnt("):
-                        del pend[:max(0, len(pend) - int(part[8:-1]))]
-            elif m == "s_nop":
-                pass
-            elif m == "s_mov_b32":
-                S[int(t[1][1:])] = (t[2] & 0xFFFFFFFF) if isinstance(t[2], int) else S.get(int(t[2][1:]), 0)
-            elif m == "s_mov_b64":
-                if t[2] == "exec":
-                    masks[t[1]] = exec_.copy()
-                else:
-                    assert t[1] == "exec"
-                    exec_ = masks[t[2]].copy()
-            elif m == "s_and_b64":
-                # lane-class mask & entry EXEC: the low word of the first source was set by s_mov_b32 just before
-                lo = int(t[2][2:t[2].index(":")])
-                word = S[lo]
-                masks[t[1]] = np.array([(word >> ln) & 1 for ln in range(4)], bool) & masks[t[3]]
-            elif m == "s_or_b64":
-                masks[t[1]] = masks[t[2]] | masks[t[3]]
-            elif m in ("s_sub_i32", "s_add_i32"):
-                a = S.get(int(t[2][1:]), 0) if isinstance(t[2], str) else t[2]
-                b = S.get(int(t[3][1:]), 0) if isinstance(t[3], str) else t[3]
-                S[int(t[1][1:])] = (a - b if m == "s_sub_i32" else a + b) & 0xFFFFFFFF
-            elif m in ("s_cmp_lt_i32", "s_cmp_gt_i32"):
-                sx = lambda x: (lambda w: w - (1 << 32) if w & 0x80000000 else w)(S.get(int(x[1:]), 0) if isinstance(x, str) else x & 0xFFFFFFFF)
-                a, b = sx(t[1]), sx(t[2])
-                scc = int(a < b) if m == "s_cmp_lt_i32" else int(a > b)
-            elif m == "s_cbranch_scc1":
-                if scc:
-                    lab, d = t[1][:-1], t[1][-1]
-                    c = labels[lab]
-                    pc = min(x for x in c if x > pc) if d == "f" else max(x for x in c if x < pc)
-            elif m == "ds_read_b128":
-                lo = int(t[1][2:t[1].index(":")])
-                w0 = t[3] // 1024 * 4
-                for ln in range(4):
-                    if exec_[ln]:
-                        V[ln, lo:lo + 4] = lds[ln, w0:w0 + 4]
-            elif m == "ds_write_b128":
-                lo = int(t[2][2:t[2].index(":")])
-                w0 = t[3] // 1024 * 4
-                for ln in range(4):
-                    if exec_[ln]:
-                        lds[ln, w0:w0 + 4] = V[ln, lo:lo + 4]
-            elif m == "v_accvgpr_read_b32":
-                V[exec_, vi(t[1])] = A[exec_, int(t[2][1:])]
-            elif m == "v_accvgpr_write_b32":
-                A[exec_, int(t[1][1:])] = V[exec_, vi(t[2])]
-            elif m == "v_mov_b32":
-                if isinstance(t[2], str) and t[2][0] == "v":
-                    V[exec_, vi(t[1])] = V[exec_, vi(t[2])]
-                else:
-                    setv(t[1], fsrc(t[2]))
-            elif m == "v_mov_b32_dpp":
-                setv(t[1], dpp_src(vi(t[2]), t[3]))
-            elif m == "v_fmac_f32":
-                setv(t[1], (fsrc(t[2]).astype(np.float64) * fsrc(t[3]).astype(np.float64) + fsrc(t[1]).astype(np.float64)).astype(f32))
-            elif m == "v_fmac_f32_dpp":
-                a = dpp_src(vi(t[2]), t[4]).astype(np.float64)
-                setv(t[1], (a * fsrc(t[3]).astype(np.float64) + fsrc(t[1]).astype(np.float64)).astype(f32))
-            elif m == "v_fma_f32":
-                setv(t[1], (fsrc(t[2]).astype(np.float64) * fsrc(t[3]).astype(np.float64) + fsrc(t[4]).astype(np.float64)).astype(f32))
-            elif m == "v_mul_f32":
-                setv(t[1], fsrc(t[2]) * fsrc(t[3]))
-            elif m == "v_add_f32":
-                setv(t[1], fsrc(t[2]) + fsrc(t[3]))
-            elif m == "v_sub_f32":
-                setv(t[1], fsrc(t[2]) - fsrc(t[3]))
-            elif m in ("v_max_f32", "v_min_f32", "v_max_f32_dpp"):
-                a, b = (dpp_src(t[2], t[4]) if m.endswith("_dpp") else fsrc(t[2])), fsrc(t[3])
-                r = np.where(b != b, a, np.where(a != a, b, np.minimum(a, b) if m == "v_min_f32" else np.maximum(a, b)))
-                setv(t[1], r)
-            elif m == "v_max3_f32":
-                a, b, c = fsrc(t[2]), fsrc(t[3]), fsrc(t[4])
-                setv(t[1], np.fmax(np.fmax(a, b), c))
-            elif m == "v_and_b32":
-                assert t[2] == 0x7fffffff
-                V[exec_, vi(t[1])] = (V[:, vi(t[3])] & u32(0x7fffffff))[exec_]
-            elif m in ("v_mul_f32_dpp", "v_add_f32_dpp"):
-                a, b = dpp_src(t[2], t[4]), fsrc(t[3])
-                setv(t[1], a * b if m == "v_mul_f32_dpp" else a + b)
-            elif m == "v_cmp_lt_f32":
-                assert t[1] == "vcc"
-                vcc[exec_] = (fsrc(t[2]) < fsrc(t[3]))[exec_]
-            elif m == "v_cndmask_b32":
-                assert t[4] == "vcc"
-                a, b = fsrc(t[2]), fsrc(t[3])
-                setv(t[1], np.where(vcc, b, a))
-            elif m == "v_rsq_f32":
-                setv(t[1], (1.0 / np.sqrt(fsrc(t[2]).astype(np.float64))).astype(f32))
-            elif m == "v_rcp_f32":
-                setv(t[1], f32(1.0) / fsrc(t[2]))
-            elif m == "v_pk_mov_b32":
-                d = t[-1]
-                lo = int(t[1][2:t[1].index(":")])
-                r0, r1 = half(t[2], d["op_sel"][0]), half(t[3], d["op_sel"][1])
-                V[exec_, lo] = bits(r0.astype(f32))[exec_]
-                V[exec_, lo + 1] = bits(r1.astype(f32))[exec_]
-            elif m in ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32"):
-                d = t[-1]
-                srcs = t[2:-1]
-                dlo = int(t[1][2:t[1].index(":")])
-                res = []
-                for hi in (0, 1):
-                    sel = d["op_sel_hi"] if hi else d["op_sel"]
-                    ng = d["neg_hi"] if hi else d["neg_lo"]
-                    vals = [half(x, sel[q]) * (-1 if ng[q] else 1) for q, x in enumerate(srcs)]
-                    if m == "v_pk_fma_f32":
-                        res.append((vals[0] * vals[1] + vals[2]).astype(f32))
-                    elif m == "v_pk_mul_f32":
-                        res.append(vals[0].astype(f32) * vals[1].astype(f32))
-                    else:
-                        res.append(vals[0].astype(f32) + vals[1].astype(f32))
-                V[exec_, dlo] = bits(res[0])[exec_]
-                V[exec_, dlo + 1] = bits(res[1])[exec_]
-            else:
-                raise ValueError("unknown instruction in the quad section: %r" % (t,))
-            pc += 1
-    assert exec_.all() and not pend, "EXEC not restored / LDS operations outstanding at the end of the quad section"
-    return pc + 1, nexec
+    the calling code (scalar constants, S_ITERS). Runs the section on the four lanes of ONE quad to ("quad_end",) and
+    returns (pc behind it, executed count); the register files and slices are updated in place."""
+    from . import isasim
+    m = isasim.Machine(ins, 4, sgpr=S, lds=lds, max_exec=max_exec, V=V, A=A)
+    for _ in m.run(pc + 1):
+        raise AssertionError("s_barrier inside a quad section")
+    assert m.exec.all() and not any(dst for pend in m.pend.values() for dst in pend), \
+        "EXEC not restored / loads outstanding at the end of the quad section"
+    return m.pc + 1, m.nexec

@@ -26,7 +26,6 @@ Arithmetic = asmgen64.body's, operation for operation, except the order in which
 
 Reference mapping: template/uprightmpc2/osqp.c:354-370, auxil.c:164-228, qdldl.c:250-293 (through asmgen64.body).
 """
-import struct
 
 import numpy as np
 
@@ -431,208 +430,19 @@ def section(e, plan, s):
 # ---------------------------------------------------------------------------------------------------------------------
 def simulate(ins, pc, V, A, lds, S, tab, max_exec=400000):
     """ins[pc] == ("quad_begin",). V, A: uint32 [4][256]; lds: float64 [4][320], each lane's own slice by WORD; S: the
-    calling interpreter's SGPR dict (constants as 64-bit pairs, S_ITERS); tab: table() of the plan. LDS addresses are
-    taken relative to the lane's base (v1 must be equal in the four images: the caller runs with v1 = 0). Returns
-    (pc behind ("quad_end",), executed instructions)."""
-    from fractions import Fraction
-    u32 = np.uint32
-    exec_ = np.ones(4, bool)
-    vcc = np.zeros(4, bool)
-    masks, labels, scc = {}, {}, 0
-    for k, t in enumerate(ins):
-        if t[0] == "label":
-            labels.setdefault(t[1], []).append(k)
+    calling code's SGPRs (constants as 64-bit pairs, S_ITERS); tab: table() of the plan. Returns (pc behind
+    ("quad_end",), executed instructions)."""
+    from . import isasim
     TAB_BASE = 1 << 44
-    S[S_TAB], S[S_TAB + 1] = TAB_BASE & 0xFFFFFFFF, TAB_BASE >> 32
-    vi = lambda x: int(x[1:])
-    lohi = lambda x: int(x[2:x.index(":")])
-
-    def f64(lo, hi):
-        return struct.unpack("<d", struct.pack("<Q", int(lo) | (int(hi) << 32)))[0]
-
-    def getd(x, ln):
-        if isinstance(x, float):
-            return x
-        neg = x.startswith("-")
-        if neg:
-            x = x[1:]
-        if x.startswith("|"):
-            return (-1.0 if neg else 1.0) * abs(getd(x[1:-1], ln))
-        lo = lohi(x)
-        val = f64(V[ln, lo], V[ln, lo + 1]) if x[0] == "v" else f64(S[lo], S[lo + 1])
-        return -val if neg else val
-
-    def setd(x, ln, val):
-        lo = lohi(x)
-        b = struct.unpack("<Q", struct.pack("<d", float(val)))[0]
-        V[ln, lo], V[ln, lo + 1] = b & 0xFFFFFFFF, b >> 32
-
-    def fma(a, b, c):
-        if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
-            return a * b + c
-        return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-    def word_of(byte):
-        assert byte % 8 == 0 and 0 <= byte < 160 * 1024
-        return (byte // 1024) * 2 + (byte % 1024) // 8
-    pend = []        # outstanding LDS reads: sets of (lane-independent) destination registers, in issue order
-    nexec = 0
-    assert ins[pc] == ("quad_begin",)
-    pc += 1
-    while ins[pc] != ("quad_end",):
-        t = ins[pc]
-        m = t[0]
-        if m == "label":
-            pc += 1
-            continue
-        nexec += 1
-        assert nexec < max_exec, "runaway quad section"
-        if m[0] == "v" or m.startswith("ds_"):
-            used = set()
-            for x in t[1:]:
-                if isinstance(x, str):
-                    y = x.lstrip("-")
-                    if y.startswith("v["):
-                        used |= set(range(lohi(y), int(y[y.index(":") + 1:-1]) + 1))
-                    elif y[0] == "v" and y[1:].isdigit():
-                        used.add(int(y[1:]))
-            for dst in pend:
-                assert not (dst & used), ("register used before its LDS read was waited for", t)
-        if m == "s_waitcnt":
-            for part in t[1].split():
-                name, val = part[:-1].split("(")
-                if name == "lgkmcnt":
-                    del pend[:max(0, len(pend) - int(val))]
-        elif m == "s_nop":
-            pass
-        elif m == "s_mov_b32":
-            S[int(t[1][1:])] = (t[2] & 0xFFFFFFFF) if isinstance(t[2], int) else S.get(int(t[2][1:]), 0)
-        elif m == "v_cmp_nlt_f64":
-            assert t[1] == "vcc"
-            for ln in range(4):
-                if exec_[ln]:
-                    vcc[ln] = not (getd(t[2], ln) < getd(t[3], ln))
-        elif m == "v_cndmask_b32":
-            assert t[4] == "vcc"
-            for ln in range(4):
-                if exec_[ln]:
-                    a = u32(t[2]) if isinstance(t[2], int) else V[ln, vi(t[2])]
-                    V[ln, vi(t[1])] = V[ln, vi(t[3])] if vcc[ln] else a
-        elif m in ("v_rsq_f64", "v_rcp_f64"):
-            for ln in range(4):
-                if exec_[ln]:
-                    a = getd(t[2], ln)
-                    with np.errstate(all="ignore"):
-                        setd(t[1], ln, (1.0 / np.sqrt(a)) if m == "v_rsq_f64" else (np.float64(1.0) / np.float64(a)))
-        elif m == "s_mov_b64":
-            if t[2] == "exec":
-                masks[t[1]] = exec_.copy()
-            else:
-                assert t[1] == "exec"
-                exec_ = masks[t[2]].copy()
-        elif m == "s_and_b64":
-            word = S[lohi(t[2])]
-            masks[t[1]] = np.array([(word >> ln) & 1 for ln in range(4)], bool) & masks[t[3]]
-        elif m == "s_sub_i32":
-            a = S.get(int(t[2][1:]), 0) if isinstance(t[2], str) else t[2]
-            b = S.get(int(t[3][1:]), 0) if isinstance(t[3], str) else t[3]
-            S[int(t[1][1:])] = (a - b) & 0xFFFFFFFF
-        elif m in ("s_cmp_lt_i32", "s_cmp_gt_i32"):
-            sx = lambda x: (lambda w: w - (1 << 32) if w & 0x80000000 else w)(S.get(int(x[1:]), 0) if isinstance(x, str) else x & 0xFFFFFFFF)
-            scc = int(sx(t[1]) < sx(t[2])) if m == "s_cmp_lt_i32" else int(sx(t[1]) > sx(t[2]))
-        elif m == "s_cbranch_scc1":
-            if scc:
-                lab, d = t[1][:-1], t[1][-1]
-                c = labels[lab]
-                pc = min(x for x in c if x > pc) if d == "f" else max(x for x in c if x < pc)
-        elif m == "v_bfe_u32":
-            assert (t[3], t[4]) == (4, 2) and t[2] == "v1"
-            for ln in range(4):
-                if exec_[ln]:
-                    V[ln, vi(t[1])] = ln            # (lane & 3): the images are the four lanes of one quad
-        elif m == "v_mul_u32_u24":
-            for ln in range(4):
-                if exec_[ln]:
-                    V[ln, vi(t[1])] = (t[2] * int(V[ln, vi(t[3])])) & 0xFFFFFFFF
-        elif m == "v_add_u32":
-            for ln in range(4):
-                if exec_[ln]:
-                    a = t[2] if isinstance(t[2], int) else int(V[ln, vi(t[2])])
-                    V[ln, vi(t[1])] = (a + int(V[ln, vi(t[3])])) & 0xFFFFFFFF
-        elif m == "v_mov_b32":
-            for ln in range(4):
-                if exec_[ln]:
-                    V[ln, vi(t[1])] = u32(t[2]) if isinstance(t[2], int) else V[ln, vi(t[2])]
-        elif m == "v_mov_b32_dpp":
-            mod = t[3]
-            qp = [int(c) for c in mod[mod.index("[") + 1:mod.index("]")].split(",")]
-            old = V[:, vi(t[2])].copy()
-            for ln in range(4):
-                if exec_[ln]:
-                    assert exec_[qp[ln]], "DPP read of a masked-off lane"
-                    V[ln, vi(t[1])] = old[qp[ln]]
-        elif m == "v_accvgpr_read_b32":
-            V[exec_, vi(t[1])] = A[exec_, int(t[2][1:])]
-        elif m == "v_accvgpr_write_b32":
-            A[exec_, int(t[1][1:])] = V[exec_, vi(t[2])]
-        elif m == "global_load_dwordx4":
-            lo = lohi(t[1])
-            off = int(t[4].split(":")[1])
-            assert (S[S_TAB] | (S[S_TAB + 1] << 32)) == TAB_BASE
-            for ln in range(4):
-                if exec_[ln]:
-                    byte = int(V[ln, vi(t[2])]) + off
-                    assert byte % 4 == 0 and 0 <= byte // 4 + 3 < tab.size
-                    V[ln, lo:lo + 4] = tab.ravel()[byte // 4:byte // 4 + 4]
-        elif m == "ds_read_b128":
-            lo = lohi(t[1])
-            for ln in range(4):
-                if exec_[ln]:
-                    w = word_of(int(V[ln, vi(t[2])]) + t[3])
-                    for h in range(2):
-                        b = struct.unpack("<Q", struct.pack("<d", float(lds[ln, w + h])))[0]
-                        V[ln, lo + 2 * h], V[ln, lo + 2 * h + 1] = b & 0xFFFFFFFF, b >> 32
-            pend.append(set(range(lo, lo + 4)))
-        elif m == "ds_read_b64":
-            lo = lohi(t[1])
-            for ln in range(4):
-                if exec_[ln]:
-                    w = word_of(int(V[ln, vi(t[2])]) + t[3])
-                    b = struct.unpack("<Q", struct.pack("<d", float(lds[ln, w])))[0]
-                    V[ln, lo], V[ln, lo + 1] = b & 0xFFFFFFFF, b >> 32
-            pend.append({lo, lo + 1})
-        elif m == "ds_write_b64":
-            for ln in range(4):
-                if exec_[ln]:
-                    lds[ln, word_of(int(V[ln, vi(t[1])]) + t[3])] = getd(t[2], ln)
-            pend.append(set())
-        elif m == "ds_write_b128":
-            lo = lohi(t[2])
-            for ln in range(4):
-                if exec_[ln]:
-                    w = word_of(int(V[ln, vi(t[1])]) + t[3])
-                    for h in range(2):
-                        lds[ln, w + h] = f64(V[ln, lo + 2 * h], V[ln, lo + 2 * h + 1])
-            pend.append(set())
-        elif m in ("v_fma_f64", "v_mul_f64", "v_add_f64", "v_max_f64", "v_min_f64"):
-            for ln in range(4):
-                if not exec_[ln]:
-                    continue
-                a, b = getd(t[2], ln), getd(t[3], ln)
-                if m == "v_fma_f64":
-                    r = fma(a, b, getd(t[4], ln))
-                elif m == "v_mul_f64":
-                    r = a * b
-                elif m == "v_add_f64":
-                    r = a + b
-                else:
-                    r = max(a, b) if m == "v_max_f64" else min(a, b)
-                setd(t[1], ln, r)
-        else:
-            raise ValueError("unknown instruction in the fp64 quad section: %r" % (t,))
-        pc += 1
-    assert exec_.all() and not pend, "EXEC not restored / LDS reads outstanding at the end of the quad section"
-    return pc + 1, nexec
+    S = {**S, S_TAB: TAB_BASE & 0xFFFFFFFF, S_TAB + 1: TAB_BASE >> 32}
+    regions = [] if tab is None else [(TAB_BASE, 4, np.ascontiguousarray(tab, np.uint32).ravel())]
+    m = isasim.Machine(ins, 4, regions=regions, sgpr=S, lds=lds.view(np.uint32), max_exec=max_exec, V=V, A=A)
+    V[:, isasim.LANE_LDS_VGPR] = 16 * np.arange(4)
+    for _ in m.run(pc + 1):
+        raise AssertionError("s_barrier inside a quad section")
+    assert m.exec.all() and not any(dst for pend in m.pend.values() for dst in pend), \
+        "EXEC not restored / loads outstanding at the end of the quad section"
+    return m.pc + 1, m.nexec
 
 
 # =====================================================================================================================

@@ -2247,354 +2247,54 @@ def write(path=None, N=3, perm=None, quad=False):
 # ----------------------------------------------------------------------------------------------------------
 # CPU interpreter of the emitted stream (one lane), for tests/test_asm_step.py
 # ----------------------------------------------------------------------------------------------------------
+# What the quad sections hand back. The ADMM section (asmquad.py): the four lanes must agree on every one-lane home of
+# the loop's outputs, nothing else may be read again (poisoned); the L, 1/D, q homes in the AGPRs below A_LO were consumed,
+# bounds, thrust-row words and weights stay. The named sections (Ruiz passes, plant) list what they hand back in their
+# quad_end; everything else is as before, and the AGPRs must agree.
+_KEEP_V = {0, 1} | set(range(V_W, V_Z)) | set(range(V_Z + 2 * 3 * symbolic.NY, V_Z + 40))
+QUAD = {None: None}
+
+
+def _quad():
+    from . import isasim
+    if QUAD[None] is None:
+        QUAD.update({None: isasim.Quad(v=_KEEP_V, dead_v=set(range(256)) - _KEEP_V, a=range(A_LO, 256), dead_a=range(A_LO)),
+                     "ruiz": isasim.Quad(a=range(256)), "plant": isasim.Quad(a=range(256))})
+    return QUAD
+
+
+FLAT = ("taskf", "wl")      # plain word arrays (not [row][B]): the byte offset / 4 indexes them
+STRIDE = 4096
+# simulated device addresses with bit 31 of the low word set (like real ones): a half that gets sign-extended on its way
+# into an address lands outside every array and is caught
+PBASE = 0x00007E0080000000
+
+
 def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
     """arrays: name -> float32 / int32 numpy vector indexed by ROW (one robot), or None for a null pointer; ints /
     floats: the StepParams scalars (ints without `stride`). Runs the whole kernel; arrays are updated in place.
     Returns the executed instruction count (pseudo-instructions excluded)."""
     import numpy as np
-    f32, u32 = np.float32, np.uint32
-    STRIDE = 4096
-    V = np.zeros(256, u32)
-    A = np.zeros(256, u32)
-    S = {}
-    lds = np.zeros(NLDS, u32)
-    POISON = u32(0x7fc0dead)
-    V[:] = POISON
-    A[:] = POISON
-    names = list(PTRS)
-    # simulated device addresses with bit 31 of the low word set (like real ones): a half that gets sign-extended on its
-    # way into an address lands outside every array and is caught below
-    base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(names)}
+    from . import isasim
+    base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(PTRS)}
     ptr_xform = ptr_xform or (lambda a: a)
-    blob = bytearray(PARAM_BYTES)
+    blob = bytearray((PARAM_BYTES + 3) // 4 * 4)
     for n in PTRS:
         struct.pack_into("<Q", blob, OFF[n], ptr_xform(base_of[n]) if arrays.get(n) is not None else 0)
-    allints = dict(ints)
-    allints["stride"] = STRIDE
+    allints = dict(ints, stride=STRIDE)
     allints.setdefault("seq", 0)
     for n in INTS:
         struct.pack_into("<i", blob, OFF[n], int(allints[n]))
     for n in FLOATS:
         struct.pack_into("<f", blob, OFF[n], float(floats[n]))
-    PBASE = 0x00007E0080000000
-    S[S_PARAM], S[S_PARAM + 1] = PBASE & 0xFFFFFFFF, PBASE >> 32
-    V[0], V[1] = 0, 0
-    exec_ = 1
-    scc = 0
-    labels = {}
-    for k, t in enumerate(ins):
-        if t[0] == "label":
-            labels.setdefault(t[1], []).append(k)
-
-    def asf(bits):
-        return np.array([bits], u32).view(f32)[0]
-
-    def bits(val):
-        return np.array([val], f32).view(u32)[0]
-
-    def sreg(x):
-        if x == "vcc":
-            return 106
-        if x == "exec":
-            return 126
-        return int(x[2:x.index(":")]) if x.startswith("s[") else int(x[1:])
-
-    def s64(x):
-        if isinstance(x, int):
-            return x & 0xFFFFFFFFFFFFFFFF
-        if x == "exec":
-            return exec_
-        lo = sreg(x)
-        return (S.get(lo, 0) & 0xFFFFFFFF) | ((S.get(lo + 1, 0) & 0xFFFFFFFF) << 32)
-
-    def set64(x, val):
-        nonlocal exec_
-        if x == "exec":
-            exec_ = val & 1
-            return
-        lo = sreg(x)
-        S[lo], S[lo + 1] = val & 0xFFFFFFFF, (val >> 32) & 0xFFFFFFFF
-
-    def s32(x):
-        if isinstance(x, int):
-            return x & 0xFFFFFFFF
-        return S.get(sreg(x), 0) & 0xFFFFFFFF
-
-    def src_bits(x):
-        """raw 32 bits of an operand (no modifiers)"""
-        if isinstance(x, float):
-            return int(bits(f32(x)))
-        if isinstance(x, int):
-            return x & 0xFFFFFFFF
-        if x[0] == "v":
-            return int(V[int(x[1:])])
-        if x[0] == "s":
-            return s32(x)
-        raise ValueError(x)
-
-    def fsrc(x):
-        if isinstance(x, (int, float)) and not isinstance(x, bool):
-            if isinstance(x, int):
-                # integer inline constants used as float operands are only 0 here
-                assert x == 0, x
-                return f32(0)
-            return f32(x)
-        neg = x.startswith("-")
-        if neg:
-            x = x[1:]
-        ab = x.startswith("|")
-        if ab:
-            x = x[1:-1]
-        val = asf(u32(src_bits(x)))
-        if ab:
-            val = f32(abs(val))
-        return f32(-val) if neg else val
-
-    def setv(x, val):
-        V[int(x[1:])] = bits(f32(val))
-
-    def setvb(x, b):
-        V[int(x[1:])] = u32(b & 0xFFFFFFFF)
-
-    def half(x, sel):
-        lo = int(x[2:x.index(":")])
-        if x[0] == "v":
-            return asf(V[lo + sel])
-        return asf(u32(S.get(lo + sel, 0)))
-
-    FLAT = ("taskf", "wl")      # plain word arrays (not [row][B]): the byte offset / 4 indexes them
-
-    def mem(addr):
-        """array and element of a byte address: SGPR base (64 bits) + zero-extended VGPR offset + immediate, as the ISA forms
-        it; anything that is not an element of an array handed in is a fault (asmqp.AddressFault)"""
-        addr &= 0xFFFFFFFFFFFFFFFF
-        if PBASE <= addr < PBASE + PARAM_BYTES:
-            return None, addr - PBASE
-        for name in names:
-            arr = arrays.get(name)
-            if arr is None:
-                continue
-            stride = 4 if name in FLAT else STRIDE
-            off = addr - base_of[name]
-            if 0 <= off < len(arr) * stride and off % stride == 0:
-                return arr, off // stride
-        from .asmqp import AddressFault
-        raise AddressFault("%r touches 0x%016x, outside every array of the call" % (ins[pc], addr))
-
-    def setmask(dst, cond):
-        if dst == "vcc":
-            S[106], S[107] = int(bool(cond)), 0
-        else:
-            set64(dst, int(bool(cond)))
-
-    cmpf = {"lt": lambda a, b: a < b, "le": lambda a, b: a <= b, "gt": lambda a, b: a > b, "ge": lambda a, b: a >= b,
-            "eq": lambda a, b: a == b, "u": lambda a, b: (a != a) or (b != b)}
-    pc = nexec = 0
-    nquad = [0]
-    sections = {}
-    self_neq = 2 * 3 * symbolic.NY
-    simulate.last_quad_instructions = 0
-    simulate.last_quad_sections = sections
-    with np.errstate(all="ignore"):
-        while pc < len(ins):
-            t = ins[pc]
-            m = t[0]
-            if m == "kill":
-                V[int(t[1][1:])] = POISON
-                pc += 1
-                continue
-            if m == "label":
-                pc += 1
-                continue
-            if m == "quad_begin":
-                # the one-robot-per-quad section (asmquad.py): the four lanes of a quad have run everything so far
-                # redundantly, so each starts from THIS lane's registers, AGPRs and LDS slice; afterwards the four lanes must
-                # agree on every one-lane home of the loop's outputs, and nothing else may be read again (poisoned)
-                from . import asmquad
-                assert exec_ == 1
-                V4, A4, L4 = np.tile(V, (4, 1)), np.tile(A, (4, 1)), np.tile(lds, (4, 1))
-                pc, nq = asmquad.simulate(ins, pc, V4, A4, L4, S)
-                nexec += nq
-                nquad[0] += nq
-                sections[t[1] if len(t) > 1 else "admm"] = sections.get(t[1] if len(t) > 1 else "admm", 0) + nq
-                endm = ins[pc - 1]
-                if len(endm) > 1:           # a section that names what it hands back (the Ruiz passes): everything else is as before
-                    for r in endm[1]:
-                        assert (V4[1:4, r] == V4[0, r]).all(), "lanes of the quad disagree on v%d after the %s section" % (r, t[1])
-                        V[r] = V4[0, r]
-                    assert (A4[1:4] == A4[0]).all()
-                    continue
-                keep = set([0, 1]) | set(range(V_W, V_Z)) | set(range(V_Z + self_neq, V_Z + 40))
-                for r in range(256):
-                    if r in keep:
-                        assert (V4[1:4, r] == V4[0, r]).all(), "lanes of the quad disagree on v%d after the quad section" % r
-                        V[r] = V4[0, r]
-                    else:
-                        V[r] = POISON
-                assert (A4[1:4, A_LO:] == A4[0, A_LO:]).all()
-                A[:] = A4[0]
-                A[:A_LO] = POISON          # L, 1/D, q homes were consumed; bounds, thrust-row words and weights stay
-                continue
-            nexec += 1
-            assert nexec < max_exec, "runaway program"
-            if m in ("s_waitcnt", "s_nop", "buffer_wbl2"):
-                pass
-            elif m.startswith("s_load_dword"):
-                n = {"s_load_dword": 1, "s_load_dwordx2": 2, "s_load_dwordx4": 4, "s_load_dwordx8": 8, "s_load_dwordx16": 16}[m]
-                imm = int(t[4].split(":")[1]) if len(t) > 4 else 0
-                arr, off = mem(s64(t[2]) + (t[3] if isinstance(t[3], int) else s32(t[3])) + imm)
-                lo = sreg(t[1])
-                for k in range(n):
-                    if arr is None:
-                        S[lo + k] = struct.unpack_from("<I", blob, off + 4 * k)[0]
-                    else:
-                        S[lo + k] = int(bits(arr[off + k]))
-            elif m == "s_mov_b32":
-                S[sreg(t[1])] = s32(t[2])
-            elif m == "s_mov_b64":
-                set64(t[1], 0xFFFFFFFFFFFFFFFF if t[2] == -1 else s64(t[2]))
-                if t[1] != "exec" and t[2] == -1:
-                    set64(t[1], 1)
-            elif m == "s_mul_i32":
-                S[sreg(t[1])] = (s32(t[2]) * s32(t[3])) & 0xFFFFFFFF
-            elif m == "s_lshl_b32":
-                S[sreg(t[1])] = (s32(t[2]) << (s32(t[3]) & 31)) & 0xFFFFFFFF
-            elif m in ("s_add_i32", "s_sub_i32"):
-                a, b = s32(t[2]), s32(t[3])
-                S[sreg(t[1])] = (a + b if m == "s_add_i32" else a - b) & 0xFFFFFFFF
-            elif m in ("s_cmp_lt_i32", "s_cmp_gt_i32"):
-                a, b = s32(t[1]), s32(t[2])
-                a = a - (1 << 32) if a & 0x80000000 else a
-                b = b - (1 << 32) if b & 0x80000000 else b
-                scc = int(a < b) if m == "s_cmp_lt_i32" else int(a > b)
-            elif m in ("s_cmp_lg_u32", "s_cmp_eq_u32"):
-                scc = int((s32(t[1]) != s32(t[2])) == (m == "s_cmp_lg_u32"))
-            elif m == "s_cmp_eq_u64":
-                scc = int(s64(t[1]) == s64(t[2]))
-            elif m in ("s_and_b64", "s_or_b64", "s_andn2_b64"):
-                a, b = s64(t[2]) & 1, s64(t[3]) & 1
-                r = (a & b) if m == "s_and_b64" else (a | b) if m == "s_or_b64" else (a & (1 - b))
-                setmask(t[1], r) if t[1] == "vcc" else set64(t[1], r)
-                scc = int(r != 0)
-            elif m == "s_and_saveexec_b64":
-                set64(t[1], exec_)
-                exec_ = exec_ & (s64(t[2]) & 1)
-                scc = int(exec_ != 0)
-            elif m in ("s_branch", "s_cbranch_scc1", "s_cbranch_vccz", "s_cbranch_execz"):
-                take = m == "s_branch" or (m == "s_cbranch_scc1" and scc) or \
-                    (m == "s_cbranch_vccz" and (S.get(106, 0) & exec_) == 0) or (m == "s_cbranch_execz" and exec_ == 0)
-                if take:
-                    lab, d = t[1][:-1], t[1][-1]
-                    cands = labels[lab]
-                    pc = min(c for c in cands if c > pc) if d == "f" else max(c for c in cands if c < pc)
-            elif not exec_ and m[0] in "vgd":
-                pass                                      # the lane is masked off
-            elif m == "global_load_dword":
-                imm = int(t[4].split(":")[1]) if len(t) > 4 and isinstance(t[4], str) and t[4].startswith("offset:") else 0
-                arr, row = mem(s64(t[3]) + int(V[int(t[2][1:])]) + imm)
-                val = np.array([arr[row]]).view(u32)[0] if arr.dtype != np.float32 else bits(arr[row])
-                if t[1][0] == "a":
-                    A[int(t[1][1:])] = val
-                else:
-                    V[int(t[1][1:])] = val
-            elif m == "global_store_dword":
-                arr, row = mem(s64(t[3]) + int(V[int(t[1][1:])]))
-                raw = V[int(t[2][1:])]
-                arr[row] = asf(raw) if arr.dtype == np.float32 else np.array([raw], u32).view(np.int32)[0]
-            elif m in ("ds_write_b128", "ds_read_b128", "ds_write_b32", "ds_read_b32"):
-                w0 = t[3] // 1024 * 4 + (t[3] % 1024) // 4
-                if m == "ds_write_b128":
-                    lo = int(t[2][2:t[2].index(":")])
-                    lds[w0:w0 + 4] = V[lo:lo + 4]
-                elif m == "ds_read_b128":
-                    lo = int(t[1][2:t[1].index(":")])
-                    V[lo:lo + 4] = lds[w0:w0 + 4]
-                elif m == "ds_write_b32":
-                    lds[w0] = V[int(t[2][1:])]
-                else:
-                    V[int(t[1][1:])] = lds[w0]
-            elif m == "v_accvgpr_read_b32":
-                V[int(t[1][1:])] = A[int(t[2][1:])]
-            elif m == "v_accvgpr_write_b32":
-                A[int(t[1][1:])] = u32(src_bits(t[2]))
-            elif m == "v_mov_b32":
-                x = t[2]
-                if isinstance(x, str) and (x.startswith("-") or x.startswith("|")):
-                    setv(t[1], fsrc(x))
-                else:
-                    setvb(t[1], src_bits(x))
-            elif m == "v_pk_mov_b32":
-                d = t[-1]
-                lo = int(t[1][2:t[1].index(":")])
-                r0, r1 = half(t[2], d["op_sel"][0]), half(t[3], d["op_sel"][1])
-                V[lo], V[lo + 1] = bits(r0), bits(r1)
-            elif m == "v_add_u32":
-                setvb(t[1], (src_bits(t[2]) + src_bits(t[3])) & 0xFFFFFFFF)
-            elif m == "v_and_b32":
-                setvb(t[1], src_bits(t[2]) & src_bits(t[3]))
-            elif m == "v_fma_f32":
-                setv(t[1], f32(np.float64(fsrc(t[2])) * np.float64(fsrc(t[3])) + np.float64(fsrc(t[4]))))
-            elif m == "v_fmac_f32":
-                setv(t[1], f32(np.float64(fsrc(t[2])) * np.float64(fsrc(t[3])) + np.float64(fsrc(t[1]))))
-            elif m == "v_fmaak_f32":
-                setv(t[1], f32(np.float64(fsrc(t[2])) * np.float64(fsrc(t[3])) + np.float64(asf(u32(t[4])))))
-            elif m == "v_mul_f32":
-                setv(t[1], f32(fsrc(t[2]) * fsrc(t[3])))
-            elif m == "v_add_f32":
-                setv(t[1], f32(fsrc(t[2]) + fsrc(t[3])))
-            elif m == "v_sub_f32":
-                setv(t[1], f32(fsrc(t[2]) - fsrc(t[3])))
-            elif m == "v_subrev_f32":
-                setv(t[1], f32(fsrc(t[3]) - fsrc(t[2])))
-            elif m in ("v_max_f32", "v_min_f32"):
-                a, b = fsrc(t[2]), fsrc(t[3])
-                r = (a if b != b else b if a != a else (max(a, b) if m == "v_max_f32" else min(a, b)))
-                setv(t[1], r)
-            elif m == "v_max3_f32":
-                vals = [x for x in (fsrc(t[2]), fsrc(t[3]), fsrc(t[4])) if x == x]
-                setv(t[1], max(vals) if vals else f32(np.nan))
-            elif m == "v_min3_f32":
-                vals = [x for x in (fsrc(t[2]), fsrc(t[3]), fsrc(t[4])) if x == x]
-                setv(t[1], min(vals) if vals else f32(np.nan))
-            elif m == "v_med3_f32":
-                vals = sorted((fsrc(t[2]), fsrc(t[3]), fsrc(t[4])))
-                setv(t[1], vals[1])
-            elif m == "v_rcp_f32":
-                setv(t[1], f32(1.0) / fsrc(t[2]))
-            elif m == "v_rsq_f32":
-                setv(t[1], f32(1.0 / np.sqrt(np.float64(fsrc(t[2])))))
-            elif m == "v_sqrt_f32":
-                setv(t[1], f32(np.sqrt(np.float64(fsrc(t[2])))))
-            elif m.startswith("v_cmp_") and m.endswith("_f32") or m.startswith("v_cmp_") and m.endswith("_f32_e64"):
-                op = m[len("v_cmp_"):].split("_")[0]
-                setmask(t[1], cmpf[op](fsrc(t[2]), fsrc(t[3])))
-            elif m == "v_cmp_eq_i32_e64":
-                a, b = src_bits(t[2]), src_bits(t[3])
-                setmask(t[1], a == b)
-            elif m in ("v_cndmask_b32", "v_cndmask_b32_e64"):
-                sel = s64(t[4]) & 1
-                setvb(t[1], src_bits(t[3]) if sel else src_bits(t[2]))
-            elif m in ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32"):
-                d = t[-1]
-                srcs = t[2:-1]
-                dlo = int(t[1][2:t[1].index(":")])
-                res = []
-                for hi in (0, 1):
-                    sel = d["op_sel_hi"] if hi else d["op_sel"]
-                    ng = d["neg_hi"] if hi else d["neg_lo"]
-                    vals = [np.float64(half(x, sel[q])) * (-1 if ng[q] else 1) for q, x in enumerate(srcs)]
-                    if m == "v_pk_fma_f32":
-                        res.append(f32(vals[0] * vals[1] + vals[2]))
-                    elif m == "v_pk_mul_f32":
-                        res.append(f32(f32(vals[0]) * f32(vals[1])))
-                    else:
-                        res.append(f32(f32(vals[0]) + f32(vals[1])))
-                V[dlo], V[dlo + 1] = bits(res[0]), bits(res[1])
-            else:
-                raise ValueError("unknown instruction %r" % (t,))
-            pc += 1
-    simulate.last_quad_instructions = nquad[0]
-    return nexec
+    regions = [(PBASE, 4, np.frombuffer(bytes(blob), np.uint32))] + \
+        [(base_of[n], 4 if n in FLAT else STRIDE, arrays[n]) for n in PTRS if arrays.get(n) is not None]
+    m = isasim.Machine(ins, regions=regions, sgpr={S_PARAM: PBASE & 0xFFFFFFFF, S_PARAM + 1: PBASE >> 32}, vgpr={0: 0},
+                       lds=np.zeros((1, NLDS), np.uint32), max_exec=max_exec, quad=_quad())
+    isasim.run(m)
+    simulate.last_quad_sections = {("admm" if k is None else k): n for k, n in m.sections.items()}
+    simulate.last_quad_instructions = sum(m.sections.values())
+    return m.nexec
 
 
 if __name__ == "__main__":

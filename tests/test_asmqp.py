@@ -780,3 +780,38 @@ def test_no_memory_instruction_inside_the_iterations_of_the_cut_loop(prog):
             for body in fused:
                 lds = [t for t in body if t[0].startswith("ds_")]
                 assert len(lds) <= 4 and len(body) <= 380, (len(lds), len(body))
+
+
+def _run_on(adapter, ins):
+    """`ins` through the interpreter setup of one generator's simulate()"""
+    from robobee3d_amd import asmgen, asmgen64, asmqp, asmquad, asmquad64, asmstep
+    f32 = np.float32
+    z4 = lambda n: np.zeros((4, n), np.uint32)
+    if adapter == "asmgen":
+        asmgen.simulate(ins, np.zeros(asmgen.WS_ROWS, f32), np.zeros(127, f32), 1)
+    elif adapter == "asmgen64":
+        asmgen64.simulate(ins, np.zeros(asmgen.WS_ROWS), np.zeros(123), 1, np.zeros(320))
+    elif adapter == "asmstep":
+        asmstep.simulate(ins, {}, dict(K=1, maxIter=1, nsub=0, plant=1), asmstep.host_floats())
+    elif adapter == "asmquad":
+        asmquad.simulate([("quad_begin",)] + ins + [("quad_end",)], 0, z4(256), z4(256), z4(asmgen.NLDS), {})
+    elif adapter == "asmquad64":
+        asmquad64.simulate([("quad_begin",)] + ins + [("quad_end",)], 0, z4(256), z4(256), np.zeros((4, 320)), {}, None)
+    else:
+        asmqp.simulate(ins, np.zeros(1, np.float32), np.zeros(1, np.float32), 1, (1.6, 1e-6, 0.01))
+
+
+@pytest.mark.parametrize("adapter", ["asmgen", "asmgen64", "asmstep", "asmquad", "asmquad64", "asmqp"])
+def test_every_stream_gets_the_completion_address_and_kill_checks(adapter):
+    """one interpreter (isasim) behind every generator: a register read before the s_waitcnt that retires its load, a
+    global access outside the memory map and a read of a killed register raise whichever stream they appear in"""
+    unwaited = [("ds_read_b128", "v[8:11]", "v1", 0), ("v_add_f32", "v12", "v8", "v9")]
+    wild = [("s_mov_b32", "s20", 0x1234), ("s_mov_b32", "s21", 0), ("global_load_dword", "v8", "v0", "s[20:21]")]
+    killed = [("v_mov_b32", "v8", 1.0), ("kill", "v8"), ("v_add_f32", "v9", "v8", "v8")]
+    with pytest.raises(AssertionError, match="waited for"):
+        _run_on(adapter, unwaited)
+    from robobee3d_amd.isasim import AddressFault
+    with pytest.raises(AddressFault):
+        _run_on(adapter, wild)
+    with pytest.raises(AssertionError, match="after its kill"):
+        _run_on(adapter, killed)
