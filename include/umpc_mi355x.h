@@ -203,9 +203,36 @@ double umpcBatchTime(const umpc_batch_t *h);
  * copy), umpcBatchCreate checks the batch-constant ones. Returns 0, -1 (bad weights) or a hipError_t. */
 int umpcBatchSetWeights(umpc_batch_t *h, const void *weights);
 
+/* Reference trajectories: a different reference at every closed-loop step of ONE launch, per robot (waypoints, a
+ * recorded flight, a planner's output, a task / parameter sweep over the batch).
+ * tab: device [steps][9][B] in the handle's dtype -- slice k = the `ref` rows (pdes, dpdes, sdes) of step k, robot index
+ * fastest -- kept by pointer, not copied (like the weights table: it must stay allocated, and may be rewritten between
+ * launches, until it is replaced or the handle destroyed); NULL = off. While a table is set the `ref` argument of
+ * umpcBatchRollout / umpcBatchUpdate is not read (it may be NULL): step k of a rollout reads slice cursor + k. The cursor
+ * starts at `cursor0` and advances by K with every umpcBatchRollout whose nsub > 0 (like umpcBatchTime). A rollout that
+ * would read past `steps` is refused (-1, umpcLastError) BEFORE anything is launched. umpcBatchUpdate reads slice `cursor`
+ * and does not advance it.
+ * A table and a handle task != 0 exclude each other: whichever of umpcBatchSetRefTrajectory / umpcBatchSetTask comes
+ * second is refused (-1). umpcBatchReactive and umpcBatchTaskReference are refused (-1) while a table is set: they
+ * evaluate the reference per plant substep / at a free time, and a table has one slice per MPC step (substep-granular
+ * references are not built). The WL coupling, per-robot weights, Ib, gain, actualT0, both plant modes and
+ * umpcBatchSetStepKernel 0..3 all combine with a table. Memory: 9 x B x steps scalars (fp32, B = 65 536, 500 steps:
+ * 1.2 GB) -- long runs are chunked: fill the next table while one runs, then set it with cursor0 = 0. */
+int umpcBatchSetRefTrajectory(umpc_batch_t *h, const void *tab, long long steps, long long cursor0);
+long long umpcBatchRefCursor(const umpc_batch_t *h);
+/* Fills tab [steps][9][B] with the task generators evaluated PER ROBOT at the fire times t_k = t_ms + k * nsub * dtsim
+ * (the step kernel's own device function and time expression, in the handle's dtype: a table with batch-constant
+ * parameters holds what umpcBatchSetTask would generate). task: int32 [B] device array of UMPC_TASK_* ids, or NULL (= the
+ * handle's task); params: [4][B] in the handle's dtype, rows in the order listed at umpcBatchSetTask, or NULL (= the
+ * handle's); ref [9][B] as in umpcBatchRollout (rows 0..2 = initialPos for a task != 0; task 0 copies the column).
+ * Asynchronous on `stream`. Does not set the table: pass it to umpcBatchSetRefTrajectory. */
+int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
+                       const void *ref, void *tab, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
- * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (no task
- * generator, batch-constant weights, no WL coupling, maxIter >= 1), else the C++ kernel with the assembly ADMM loop.
+ * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
+ * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are
+ * options of that stream), else the C++ kernel with the assembly ADMM loop.
  * fp64: the C++ kernel with L and 1/D in LDS and the Ruiz passes and the ADMM phase as generated fp64 assembly
  * (robobee3d_amd/asmgen64.py; one workgroup per CU at a time, maxIter >= 1, batches up to ~4.8e5 robots), else the all-C++
  * kernel.

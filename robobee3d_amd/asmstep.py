@@ -47,6 +47,9 @@ PTRS = ["state", "ctrl", "ref", "ws", "out", "stats", "status", "info", "Ib", "g
         "done"]
 NPTR_RES = 11             # the first 11 pointers live in s40..s61 for the whole kernel
 INTS = ["stride", "K", "maxIter", "nsub", "plant", "seq"]
+# Appended BEHIND the floats (every older byte offset stays): `refstep` = bytes the `ref` pointer advances per closed-loop
+# step (a reference trajectory [steps][9][B]: 9 * B * 4; 0 = one frozen reference per launch)
+TAIL_INTS = ["refstep"]
 FLOATS = ["dt", "dtg", "Tmax", "wpr", "wpf", "ws_", "wvr", "wvf", "wds", "wthrust", "wmom",
           "iwpr", "iwpf", "iws", "iwvr", "iwvf", "iwds", "iwthrust", "iwmom",
           "Ib0", "Ib1", "Ib2", "Ibi0", "Ibi1", "Ibi2", "h", "hh", "h6", "taulim", "gpl", "idt", "mbg"]
@@ -74,7 +77,7 @@ _o = 0
 for _n in PTRS:
     OFF[_n] = _o
     _o += 8
-for _n in INTS + FLOATS:
+for _n in INTS + FLOATS + TAIL_INTS:
     OFF[_n] = _o
     _o += 4
 PARAM_BYTES = _o
@@ -2136,6 +2139,13 @@ class StepGen:
             asmgen.XV_COUNT = 0  # ... for this stream only: asmgen.program() of the C++ kernel must not see them
             asmgen.NRING = 4
         self.phase_c()
+        # reference trajectory: `ref` moves on by `refstep` bytes for the next step (both ref loads of this step, phase A
+        # and phase C, are behind us). No SGPR is free for the whole kernel in the quad form, so the word is read from the
+        # parameter block here, once per step; the 64-bit add carries (the offset passes 4 GB in a long launch).
+        e("s_load_dword", sg(S_TMP), sp(S_PBLK), OFF["refstep"])
+        e("s_waitcnt", "lgkmcnt(0)")
+        e("s_add_u32", sg(S_PTR["ref"]), sg(S_PTR["ref"]), sg(S_TMP))
+        e("s_addc_u32", sg(S_PTR["ref"] + 1), sg(S_PTR["ref"] + 1), 0)
         e("s_add_i32", sg(S_STEP), sg(S_STEP), 1)
         e("s_cmp_lt_i32", sg(S_STEP), sg(S_INT["K"]))
         e("s_cbranch_scc1", top + "b")
@@ -2228,6 +2238,8 @@ def write(path=None, N=3, perm=None, quad=False):
             out.append("  int32_t %s;" % n)
         for n in FLOATS:
             out.append("  float %s;" % n)
+        for n in TAIL_INTS:
+            out.append("  int32_t %s;" % n)
         out += ["};", "static_assert(sizeof(StepParams) == %d, \"StepParams layout\");" % ((PARAM_BYTES + 7) // 8 * 8),
                 "constexpr int STEP_LDS_BYTES_PER_LANE = %d;" % (NLDS * 4), "}  // namespace umpcasm",
                 "// inputs: v0 = 4 * robot, v1 = lane LDS address, s[4:5] = &StepParams (kernarg)",
@@ -2283,7 +2295,8 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
         struct.pack_into("<Q", blob, OFF[n], ptr_xform(base_of[n]) if arrays.get(n) is not None else 0)
     allints = dict(ints, stride=STRIDE)
     allints.setdefault("seq", 0)
-    for n in INTS:
+    allints.setdefault("refstep", 0)      # bytes; a table of slices [9] per step in arrays["ref"] takes 9 * STRIDE
+    for n in INTS + TAIL_INTS:
         struct.pack_into("<i", blob, OFF[n], int(allints[n]))
     for n in FLOATS:
         struct.pack_into("<f", blob, OFF[n], float(floats[n]))

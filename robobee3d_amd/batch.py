@@ -199,6 +199,64 @@ class BatchUprightMPC:
         self._task = (tid, arr)
         self._check(self.L.umpcBatchSetTask(self.h, tid, arr, float(t_ms)))
 
+    def set_reference_trajectory(self, tab, cursor=0):
+        """A reference per closed-loop step and per robot (umpcBatchSetRefTrajectory): tab [steps, 9, B] holds the rows
+        (pdes, dpdes, sdes) of every step; step k of a rollout reads slice ref_cursor + k and `self.ref` is not read. The
+        cursor starts at `cursor` and advances with every rollout(); a rollout that would run past the table raises before
+        anything is launched. None switches back to `self.ref`. Excludes set_task (either call raises after the other) and
+        reactive_rollout / task_reference; combines with everything else. Memory: 36 B x B x steps in fp32 -- chunk long runs."""
+        if tab is None:
+            self._check(self.L.umpcBatchSetRefTrajectory(self.h, None, 0, 0))
+            self._reftab = None
+            return
+        t = torch.as_tensor(tab, dtype=self.dtype).to(self.device).contiguous()
+        if t.dim() != 3 or tuple(t.shape[1:]) != (_lib.REF_ROWS, self.B):
+            raise ValueError("reference trajectory must be [steps, 9, %d], got %r" % (self.B, tuple(t.shape)))
+        self._check(self.L.umpcBatchSetRefTrajectory(self.h, _ptr(t), int(t.shape[0]), int(cursor)))
+        self._reftab = t  # keep alive: the library stores the pointer
+
+    @property
+    def ref_cursor(self):
+        """The slice of the reference trajectory the next closed-loop step reads (umpcBatchRefCursor)."""
+        return int(self.L.umpcBatchRefCursor(self.h))
+
+    def task_table(self, steps, tasks=None, t_ms=None, **params):
+        """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
+        at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of
+        TASKS, a length-B sequence of names, or None (= the handle's task); every keyword of TASKS (trajAmp, trajFreq, dz,
+        useY, tduration, vdes, tstart, tend, trotstart, trotend) a scalar or a [B] array, defaults as set_task for the
+        robot's task. Rows 0..2 of `self.ref` are the robots' initialPos ("ref" robots copy their whole column)."""
+        steps = int(steps)
+        bad = sorted(set(params) - set(self.TASK_DEFAULTS))
+        if bad:
+            raise TypeError("unknown task parameter(s) %r" % bad)
+        tab = torch.empty((steps, _lib.REF_ROWS, self.B), dtype=self.dtype, device=self.device)
+        tid = prm = None
+        if tasks is not None or params:
+            by_id = {v[0]: k for k, v in self.TASKS.items()}
+            names = [by_id[self._task_id()]] * self.B if tasks is None else [tasks] * self.B if isinstance(tasks, str) else list(tasks)
+            if len(names) != self.B:
+                raise ValueError("tasks must be one name or %d names" % self.B)
+            names = np.asarray(names)
+            ids = np.zeros(self.B, np.int32)
+            P = np.zeros((4, self.B), np.float64)
+            for name in sorted(set(names.tolist())):
+                t_id, slots = self.TASKS[name]
+                sel = names == name
+                ids[sel] = t_id
+                dflt = dict(self.TASK_DEFAULTS)
+                dflt["vdes"] = {"straightAcc": 2, "perch": 0.2}.get(name, 0)
+                dflt["tend"] = {"flip": 200, "perch": 500}.get(name, 0)
+                for i, n in enumerate(slots):
+                    val = np.broadcast_to(np.asarray(params.get(n, dflt[n]), np.float64), (self.B,))
+                    P[i, sel] = val[sel]
+            tid = torch.as_tensor(ids).to(self.device)
+            prm = torch.as_tensor(P).to(self.dtype).to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchTaskTable(self.h, steps, self.time_ms if t_ms is None else float(t_ms), _ptr(tid),
+                                                  _ptr(prm), _ptr(self.ref), _ptr(tab), self._stream()))
+        return tab
+
     def set_weights(self, weights):
         """Per-robot objective weights [8, B] = (ws, wds, wpr, wpf, wvr, wvf, wthrust, wmom), or None."""
         if weights is None:

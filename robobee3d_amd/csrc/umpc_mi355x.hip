@@ -347,6 +347,36 @@ __global__ void umpc_taskf_kernel(DevParams<float> prm, int K, float t0, float *
   o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = r[5]; o[6] = r[6]; o[7] = r[8];
 }
 
+// Per-robot task tables (umpcBatchTaskTable): slice k of tab [steps][9][B] = task_reference(task[b], params[.][b], t_k, ref
+// column b) at the fire time t_k of closed-loop step k -- the SAME device function and the SAME expression for t_k, in the
+// same scalar type, as closed_loop_step (umpc_step.h) and umpc_taskf_kernel, so a table with batch-constant parameters holds
+// exactly what the step kernel would generate. 2-D grid: x = robots (robot index fastest: every store of a warp is one
+// coalesced row segment), y = a grid stride over the steps; a thread loads its robot's task, parameters and ref column once
+// and reuses them for all its steps. task 0 copies the ref column.
+template <typename T>
+__global__ void umpc_task_table_kernel(DevParams<T> prm, int B_, long long steps, T t0, const int32_t *task, const T *params,
+                                       const T *ref, T *tab) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B_) return;
+  const size_t B = (size_t)B_;
+  const int tk = task ? task[b] : prm.task;
+  T tp[4], r0[9];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tp[i] = params ? params[(size_t)i * B + b] : prm.task_p[i];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r0[i] = ref[(size_t)i * B + b];
+  for (long long k = blockIdx.y; k < steps; k += gridDim.y) {
+    T r[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r[i] = r0[i];
+    const T tnow = t0 + T(k) * (T(prm.nsub) * prm.dtsim);
+    umpc::task_reference(tk, tp, tnow, r);
+    T *o = tab + (size_t)k * 9 * B;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o[(size_t)i * B + b] = r[i];
+  }
+}
+
 template <typename T>
 __global__ void umpc_init_ctrl_kernel(int B_, T *ctrl) {
   const size_t B = (size_t)B_;
@@ -388,6 +418,9 @@ struct umpc_batch {
   const char *last_kernel = "";   // the kernel the last umpcBatchRollout / umpcBatchUpdate dispatched (umpcBatchKernelName)
   float *taskf = nullptr;         // task table of the all-assembly kernel: 8 floats per step of a launch
   int taskf_cap = 0;              // ... steps it holds
+  const void *reftab = nullptr;   // reference trajectory [steps][9][B] (umpcBatchSetRefTrajectory), kept by pointer; null = off
+  long long reftab_steps = 0;     // ... slices it holds
+  long long ref_cursor = 0;       // ... slice the next closed-loop step reads (advanced by every rollout with nsub > 0)
 };
 
 // Parameter block of the all-assembly step kernel (umpcasm::StepParams, read by the stream with scalar loads)
@@ -400,7 +433,7 @@ static umpcasm::StepParams make_step_params(umpc_batch_t *h, int K, int nsub, vo
   p.ws = (char *)h->ws + (size_t)umpcasm::WS_DS * (size_t)h->B * 4;
   p.info = info; p.Ib = Ib; p.gain = gain; p.aT0 = actualT0;
   p.taskf = nullptr; p.weights = h->weights; p.wl = h->wl; p.wlu = h->wlu; p.wlw = h->wlw;
-  p.done = nullptr; p.seq = 0;
+  p.done = nullptr; p.seq = 0; p.refstep = 0;
   p.stride = h->B * 4; p.K = K; p.maxIter = h->prm.maxIter; p.nsub = nsub; p.plant = h->prm.plant_mode;
   const umpc_batch_params_t &q = h->prm;
   const float one = 1.0f;
@@ -422,12 +455,25 @@ template <typename T>
 static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
                           const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
                           int32_t *status, void *info, void *stream) {
+  // reference trajectory: step k of this launch reads slice cursor + k of the table (`ref` is not read); refused BEFORE
+  // anything is launched when the launch would read past the table's end
+  size_t ref_step = 0;
+  if (h->reftab) {
+    if (h->ref_cursor + (long long)K > h->reftab_steps) {
+      g_err = "umpcBatchRollout: the reference trajectory ends before the launch does (cursor " + std::to_string(h->ref_cursor) +
+              " + K " + std::to_string(K) + " > steps " + std::to_string(h->reftab_steps) + ")";
+      return -1;
+    }
+    ref_step = (size_t)9 * (size_t)h->B;
+    ref = (const T *)h->reftab + (size_t)h->ref_cursor * ref_step;
+  }
   if (!state || !ctrl || !ref || !out) { g_err = "umpcBatchRollout: null array"; return -1; }
+  if (h->reftab && nsub > 0) h->ref_cursor += K;
   umpc::StepIO<T> a;
   a.prm = make_dev<T>(h->prm);
   a.prm.nsub = nsub;
   a.B = h->B;
-  a.state = (T *)state; a.ctrl = (T *)ctrl; a.ref = (const T *)ref;
+  a.state = (T *)state; a.ctrl = (T *)ctrl; a.ref = (const T *)ref; a.ref_step = (unsigned)ref_step;
   a.prm.task = h->task;
   for (int i = 0; i < 4; ++i) a.prm.task_p[i] = (T)h->task_p[i];
   a.weights = (const T *)h->weights; a.t0 = (T)h->t_ms;
@@ -445,6 +491,7 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
     const bool fits = (size_t)UMPC_CTRL_ROWS * (size_t)h->B * 4 < ((size_t)1 << 31);
     if (!no_asm && h->step_kernel != 1 && fits && K >= 1 && h->prm.maxIter >= 1) {
       umpcasm::StepParams p = make_step_params(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info);
+      p.refstep = (int32_t)(ref_step * 4);        // bytes per step (9 rows x B x 4 < 2^31: `fits` bounds 127 rows)
       // SURVEY 8(f) options of the same stream: task generator (a table of K entries written by a K-thread kernel ahead
       // of the launch, same stream), per-robot weights, the fused WL step
       if (h->task != 0) {
@@ -538,6 +585,23 @@ static int launch_reactive(umpc_batch_t *h, int nsteps, int every, void *state, 
   return e == hipSuccess ? 0 : fail(e, "umpcBatchReactive");
 }
 
+template <typename T>
+static int launch_task_table(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
+                             const void *ref, void *tab, void *stream) {
+  DevParams<T> prm = make_dev<T>(h->prm);
+  prm.task = h->task;
+  for (int i = 0; i < 4; ++i) prm.task_p[i] = (T)h->task_p[i];
+  // enough blocks in y to fill the device when B is small, never more than the steps there are (or the grid limit)
+  const unsigned gx = (unsigned)((h->B + 255) / 256);
+  long long gy = (2048 + gx - 1) / gx;
+  if (gy > steps) gy = steps;
+  if (gy > 65535) gy = 65535;
+  hipLaunchKernelGGL(umpc_task_table_kernel<T>, dim3(gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, prm, h->B, steps,
+                     (T)t_ms, task, (const T *)params, (const T *)ref, (T *)tab);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, "umpcBatchTaskTable");
+}
+
 extern "C" {
 
 const char *umpcLastError(void) { return g_err.c_str(); }
@@ -600,10 +664,36 @@ void umpcBatchDestroy(umpc_batch_t *h) {
 }
 int umpcBatchSetTask(umpc_batch_t *h, int task, const double params[4], double t_ms) {
   if (!h || task < 0 || task > 4) { g_err = "umpcBatchSetTask: bad argument"; return -1; }
+  if (task != 0 && h->reftab) {
+    g_err = "umpcBatchSetTask: a reference trajectory is set (umpcBatchSetRefTrajectory); a handle follows one or the other";
+    return -1;
+  }
   h->task = task;
   for (int i = 0; i < 4; ++i) h->task_p[i] = params ? params[i] : 0.0;
   h->t_ms = t_ms;
   return 0;
+}
+int umpcBatchSetRefTrajectory(umpc_batch_t *h, const void *tab, long long steps, long long cursor0) {
+  if (!h) { g_err = "umpcBatchSetRefTrajectory: bad argument"; return -1; }
+  if (!tab) {
+    h->reftab = nullptr; h->reftab_steps = 0; h->ref_cursor = 0;
+    return 0;
+  }
+  if (steps < 1 || cursor0 < 0 || cursor0 > steps) { g_err = "umpcBatchSetRefTrajectory: bad argument (steps >= 1, 0 <= cursor0 <= steps)"; return -1; }
+  if (h->task != 0) {
+    g_err = "umpcBatchSetRefTrajectory: a task generator is set (umpcBatchSetTask); a handle follows one or the other";
+    return -1;
+  }
+  h->reftab = tab; h->reftab_steps = steps; h->ref_cursor = cursor0;
+  return 0;
+}
+long long umpcBatchRefCursor(const umpc_batch_t *h) { return h ? h->ref_cursor : 0; }
+
+int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
+                       const void *ref, void *tab, void *stream) {
+  if (!h || steps < 1 || !ref || !tab) { g_err = "umpcBatchTaskTable: bad argument"; return -1; }
+  return h->dtype == UMPC_F32 ? launch_task_table<float>(h, steps, t_ms, task, params, ref, tab, stream)
+                              : launch_task_table<double>(h, steps, t_ms, task, params, ref, tab, stream);
 }
 int umpcBatchSetWeights(umpc_batch_t *h, const void *weights) {
   if (!h) return -1;
@@ -656,6 +746,7 @@ int umpcBatchRollout(umpc_batch_t *h, int K, void *state, void *ctrl, const void
 
 int umpcBatchTaskReference(umpc_batch_t *h, double t_ms, const void *ref, void *out, void *stream) {
   if (!h || !ref || !out) { g_err = "umpcBatchTaskReference: bad argument"; return -1; }
+  if (h->reftab) { g_err = "umpcBatchTaskReference: a reference trajectory is set (its slices ARE the reference)"; return -1; }
   const int grid = (h->B + 255) / 256;
   if (h->dtype == UMPC_F32) {
     DevParams<float> prm = make_dev<float>(h->prm);
@@ -677,6 +768,7 @@ int umpcBatchTaskReference(umpc_batch_t *h, double t_ms, const void *ref, void *
 int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const void *ref, const void *gains,
                       const void *Ib, const void *gain, void *out, void *stats, void *stream) {
   if (!h || nsteps < 0 || every < 1 || !state || !ref) { g_err = "umpcBatchReactive: bad argument"; return -1; }
+  if (h->reftab) { g_err = "umpcBatchReactive: a reference trajectory is set (it has one slice per MPC step, not per substep)"; return -1; }
   return h->dtype == UMPC_F32 ? launch_reactive<float>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream)
                               : launch_reactive<double>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream);
 }

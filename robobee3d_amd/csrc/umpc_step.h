@@ -460,6 +460,10 @@ struct StepIO {
   const WLDev *wl; // device copy of the WL parameters
   T *wlu;          // [4][B] WL input state u4, in/out
   T *wlw;          // [6][B] w0 of the last step, or null
+  // Reference trajectory [steps][9][B] (umpcBatchSetRefTrajectory): `ref` is slice `cursor`, and step k of the launch reads
+  // ref + k * ref_step (elements: 9 * B; 0 = one frozen reference). 32 bits and LAST in the struct: the fp64 step kernels
+  // keep their measured scratch frames with it here (csrc/resource_limits.json), a 64-bit member next to `ref` grew one.
+  unsigned ref_step;
 };
 
 // One closed-loop step of robot b: controller step (= umpcUpdate) + nsub plant substeps.
@@ -555,7 +559,7 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
 #pragma unroll
     for (int i = 0; i < 6; ++i) dq0[i] = GLD(a.state, 12 + i);
 #pragma unroll
-    for (int i = 0; i < 9; ++i) ref[i] = GLD(a.ref, i);
+    for (int i = 0; i < 9; ++i) ref[i] = GLD(a.ref + (size_t)step * a.ref_step, i);
     task_reference(prm.task, prm.task_p, tnow, ref);
 #pragma unroll
     for (int k = 0; k < N; ++k) Eprev3[k] = GLD(a.ctrl, NX + 2 * NC + 1 + k);

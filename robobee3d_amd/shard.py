@@ -64,6 +64,14 @@ def split_range(total, rank, ws):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def table_block(tab, lo, hi):
+    """The block [lo, hi) of the robots of a per-robot table whose LAST axis is the robot index -- a reference trajectory
+    [steps, 9, B] (BatchUprightMPC.set_reference_trajectory), a weights table [8, B], a state [18, B] -- as the contiguous
+    tensor a block's handle takes. Robots are independent, so a block of a job (global_batch = the job's size) run on its
+    column slice equals the undivided run bit for bit."""
+    return tab[..., lo:hi].contiguous()
+
+
 def max_over_ranks(value, device="cpu"):
     t = torch.tensor([float(value)], dtype=torch.float64, device=device)
     if dist.is_initialized():
