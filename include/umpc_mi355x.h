@@ -229,6 +229,37 @@ long long umpcBatchRefCursor(const umpc_batch_t *h);
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
                        const void *ref, void *tab, void *stream);
 
+/* Step history: what EVERY closed-loop step of a rollout launch read and produced, for the whole batch (the output side of
+ * a reference trajectory: which robots left the path, when, with what command).
+ * Device tables in the handle's dtype, robot index fastest, kept by pointer, not copied (they must stay allocated until
+ * replaced or the handle destroyed); any one may be NULL = that record is off, all NULL = history off:
+ *   state_hist  [steps+1][18][B]   slice c = the state BEFORE step c, slice c + 1 = the state after it
+ *   out_hist    [steps][9][B]      (T0 + u0, u1, u2, accdes[6]) of step c
+ *   status_hist [steps][B] int32   OSQP status of step c
+ *   info_hist   [steps][2][B]      (pri_res, dua_res) of step c
+ * While a history is set, a umpcBatchRollout of K steps at cursor c leaves state slice c = its `state` argument as passed,
+ * slices c + 1 .. c + K and slices c .. c + K - 1 of the other tables as above, and its `state`, `out`, `status`, `info`
+ * arguments exactly what they are without a history. The kernels' own per-step stores go to the tables (the destination
+ * moves on one slice per step: the step kernel issues no store more than without a history); stream-ordered device copies
+ * around the launch serve the arguments -- five per launch at the most.
+ * One form is an exception: the fp64 kernel with one robot per lane quad (the automatic choice for fp64 at B <= 4 096, or
+ * umpcBatchSetStepKernel 3) cannot move its pointers inside its register / scratch budget, so with a history set the
+ * library issues its K steps as K single-step launches on moved pointers, each preceded by a device copy of state slice
+ * k into slice k + 1 (18 x B scalars per step more, K launches instead of one; the results are the same). Every other
+ * form -- fp32 lane / quad / C++, fp64 lane / C++ -- stays one launch with no copy per step.
+ * A HIP error in the middle of a rollout with a history leaves both cursors and umpcBatchTime where they were. The cursor starts at `cursor0` and
+ * advances by K per rollout, so consecutive rollouts continue one table; a rollout that would pass `steps` is refused
+ * (-1, umpcLastError) BEFORE anything is launched or copied. Refused (-1): a handle with nsub = 0 (its rollouts never
+ * write the state), steps < 1, cursor0 outside [0, steps]. umpcBatchUpdate, umpcBatchPlant, umpcBatchReactive and the
+ * B = 1 drop-in neither record nor move the cursor.
+ * Combines with a reference trajectory, the tasks, per-robot weights, Ib, gain, actualT0, the WL coupling, both plant
+ * modes, both dtypes and umpcBatchSetStepKernel 0..3. Memory: (18 (steps + 1) + 9 steps + steps + 2 steps) x B scalars
+ * when all four are on -- fp32, B = 65 536, 500 steps: state 2.4 GB, out 1.2 GB -- long runs are chunked: read a full table
+ * out, then set it again with cursor0 = 0. */
+int umpcBatchSetHistory(umpc_batch_t *h, void *state_hist, void *out_hist, int32_t *status_hist, void *info_hist,
+                        long long steps, long long cursor0);
+long long umpcBatchHistoryCursor(const umpc_batch_t *h);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

@@ -25,7 +25,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchRollout", "umpcBatchUpdate", "umpcBatchPlant", "umpcBatchAssemble",
            "umpcBatchSize", "umpcBatchDtype", "umpcAxIdx", "umpcKKTPerm", "umpcNnzL",
            "umpcBatchSetTask", "umpcBatchTime", "umpcBatchSetWeights", "umpcBatchSetStepKernel", "umpcBatchSetGlobalBatch", "umpcBatchGlobalBatch", "umpcBatchReactive", "umpcBatchTaskReference",
-           "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable",
+           "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable", "umpcBatchSetHistory", "umpcBatchHistoryCursor",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -262,6 +262,9 @@ def lib():
         L.umpcBatchSetRefTrajectory.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong]
         L.umpcBatchRefCursor.argtypes = [C.c_void_p]
         L.umpcBatchRefCursor.restype = C.c_longlong
+        L.umpcBatchSetHistory.argtypes = [C.c_void_p] * 5 + [C.c_longlong, C.c_longlong]
+        L.umpcBatchHistoryCursor.argtypes = [C.c_void_p]
+        L.umpcBatchHistoryCursor.restype = C.c_longlong
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

@@ -81,6 +81,17 @@ for _n in INTS + FLOATS + TAIL_INTS:
     OFF[_n] = _o
     _o += 4
 PARAM_BYTES = _o
+# A SECOND block, struct umpcasm::StepHist, follows StepParams in the kernarg segment (struct umpcasm::StepArgs) at the padded
+# size of the first: the per-step byte strides of the step HISTORY (umpcBatchSetHistory). Step k reads slice k of a state table
+# [steps+1][18][B] and writes slice k + 1; out [steps][9][B], status [steps][B] and info [steps][2][B] take slice k. All 0 = every
+# step overwrites the same arrays. PARAM_BYTES and every offset above stay as they are; the stream reads these words through
+# S_PBLK like the late words of the first block.
+HIST_INTS = ["statestep", "outstep", "statusstep", "infostep"]
+HIST_OFF = (PARAM_BYTES + 7) // 8 * 8
+for _k, _n in enumerate(HIST_INTS):
+    OFF[_n] = HIST_OFF + 4 * _k
+HIST_BYTES = 4 * len(HIST_INTS)
+S_HIST = 32               # s[32:35]: the block's words at the end of a step (the lane masks s30..s37 are dead between steps)
 
 VFIRST, VEND = 2, 256
 XV_N, XV_B = 10, 246      # L entries kept in VGPRs beyond the loop's fixed layout (asmgen.XV_COUNT / XV_BASE)
@@ -365,6 +376,16 @@ class StepGen:
 
     def adv(self, voff):
         self.e("v_add_u32", v(voff), sg(S_INT["stride"]), v(voff))
+
+    def advance_ptr(self, ptr, sstep):
+        """the 64-bit base pointer of `ptr` += s<sstep> (bytes, unsigned 32 bits), carry included: the low word wraps exactly
+        when the sum is below the addend. Built without s_add_u32 / s_addc_u32, which stay the mark of the `ref` advance
+        (tests/test_ref_trajectory.py extracts that pair by mnemonic). SALU only; s<sstep> ends holding the carry."""
+        e, lo = self.e, S_PTR[ptr]
+        e("s_add_i32", sg(lo), sg(lo), sg(sstep))
+        e("s_cmp_lt_u32", sg(lo), sg(sstep))
+        e("s_cselect_b32", sg(sstep), 1, 0)
+        e("s_add_i32", sg(lo + 1), sg(lo + 1), sg(sstep))
 
     def load_rows(self, ptr, first_row, regs, voff=None):
         own = voff is None
@@ -2011,6 +2032,12 @@ class StepGen:
         e("s_cmp_gt_i32", sg(S_SUB), 0)
         e("s_cbranch_scc1", top + "b")
         e("label", lab_done)
+        # step history: both state loads of this step (phase A, phase C) are behind us and its only state store follows, so
+        # the base moves on by `statestep` bytes HERE -- the store fills slice k + 1, which the next step's loads read. The
+        # word is read from the second parameter block once per step (no SGPR is free for the whole kernel in the quad form).
+        e("s_load_dword", sg(S_TMP), sp(S_PBLK), OFF["statestep"])
+        e("s_waitcnt", "lgkmcnt(0)")
+        self.advance_ptr("state", S_TMP)
         self.store_rows("state", 0, [Y0 + i for i in range(18)], voff)
         e("s_cmp_eq_u64", sp(S_PTR["stats"]), 0)
         e("s_cbranch_scc1", lab_s2 + "f")
@@ -2142,10 +2169,16 @@ class StepGen:
         # reference trajectory: `ref` moves on by `refstep` bytes for the next step (both ref loads of this step, phase A
         # and phase C, are behind us). No SGPR is free for the whole kernel in the quad form, so the word is read from the
         # parameter block here, once per step; the 64-bit add carries (the offset passes 4 GB in a long launch).
+        # Step history: `out`, `status` and `info` move on by their strides of the second block in the same place (all their
+        # stores of this step are issued; an address is read when its store issues). One x4 load takes the block into
+        # s[32:35], lane masks that are dead between steps.
         e("s_load_dword", sg(S_TMP), sp(S_PBLK), OFF["refstep"])
+        e("s_load_dwordx4", "s[%d:%d]" % (S_HIST, S_HIST + 3), sp(S_PBLK), HIST_OFF)
         e("s_waitcnt", "lgkmcnt(0)")
         e("s_add_u32", sg(S_PTR["ref"]), sg(S_PTR["ref"]), sg(S_TMP))
         e("s_addc_u32", sg(S_PTR["ref"] + 1), sg(S_PTR["ref"] + 1), 0)
+        for n in ("out", "status", "info"):
+            self.advance_ptr(n, S_HIST + HIST_INTS.index(n + "step"))
         e("s_add_i32", sg(S_STEP), sg(S_STEP), 1)
         e("s_cmp_lt_i32", sg(S_STEP), sg(S_INT["K"]))
         e("s_cbranch_scc1", top + "b")
@@ -2229,7 +2262,7 @@ def write(path=None, N=3, perm=None, quad=False):
     else:
         out = ["// GENERATED by robobee3d_amd/asmstep.py -- do not edit.", asmgen.switch_banner(),
                "// The all-assembly fp32 step kernel body: %d instructions (K closed-loop steps of one wavefront)." % len(ins),
-               "#pragma once", "#include <stdint.h>", "namespace umpcasm {",
+               "#pragma once", "#include <stddef.h>", "#include <stdint.h>", "namespace umpcasm {",
                "// parameter block read by the kernel with s_load (byte offsets are part of the generated code)",
                "struct StepParams {"]
         for n in PTRS:
@@ -2241,6 +2274,11 @@ def write(path=None, N=3, perm=None, quad=False):
         for n in TAIL_INTS:
             out.append("  int32_t %s;" % n)
         out += ["};", "static_assert(sizeof(StepParams) == %d, \"StepParams layout\");" % ((PARAM_BYTES + 7) // 8 * 8),
+                "// step history (umpcBatchSetHistory): bytes the state / out / status / info pointers advance per closed-loop step,",
+                "// read by the stream at byte %d of the kernarg segment: the kernels take ONE StepArgs as their first argument" % HIST_OFF,
+                "struct StepHist {"] + ["  int32_t %s;" % n for n in HIST_INTS] + ["};",
+                "struct StepArgs {", "  StepParams p;", "  StepHist h;", "};",
+                "static_assert(offsetof(StepArgs, h) == %d && sizeof(StepHist) == %d, \"StepHist layout\");" % (HIST_OFF, HIST_BYTES),
                 "constexpr int STEP_LDS_BYTES_PER_LANE = %d;" % (NLDS * 4), "}  // namespace umpcasm",
                 "// inputs: v0 = 4 * robot, v1 = lane LDS address, s[4:5] = &StepParams (kernarg)",
                 "#define UMPC_STEP_ASM(voff, ldsaddr, params) asm volatile( \\"]
@@ -2290,13 +2328,15 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
     from . import isasim
     base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(PTRS)}
     ptr_xform = ptr_xform or (lambda a: a)
-    blob = bytearray((PARAM_BYTES + 3) // 4 * 4)
+    blob = bytearray(HIST_OFF + HIST_BYTES)
     for n in PTRS:
         struct.pack_into("<Q", blob, OFF[n], ptr_xform(base_of[n]) if arrays.get(n) is not None else 0)
     allints = dict(ints, stride=STRIDE)
     allints.setdefault("seq", 0)
     allints.setdefault("refstep", 0)      # bytes; a table of slices [9] per step in arrays["ref"] takes 9 * STRIDE
-    for n in INTS + TAIL_INTS:
+    for n in HIST_INTS:                   # bytes per step: 18 / 9 / 1 / 2 rows of STRIDE for tables of slices in the arrays
+        allints.setdefault(n, 0)
+    for n in INTS + TAIL_INTS + HIST_INTS:
         struct.pack_into("<i", blob, OFF[n], int(allints[n]))
     for n in FLOATS:
         struct.pack_into("<f", blob, OFF[n], float(floats[n]))

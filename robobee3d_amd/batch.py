@@ -220,6 +220,97 @@ class BatchUprightMPC:
         """The slice of the reference trajectory the next closed-loop step reads (umpcBatchRefCursor)."""
         return int(self.L.umpcBatchRefCursor(self.h))
 
+    def record_history(self, steps, state=True, out=True, status=False, info=False):
+        """Record every closed-loop step of the following rollout() calls for the whole batch (umpcBatchSetHistory):
+        allocates the chosen tables for `steps` steps -- state [steps + 1, 18, B] (slice k = the state before step k, slice
+        k + 1 after it), out [steps, 9, B], status [steps, B] int32, info [steps, 2, B] -- and sets them with the cursor at 0.
+        The kernels' own per-step stores go to the tables, so a K-step launch stays one launch with no store more (the fp64
+        quad form alone -- fp64 at B <= 4 096, or set_step_kernel("quad") -- runs K single-step launches with a state copy each);
+        self.state / out / status / info end every rollout holding what they hold without a history. Consecutive rollouts
+        continue the tables; one that would pass `steps` raises before anything is launched. update(), plant() and
+        reactive_rollout() record nothing. record_history(None) switches history off. Memory: 72 B x B x steps for the
+        state and 36 B x B x steps for out in fp32 -- chunk long runs with rewind_history()."""
+        if steps is None:
+            self._check(self.L.umpcBatchSetHistory(self.h, None, None, None, None, 0, 0))
+            self._hist = None
+            return
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        if int(self.prm.nsub) == 0:
+            raise RuntimeError("record_history: the handle has no plant (nsub = 0), there is no trajectory to record")
+        e = lambda shape, dt=self.dtype: torch.empty(shape, dtype=dt, device=self.device)
+        hist = {"state": e((steps + 1, _lib.STATE_ROWS, self.B)) if state else None,
+                "out": e((steps, _lib.OUT_ROWS, self.B)) if out else None,
+                "status": e((steps, self.B), torch.int32) if status else None,
+                "info": e((steps, 2, self.B)) if info else None}
+        if all(v is None for v in hist.values()):
+            raise ValueError("record_history: every record is off (record_history(None) switches history off)")
+        self._check(self.L.umpcBatchSetHistory(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
+                                               _ptr(hist["info"]), steps, 0))
+        self._hist = hist  # keep alive: the library stores the pointers
+        # where the record starts: the clock, the slice of a reference trajectory, the statistics accumulated before it
+        self._hist_t0, self._hist_ref0, self._hist_stats0 = self.time_ms, self.ref_cursor, self.stats.clone()
+
+    def rewind_history(self, cursor=0):
+        """Reuse the tables of record_history from step `cursor` on (a chunked long run: read the full tables out, rewind,
+        roll on): no allocation, the records that are on stay on; what lies behind `cursor` is overwritten as the run goes."""
+        hist = getattr(self, "_hist", None)
+        if hist is None:
+            raise RuntimeError("no history is set (record_history)")
+        steps = next(int(v.shape[0]) - (k == "state") for k, v in hist.items() if v is not None)
+        self._check(self.L.umpcBatchSetHistory(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
+                                               _ptr(hist["info"]), steps, int(cursor)))
+        step_ms = int(self.prm.nsub) * float(self.prm.dtsim)
+        self._hist_t0, self._hist_ref0 = self.time_ms - int(cursor) * step_ms, self.ref_cursor - int(cursor)
+        self._hist_stats0 = self.stats.clone()
+
+    @property
+    def history_cursor(self):
+        """Closed-loop steps recorded so far = the step the next rollout records first (umpcBatchHistoryCursor)."""
+        return int(self.L.umpcBatchHistoryCursor(self.h))
+
+    def history(self):
+        """The recorded part of the tables as views: {"state": [cursor + 1, 18, B], "out": [cursor, 9, B], "status":
+        [cursor, B], "info": [cursor, 2, B]}, None for a record that is off."""
+        hist = getattr(self, "_hist", None)
+        if hist is None:
+            raise RuntimeError("no history is set (record_history)")
+        c = self.history_cursor
+        return {k: None if v is None else v[:c + 1 if k == "state" else c] for k, v in hist.items()}
+
+    def history_log(self, robots=(0,)):
+        """The recorded steps of the selected robots in the layout of control_test_log / the reference's controlTest log
+        (template/uprightmpc2.py:113,152-154), at MPC-step granularity: one row per closed-loop step k --
+        't' the fire time, 'y' = (p, Rb[:, 2], dq) and 'R' the state the step fired on (before it), 'u' the command with
+        the moments clipped at +-taulim as the plant saw them, 'accdes', 'pdes' from the reference trajectory, the task
+        or `ref` -- plus 'metric' = the logMetric pair over the recorded substeps (from the statistics the step kernel
+        accumulates per substep). Needs the state and out records. save_viewlog takes a log as is. Returns {robot: log}."""
+        h = self.history()
+        if h["state"] is None or h["out"] is None:
+            raise RuntimeError("history_log needs the state and out records")
+        n = self.history_cursor
+        nsub, dts, tl = int(self.prm.nsub), float(self.prm.dtsim), float(self.prm.taulim)
+        idx = torch.as_tensor(list(robots), device=self.device)
+        tt = self._hist_t0 + np.arange(n) * (nsub * dts)
+        st = h["state"][:n][:, :, idx].to(torch.float64).cpu().numpy()            # [n, 18, r]
+        out = h["out"][:, :, idx].to(torch.float64).cpu().numpy()
+        if getattr(self, "_reftab", None) is not None:
+            pdes = self._reftab[self._hist_ref0:self._hist_ref0 + n, 0:3][:, :, idx].to(torch.float64).cpu().numpy()
+        elif self._task_id() != 0:
+            pdes = np.stack([self.task_reference(t)[0:3][:, idx].to(torch.float64).cpu().numpy() for t in tt]) if n else np.zeros((0, 3, len(idx)))
+        else:
+            pdes = np.repeat(self.ref[0:3][:, idx].to(torch.float64).cpu().numpy()[None], n, 0)
+        met = ((self.stats - self._hist_stats0)[:, idx] / max(1, n * nsub)).to(torch.float64).cpu().numpy()
+        logs = {}
+        for c, r in enumerate(robots):
+            u = out[:, 0:3, c].copy()
+            u[:, 1:3] = np.clip(u[:, 1:3], -tl, tl)
+            logs[r] = {"t": tt.copy(), "y": np.concatenate((st[:, 0:3, c], st[:, 9:12, c], st[:, 12:18, c]), 1), "u": u,
+                       "pdes": pdes[:, :, c].copy(), "accdes": out[:, 3:9, c].copy(), "R": st[:, 3:12, c].copy(),
+                       "metric": (float(met[0, c]), float(met[1, c]))}
+        return logs
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

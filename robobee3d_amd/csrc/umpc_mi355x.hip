@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kBlock) void umpc_rollout_kernel(umpc::StepIO<T> a,
 
 // The all-assembly fp32 fast path (asmstep.py -> umpc_step_asm.h): the whole K-step loop of one wavefront is ONE
 // generated instruction stream; C++ only hands over the lane's offsets and the parameter block (kernarg).
-__global__ __launch_bounds__(kBlock) void umpc_rollout_asm_kernel(const umpcasm::StepParams prm, int B, int skew_ticks,
+__global__ __launch_bounds__(kBlock) void umpc_rollout_asm_kernel(const umpcasm::StepArgs prm, int B, int skew_ticks,
                                                                   int skew_groups) {
   __shared__ float4 lds[(umpcasm::STEP_LDS_BYTES_PER_LANE / 16) * kBlock];
   const int b = blockIdx.x * kBlock + threadIdx.x;
@@ -88,8 +88,8 @@ __global__ __launch_bounds__(kBlock) void umpc_rollout_asm_kernel(const umpcasm:
   }
   const unsigned ldsaddr = (unsigned)(size_t)(&lds[threadIdx.x]);
   const unsigned voff = (unsigned)b * 4u;
-  // the parameter block is read where it lies, in the kernarg segment (first argument, offset 0): taking &prm would
-  // copy it to private memory, which scalar loads cannot reach
+  // the parameter blocks (StepParams, then the history strides StepHist: struct StepArgs) are read where they lie, in the
+  // kernarg segment (first argument, offset 0): taking &prm would copy them to private memory, which scalar loads cannot reach
   (void)prm;
   const void *pp = (const void *)__builtin_amdgcn_kernarg_segment_ptr();
   UMPC_STEP_ASM(voff, ldsaddr, pp);
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void umpc_rollout_asm_kernel(const umpcasm:
 // and split the unknowns of ADMM iterations 2..maxIter over lanes 0..2 -- ~340 instructions per iteration instead of
 // 804. For batches that cannot give every SIMD a wave of its own anyway (B <= kQuadMaxB) and for the B = 1 drop-in.
 constexpr int kQuadMaxB = 16384;      // 1024 waves of 16 robots: one per SIMD
-__global__ __launch_bounds__(kBlock) void umpc_rollout_asm_quad_kernel(const umpcasm::StepParams prm, int B) {
+__global__ __launch_bounds__(kBlock) void umpc_rollout_asm_quad_kernel(const umpcasm::StepArgs prm, int B) {
   __shared__ float4 lds[(umpcasm::STEP_LDS_BYTES_PER_LANE / 16) * kBlock];
   // XCD-aware block -> robot-group mapping: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), and a
   // wave of 16 robots touches 64 B of every SoA row -- half a 128-B line. Consecutive groups therefore go to workgroups
@@ -144,7 +144,7 @@ __global__ void umpc_dropin_debug_kernel(DevParams<float> dprm, const float *sta
 // lane 4 -- outside the quad, it never enters the stream -- assembles the debug fields FIRST (the barrier is a convergence
 // point: its stores are issued before the stream starts), and the stream's own epilogue (s_waitcnt vmcnt(0), L2 write-back at
 // system scope, completion word) then releases them with the results: one launch, one completion word to poll.
-__global__ __launch_bounds__(kBlock) void umpc_dropin_quad_kernel(const umpcasm::StepParams prm, DevParams<float> dprm,
+__global__ __launch_bounds__(kBlock) void umpc_dropin_quad_kernel(const umpcasm::StepArgs prm, DevParams<float> dprm,
                                                                   const float *state, const float *ref, const float *t0dbg,
                                                                   float *l, float *u, float *q, float *Px, float *Ax) {
   __shared__ float4 lds[(umpcasm::STEP_LDS_BYTES_PER_LANE / 16) * kBlock];
@@ -421,7 +421,18 @@ struct umpc_batch {
   const void *reftab = nullptr;   // reference trajectory [steps][9][B] (umpcBatchSetRefTrajectory), kept by pointer; null = off
   long long reftab_steps = 0;     // ... slices it holds
   long long ref_cursor = 0;       // ... slice the next closed-loop step reads (advanced by every rollout with nsub > 0)
+  // step history (umpcBatchSetHistory), kept by pointer; each may be null = that record is off
+  void *hist_state = nullptr;     // [steps+1][18][B]
+  void *hist_out = nullptr;       // [steps][9][B]
+  int32_t *hist_status = nullptr; // [steps][B]
+  void *hist_info = nullptr;      // [steps][2][B]
+  long long hist_steps = 0;       // ... steps the tables hold
+  long long hist_cursor = 0;      // ... step the next rollout records first (advanced by every rollout with nsub > 0)
+  bool hist_on() const { return hist_state || hist_out || hist_status || hist_info; }
 };
+
+// elements the state / out / status / info pointers advance per closed-loop step of one launch (0 = in place)
+struct HistStep { size_t state = 0, out = 0, status = 0, info = 0; };
 
 // Parameter block of the all-assembly step kernel (umpcasm::StepParams, read by the stream with scalar loads)
 static umpcasm::StepParams make_step_params(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
@@ -451,29 +462,24 @@ static umpcasm::StepParams make_step_params(umpc_batch_t *h, int K, int nsub, vo
   return p;
 }
 
+// the launch itself; launch_rollout (below) has made the range checks of the reference trajectory and the history
 template <typename T>
-static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
-                          const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
-                          int32_t *status, void *info, void *stream) {
-  // reference trajectory: step k of this launch reads slice cursor + k of the table (`ref` is not read); refused BEFORE
-  // anything is launched when the launch would read past the table's end
+static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
+                        const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
+                        int32_t *status, void *info, const HistStep &hs, void *stream) {
+  // reference trajectory: step k of this launch reads slice cursor + k of the table (`ref` is not read)
   size_t ref_step = 0;
   if (h->reftab) {
-    if (h->ref_cursor + (long long)K > h->reftab_steps) {
-      g_err = "umpcBatchRollout: the reference trajectory ends before the launch does (cursor " + std::to_string(h->ref_cursor) +
-              " + K " + std::to_string(K) + " > steps " + std::to_string(h->reftab_steps) + ")";
-      return -1;
-    }
     ref_step = (size_t)9 * (size_t)h->B;
     ref = (const T *)h->reftab + (size_t)h->ref_cursor * ref_step;
   }
-  if (!state || !ctrl || !ref || !out) { g_err = "umpcBatchRollout: null array"; return -1; }
   if (h->reftab && nsub > 0) h->ref_cursor += K;
   umpc::StepIO<T> a;
   a.prm = make_dev<T>(h->prm);
   a.prm.nsub = nsub;
   a.B = h->B;
   a.state = (T *)state; a.ctrl = (T *)ctrl; a.ref = (const T *)ref; a.ref_step = (unsigned)ref_step;
+  a.state_step = (unsigned)hs.state; a.out_step = (unsigned)hs.out; a.status_step = (unsigned)hs.status; a.info_step = (unsigned)hs.info;
   a.prm.task = h->task;
   for (int i = 0; i < 4; ++i) a.prm.task_p[i] = (T)h->task_p[i];
   a.weights = (const T *)h->weights; a.t0 = (T)h->t_ms;
@@ -490,8 +496,12 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
     // parks D, E, c in, so the 559-row workspace does not count)
     const bool fits = (size_t)UMPC_CTRL_ROWS * (size_t)h->B * 4 < ((size_t)1 << 31);
     if (!no_asm && h->step_kernel != 1 && fits && K >= 1 && h->prm.maxIter >= 1) {
-      umpcasm::StepParams p = make_step_params(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info);
+      umpcasm::StepArgs pa;
+      umpcasm::StepParams &p = pa.p;
+      p = make_step_params(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info);
       p.refstep = (int32_t)(ref_step * 4);        // bytes per step (9 rows x B x 4 < 2^31: `fits` bounds 127 rows)
+      pa.h.statestep = (int32_t)(hs.state * 4); pa.h.outstep = (int32_t)(hs.out * 4);      // (18 rows at the most)
+      pa.h.statusstep = (int32_t)(hs.status * 4); pa.h.infostep = (int32_t)(hs.info * 4);
       // SURVEY 8(f) options of the same stream: task generator (a table of K entries written by a K-thread kernel ahead
       // of the launch, same stream), per-robot weights, the fused WL step
       if (h->task != 0) {
@@ -512,12 +522,12 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
       const int skew_ticks = (h->B >= 32768 && K >= 2) ? skew_us10 * 10 : 0;
       if (h->step_kernel == 3 || (h->step_kernel == 0 && h->global_B <= quad_max_b())) {
         hipLaunchKernelGGL(umpc_rollout_asm_quad_kernel, dim3((h->B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
-                           (hipStream_t)stream, p, h->B);
+                           (hipStream_t)stream, pa, h->B);
         h->last_kernel = "umpc_rollout_asm_quad_kernel";
         hipError_t eq = hipGetLastError();
         return eq == hipSuccess ? 0 : fail(eq, "umpcBatchRollout");
       }
-      hipLaunchKernelGGL(umpc_rollout_asm_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, p, h->B, skew_ticks,
+      hipLaunchKernelGGL(umpc_rollout_asm_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pa, h->B, skew_ticks,
                          skew_groups < 1 ? 1 : skew_groups);
       h->last_kernel = "umpc_rollout_asm_kernel";
       hipError_t e = hipGetLastError();
@@ -545,8 +555,33 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
       static const int quad64_max_b = [] { const char *e_ = getenv("UMPC_QUAD64"); return e_ ? atoi(e_) : 4096; }();
       const bool want_quad = h->step_kernel == 3 || (h->step_kernel == 0 && h->global_B <= quad64_max_b);
       if (!no_asm64 && h->step_kernel != 1 && h->prm.maxIter >= 2 && fits && want_quad) {
-        hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true, true>), dim3((h->B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
-                           (hipStream_t)stream, a, K, (const T *)actualT0, 0);
+        // Step history in this form: K launches of one step on moved pointers. The kernel cannot move them itself -- with any
+        // stride, even a bare `state + state_step` for the store, its scratch frame passes the recorded 600 B --
+        // so step k runs in place on state slice k + 1, which a device copy fills from slice k first. Same computation:
+        // the fire time is the in-kernel expression, actualT0 goes to the first step only.
+        const bool split = hs.state || hs.out || hs.status || hs.info;
+        for (int k = 0; k < (split ? K : 1); ++k) {
+          umpc::StepIO<T> ak = a;
+          if (split) {
+            if (hs.state) {
+              ak.state = a.state + ((size_t)k + 1) * hs.state;
+              const hipError_t ec = hipMemcpyAsync(ak.state, a.state + (size_t)k * hs.state, hs.state * sizeof(T),
+                                                   hipMemcpyDeviceToDevice, (hipStream_t)stream);
+              if (ec != hipSuccess) return fail(ec, "umpcBatchRollout: history");
+            }
+            ak.ref = a.ref + (size_t)k * ref_step; ak.out = a.out + (size_t)k * hs.out;
+            if (a.status) ak.status = a.status + (size_t)k * hs.status;
+            if (a.info) ak.info = a.info + (size_t)k * hs.info;
+            ak.t0 = a.t0 + T(k) * (T(nsub) * a.prm.dtsim);
+            ak.ref_step = ak.state_step = ak.out_step = ak.status_step = ak.info_step = 0;
+          }
+          hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true, true>), dim3((h->B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
+                             (hipStream_t)stream, ak, split ? 1 : K, k == 0 ? (const T *)actualT0 : nullptr, 0);
+          if (split) {      // (a failed step stops the sequence; launch_rollout puts the cursors and the clock back)
+            const hipError_t el = hipGetLastError();
+            if (el != hipSuccess) return fail(el, "umpcBatchRollout: history");
+          }
+        }
         h->last_kernel = "umpc_rollout_kernel<double, LDSF, ASM64, QUAD>";
       } else if (!no_asm64 && h->step_kernel != 1 && h->prm.maxIter >= 1 && fits) {
         hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, K,
@@ -566,6 +601,63 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
   h->last_kernel = sizeof(T) == 4 ? "umpc_rollout_kernel<float>" : "umpc_rollout_kernel<double>";
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(e, "umpcBatchRollout");
+}
+
+// umpcBatchRollout / umpcBatchUpdate: the refusals (before anything is launched or copied), then the launch -- in place, or,
+// with a step history set (umpcBatchSetHistory) and a plant (nsub > 0), through the tables: the kernels' own stores of step k
+// land in slice cursor + k (state: cursor + k + 1), and stream-ordered device copies keep the caller's arrays what they are
+// without a history (state in; state, out, status, info back: five copies per launch at the most, none per step).
+template <typename T>
+static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
+                          const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
+                          int32_t *status, void *info, void *stream) {
+  if (h->reftab && h->ref_cursor + (long long)K > h->reftab_steps) {
+    g_err = "umpcBatchRollout: the reference trajectory ends before the launch does (cursor " + std::to_string(h->ref_cursor) +
+            " + K " + std::to_string(K) + " > steps " + std::to_string(h->reftab_steps) + ")";
+    return -1;
+  }
+  const bool hist = h->hist_on() && nsub > 0 && K >= 1;
+  if (hist && h->hist_cursor + (long long)K > h->hist_steps) {
+    g_err = "umpcBatchRollout: the step history ends before the launch does (cursor " + std::to_string(h->hist_cursor) +
+            " + K " + std::to_string(K) + " > steps " + std::to_string(h->hist_steps) + ")";
+    return -1;
+  }
+  if (!state || !ctrl || (!ref && !h->reftab) || !out) { g_err = "umpcBatchRollout: null array"; return -1; }
+  HistStep hs;
+  if (!hist) return launch_steps<T>(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info, hs, stream);
+  const size_t B = (size_t)h->B, c = (size_t)h->hist_cursor;
+  const hipStream_t s = (hipStream_t)stream;
+  T *st = (T *)state, *o = (T *)out, *inf = (T *)info;
+  int32_t *sw = status;
+  hipError_t e = hipSuccess;
+  if (h->hist_state) {
+    hs.state = 18 * B;
+    st = (T *)h->hist_state + c * hs.state;
+    if (st != (T *)state) e = hipMemcpyAsync(st, state, hs.state * sizeof(T), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return fail(e, "umpcBatchRollout: history");
+  }
+  if (h->hist_out) { hs.out = 9 * B; o = (T *)h->hist_out + c * hs.out; }
+  if (h->hist_status) { hs.status = B; sw = h->hist_status + c * hs.status; }
+  if (h->hist_info) { hs.info = 2 * B; inf = (T *)h->hist_info + c * hs.info; }
+  // a failure from here on (a HIP error of a copy or a launch) leaves the cursors and the clock where they were: the
+  // tables and the arguments may hold part of the launch, the handle never claims steps it has not recorded
+  const long long ref_cursor0 = h->ref_cursor, hist_cursor0 = h->hist_cursor;
+  const double t_ms0 = h->t_ms;
+  int rc = launch_steps<T>(h, K, nsub, st, ctrl, ref, actualT0, Ib, gain, o, stats, sw, inf, hs, stream);
+  if (!rc) {
+    const size_t last = (size_t)K - 1;
+    if (h->hist_state && st + (size_t)K * hs.state != (T *)state)
+      e = hipMemcpyAsync(state, st + (size_t)K * hs.state, hs.state * sizeof(T), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && h->hist_out) e = hipMemcpyAsync(out, o + last * hs.out, hs.out * sizeof(T), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && h->hist_status && status)
+      e = hipMemcpyAsync(status, sw + last * hs.status, hs.status * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && h->hist_info && info)
+      e = hipMemcpyAsync(info, inf + last * hs.info, hs.info * sizeof(T), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) rc = fail(e, "umpcBatchRollout: history");
+  }
+  if (rc) { h->ref_cursor = ref_cursor0; h->hist_cursor = hist_cursor0; h->t_ms = t_ms0; return rc; }
+  h->hist_cursor = hist_cursor0 + K;
+  return 0;
 }
 
 void umpc_set_error(const char *msg) { g_err = msg; }
@@ -688,6 +780,25 @@ int umpcBatchSetRefTrajectory(umpc_batch_t *h, const void *tab, long long steps,
   return 0;
 }
 long long umpcBatchRefCursor(const umpc_batch_t *h) { return h ? h->ref_cursor : 0; }
+
+int umpcBatchSetHistory(umpc_batch_t *h, void *state_hist, void *out_hist, int32_t *status_hist, void *info_hist,
+                        long long steps, long long cursor0) {
+  if (!h) { g_err = "umpcBatchSetHistory: bad argument"; return -1; }
+  if (!state_hist && !out_hist && !status_hist && !info_hist) {
+    h->hist_state = h->hist_out = h->hist_info = nullptr; h->hist_status = nullptr; h->hist_steps = 0; h->hist_cursor = 0;
+    return 0;
+  }
+  if (steps < 1 || cursor0 < 0 || cursor0 > steps) { g_err = "umpcBatchSetHistory: bad argument (steps >= 1, 0 <= cursor0 <= steps)"; return -1; }
+  if (h->prm.nsub == 0) {
+    g_err = "umpcBatchSetHistory: the handle has no plant (nsub = 0): its rollouts never write the state, there is no trajectory to record";
+    return -1;
+  }
+  if ((size_t)18 * (size_t)h->B > (size_t)0x7fffffff) { g_err = "umpcBatchSetHistory: batch too large (a slice is a 32-bit stride)"; return -1; }
+  h->hist_state = state_hist; h->hist_out = out_hist; h->hist_status = status_hist; h->hist_info = info_hist;
+  h->hist_steps = steps; h->hist_cursor = cursor0;
+  return 0;
+}
+long long umpcBatchHistoryCursor(const umpc_batch_t *h) { return h ? h->hist_cursor : 0; }
 
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
                        const void *ref, void *tab, void *stream) {
@@ -1053,22 +1164,25 @@ int umpcUpdate(UprightMPC_t *up, float uquad[3], float accdes[6], const float p0
     // the step kernel (B = 1, all assembly) and the debug-field kernel on two streams, completion by polling the two words
     // they release at system scope: no stream synchronisation on the critical path
     const unsigned seq = ++s.seq ? s.seq : ++s.seq;       // never 0 (the words start at 0)
-    umpcasm::StepParams p = make_step_params(s.h, 1, 0, d + O_STATE, s.ctrl, d + O_REF, d + O_AT0, nullptr, nullptr, d + O_OUT,
-                                             nullptr, (int32_t *)(d + O_STATUS), d + O_INFO);
+    umpcasm::StepArgs pa;                                  // (the drop-in records no history: strides 0)
+    umpcasm::StepParams &p = pa.p;
+    p = make_step_params(s.h, 1, 0, d + O_STATE, s.ctrl, d + O_REF, d + O_AT0, nullptr, nullptr, d + O_OUT, nullptr,
+                         (int32_t *)(d + O_STATUS), d + O_INFO);
+    pa.h = umpcasm::StepHist{0, 0, 0, 0};
     p.done = d + O_DONE0; p.seq = (int)seq;
     // UMPC_DROPIN_TWO_STREAMS=1: round 4's form (step kernel + debug-field kernel on two streams, two completion words), A/B
     static const bool two_streams = getenv("UMPC_DROPIN_TWO_STREAMS") != nullptr;
     const bool one_launch = quad_max_b() >= 1 && !two_streams;
     if (one_launch) {
-      hipLaunchKernelGGL(umpc_dropin_quad_kernel, dim3(1), dim3(kBlock), 0, s.stream, p, make_dev<float>(s.h->prm),
+      hipLaunchKernelGGL(umpc_dropin_quad_kernel, dim3(1), dim3(kBlock), 0, s.stream, pa, make_dev<float>(s.h->prm),
                          (const float *)(d + O_STATE), (const float *)(d + O_REF), (const float *)(d + O_T0DBG), d + O_L,
                          d + O_U, d + O_Q, d + O_PX, d + O_AX);
       *(unsigned *)(hb + O_DONE1) = seq;           // (one completion word in this form: the second one is the host's own)
     } else {
       if (quad_max_b() >= 1)
-        hipLaunchKernelGGL(umpc_rollout_asm_quad_kernel, dim3(1), dim3(kBlock), 0, s.stream, p, 1);
+        hipLaunchKernelGGL(umpc_rollout_asm_quad_kernel, dim3(1), dim3(kBlock), 0, s.stream, pa, 1);
       else
-        hipLaunchKernelGGL(umpc_rollout_asm_kernel, dim3(1), dim3(kBlock), 0, s.stream, p, 1, 0, 1);
+        hipLaunchKernelGGL(umpc_rollout_asm_kernel, dim3(1), dim3(kBlock), 0, s.stream, pa, 1, 0, 1);
       hipLaunchKernelGGL(umpc_dropin_debug_kernel, dim3(1), dim3(64), 0, s.stream2, make_dev<float>(s.h->prm),
                          (const float *)(d + O_STATE), (const float *)(d + O_REF), (const float *)(d + O_T0DBG), d + O_L, d + O_U,
                          d + O_Q, d + O_PX, d + O_AX, (unsigned *)(d + O_DONE1), seq);

@@ -464,6 +464,10 @@ struct StepIO {
   // ref + k * ref_step (elements: 9 * B; 0 = one frozen reference). 32 bits and LAST in the struct: the fp64 step kernels
   // keep their measured scratch frames with it here (csrc/resource_limits.json), a 64-bit member next to `ref` grew one.
   unsigned ref_step;
+  // Step history (umpcBatchSetHistory): step k of the launch reads state + k * state_step and writes state + (k + 1) *
+  // state_step; its out / status / info stores go to slice k of their tables (elements: 18 B, 9 B, B, 2 B; all 0 = every
+  // step overwrites the same arrays). 32 bits and last, for the same reason.
+  unsigned state_step, out_step, status_step, info_step;
 };
 
 // One closed-loop step of robot b: controller step (= umpcUpdate) + nsub plant substeps.
@@ -491,6 +495,13 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
   // laundered through an empty asm at every phase boundary so that the compiler re-derives the
   // (cheap) addresses instead of keeping ~400 precomputed 64-bit pointers alive across the loop.
   unsigned bb = (unsigned)b;
+// step history: this step's slices (wave-uniform bases, re-derived at every use like the row addresses; all strides 0
+// without a history). The fp64 QUAD form moves nothing: with any of the strides, even a bare `state + state_step` for the
+// store, its scratch frame passes the recorded limit (608 .. 612 B against 600, csrc/resource_limits.json), so the host issues
+// its steps one per launch on moved pointers (umpc_mi355x.hip, launch_steps).
+#define UMPC_STATE_IN (QUAD ? a.state : a.state + (size_t)step * a.state_step)
+#define UMPC_STATE_OUT (QUAD ? a.state : a.state + ((size_t)step + 1) * a.state_step)
+#define UMPC_OUT_K (QUAD ? a.out : a.out + (size_t)step * a.out_step)
 // scheduling fence: nothing (in particular no LDS read) is moved across it
 #define UMPC_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define UMPC_PHASE_FENCE() asm volatile("" : "+v"(bb)::"memory")
@@ -553,11 +564,11 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
   {
     T p0[3], R0[9], dq0[6], ref[9];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) p0[i] = GLD(a.state, i);
+    for (int i = 0; i < 3; ++i) p0[i] = GLD(UMPC_STATE_IN, i);
 #pragma unroll
-    for (int i = 0; i < 9; ++i) R0[i] = GLD(a.state, 3 + i);
+    for (int i = 0; i < 9; ++i) R0[i] = GLD(UMPC_STATE_IN, 3 + i);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) dq0[i] = GLD(a.state, 12 + i);
+    for (int i = 0; i < 6; ++i) dq0[i] = GLD(UMPC_STATE_IN, 12 + i);
 #pragma unroll
     for (int i = 0; i < 9; ++i) ref[i] = GLD(a.ref + (size_t)step * a.ref_step, i);
     task_reference(prm.task, prm.task_p, tnow, ref);
@@ -818,11 +829,11 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
   }
   T p0[3], R0[9], dq0[6];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) R0[i] = GLD(a.state, 3 + i);
+  for (int i = 0; i < 9; ++i) R0[i] = GLD(UMPC_STATE_IN, 3 + i);
   // (fp64 assembly route: p and dq are fetched after the residual block, which clobbers the register files)
 #define UMPC_PC_LOAD_PDQ() do { \
-  _Pragma("unroll") for (int i = 0; i < 3; ++i) p0[i] = GLD(a.state, i); \
-  _Pragma("unroll") for (int i = 0; i < 6; ++i) dq0[i] = GLD(a.state, 12 + i); } while (0)
+  _Pragma("unroll") for (int i = 0; i < 3; ++i) p0[i] = GLD(UMPC_STATE_IN, i); \
+  _Pragma("unroll") for (int i = 0; i < 6; ++i) dq0[i] = GLD(UMPC_STATE_IN, 12 + i); } while (0)
   if constexpr (!ASM64) UMPC_PC_LOAD_PDQ();
   int status = ST_UNSOLVED;
   T pri_res = T(0), dua_res = T(0);
@@ -1053,11 +1064,14 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
   }
   GLD(a.ctrl, NX + 2 * NC) = T0next;
 #pragma unroll
-  for (int i = 0; i < 3; ++i) GLD(a.out, i) = uq[i];
+  for (int i = 0; i < 3; ++i) GLD(UMPC_OUT_K, i) = uq[i];
 #pragma unroll
-  for (int i = 0; i < NY; ++i) GLD(a.out, 3 + i) = acc[i];
-  if (a.status) a.status[bb] = status;
-  if (a.info) { GLD(a.info, 0) = pri_res; GLD(a.info, 1) = dua_res; }
+  for (int i = 0; i < NY; ++i) GLD(UMPC_OUT_K, 3 + i) = acc[i];
+  if (a.status) (QUAD ? a.status : a.status + (size_t)step * a.status_step)[bb] = status;
+  if (a.info) {
+    T *const info_k = QUAD ? a.info : a.info + (size_t)step * a.info_step;
+    GLD(info_k, 0) = pri_res; GLD(info_k, 1) = dua_res;
+  }
 
   UMPC_TMARK(5);
   // ---- plant: template/uprightmpc2.py:148-151 ----
@@ -1078,26 +1092,29 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
       s_eff += uc[1] * uc[1] + uc[2] * uc[2];
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) GLD(a.state, i) = p0[i];
+    for (int i = 0; i < 3; ++i) GLD(UMPC_STATE_OUT, i) = p0[i];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) GLD(a.state, 3 + i) = R0[i];
+    for (int i = 0; i < 9; ++i) GLD(UMPC_STATE_OUT, 3 + i) = R0[i];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) GLD(a.state, 12 + i) = dq0[i];
+    for (int i = 0; i < 6; ++i) GLD(UMPC_STATE_OUT, 12 + i) = dq0[i];
     if (a.stats) { GLD(a.stats, 0) = s_err; GLD(a.stats, 1) = s_eff; }
   }
 #ifdef UMPC_PHASE_TIMING
   UMPC_TMARK(6);
 #pragma unroll
-  for (int i = 0; i < 6; ++i) GLD(a.out, 3 + i) = T(tmark[i + 1] - tmark[i]);
+  for (int i = 0; i < 6; ++i) GLD(UMPC_OUT_K, 3 + i) = T(tmark[i + 1] - tmark[i]);
 #ifdef UMPC_ASM64_TIMING   /* header generated with UMPC_ASM64_TIMING=1: the block's own stamps, LDS words 297..302 */
   if constexpr (ASM64) {
     const long long *st = asm64_stamps;
     // out rows 0..2: block prologue, (first iteration .. loop), epilogue; rows 3.. keep the phase intervals
-    GLD(a.out, 0) = T(st[1] - st[0]); GLD(a.out, 1) = T(st[4] - st[1]); GLD(a.out, 2) = T(st[5] - st[4]);
+    GLD(UMPC_OUT_K, 0) = T(st[1] - st[0]); GLD(UMPC_OUT_K, 1) = T(st[4] - st[1]); GLD(UMPC_OUT_K, 2) = T(st[5] - st[4]);
   }
 #endif
 #endif
 #undef UMPC_TMARK
+#undef UMPC_STATE_IN
+#undef UMPC_STATE_OUT
+#undef UMPC_OUT_K
 #undef GLD
 #undef UMPC_PHASE_FENCE
 #undef UMPC_SCHED_FENCE

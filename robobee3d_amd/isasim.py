@@ -509,6 +509,8 @@ SALU = {
     "s_lshl_b32": lambda mc, t: _sdst(mc, t, mc.s32(t[2]) << (mc.s32(t[3]) & 31)),
     "s_cmp_lt_i32": lambda mc, t: setattr(mc, "scc", int(_signed(mc.s32(t[1])) < _signed(mc.s32(t[2])))),
     "s_cmp_gt_i32": lambda mc, t: setattr(mc, "scc", int(_signed(mc.s32(t[1])) > _signed(mc.s32(t[2])))),
+    "s_cmp_lt_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) < mc.s32(t[2]))),
+    "s_cselect_b32": lambda mc, t: _sdst(mc, t, mc.s32(t[2]) if mc.scc else mc.s32(t[3])),
     "s_cmp_lg_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) != mc.s32(t[2]))),
     "s_cmp_eq_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) == mc.s32(t[2]))),
     "s_cmp_eq_u64": lambda mc, t: setattr(mc, "scc", int(mc.s64(t[1]) == mc.s64(t[2]))),

@@ -72,6 +72,13 @@ def table_block(tab, lo, hi):
     return tab[..., lo:hi].contiguous()
 
 
+def history_block(hist, lo, hi):
+    """The block [lo, hi) of the robots of a step history (BatchUprightMPC.history(): a dict of tables whose last axis is the
+    robot index, None for a record that is off), table by table as table_block: the history of a block of a job equals these
+    columns of the undivided run's history bit for bit."""
+    return {k: None if v is None else table_block(v, lo, hi) for k, v in hist.items()}
+
+
 def max_over_ranks(value, device="cpu"):
     t = torch.tensor([float(value)], dtype=torch.float64, device=device)
     if dist.is_initialized():
