@@ -260,6 +260,38 @@ int umpcBatchSetHistory(umpc_batch_t *h, void *state_hist, void *out_hist, int32
                         long long steps, long long cursor0);
 long long umpcBatchHistoryCursor(const umpc_batch_t *h);
 
+/* Velocity impulses: a push per closed-loop step and per robot INSIDE a rollout launch (the disturbance experiment of the
+ * reference's harness, controlTest(..., tpert=t): dq[1] += 2 once, template/uprightmpc2.py:130-133; a Monte-Carlo sweep of
+ * push time x direction x size is one batch). The input side of the step history, with the conventions of its two
+ * neighbours: a device table in the handle's dtype, robot index fastest, kept by pointer, not copied (it must stay
+ * allocated until replaced or the handle destroyed); tab == NULL switches impulses off:
+ *   tab [steps][6][B]   slice c = (dv_world[3], domega_body[3]), added to rows 12..17 of the state
+ *                       AFTER the last plant substep of closed-loop step c and BEFORE that step's state store.
+ * So the `state` argument holds the kicked state after the launch, step c + 1's controller reads it, and with a step
+ * history state slice c + 1 holds it. This is the reference's placement (there the kick precedes the MPC call of the same
+ * loop iteration, which is the end of the previous step here); a push before the first step stays the caller's job, by
+ * editing `state`. The addition is ONE IEEE add per component in the handle's dtype: a launch of K steps with a table equals
+ * K single-step launches with state[12:18] += tab[c] done in between in that dtype, bit for bit, in every kernel form. An
+ * all-zero slice is an add like any other (-0.0 + 0.0 = +0.0): "zero table" equals "no table" by value, not by bit pattern.
+ * The cursor starts at `cursor0` and advances by K with every umpcBatchRollout whose nsub > 0, independently of the
+ * reference and history cursors; a rollout that would read past `steps` is refused (-1, umpcLastError) BEFORE anything is
+ * launched or copied, and cursors and umpcBatchTime stay where they were -- as they do after a HIP error in the middle of
+ * a rollout. Refused at set time (-1): a handle with nsub = 0, steps < 1, cursor0 outside [0, steps]. umpcBatchUpdate,
+ * umpcBatchPlant and the B = 1 drop-in neither apply a slice nor move the cursor. umpcBatchReactive honours the table (the
+ * reference's MPC-vs-reactive comparison under one push): it adds slice cursor + j after substep (j + 1) * nsub - 1 and
+ * advances the cursor by nsteps / nsub; with a table set it is refused when nsteps % nsub != 0 or the table would be overrun.
+ * The fp32 assembly kernels (lane and quad) and the C++ kernels fp32, fp64 lane and fp64 C++ add the slice in the kernel:
+ * one launch, six loads and six adds per robot-step; without a table a step costs a few scalar instructions more. One form
+ * is an exception, as for the history: the fp64 kernel with one robot per lane quad (the automatic choice for fp64 at
+ * B <= 4 096, or umpcBatchSetStepKernel 3) takes no member more inside its scratch budget, so with impulses set the library
+ * issues its K steps as K single-step launches with a small add kernel (dq += slice, one lane per robot) after each; the
+ * results are the same.
+ * Combines with a reference trajectory, the tasks, per-robot weights, Ib, gain, actualT0, the WL coupling, both plant
+ * modes, both dtypes, a step history and umpcBatchSetStepKernel 0..3. Memory: 6 x B x steps scalars -- fp32, B = 65 536,
+ * 500 steps: 786 MB -- long runs are chunked: set the next part of the table with cursor0 = 0. */
+int umpcBatchSetImpulses(umpc_batch_t *h, const void *tab, long long steps, long long cursor0);
+long long umpcBatchImpulseCursor(const umpc_batch_t *h);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

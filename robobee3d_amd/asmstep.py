@@ -92,6 +92,15 @@ for _k, _n in enumerate(HIST_INTS):
     OFF[_n] = HIST_OFF + 4 * _k
 HIST_BYTES = 4 * len(HIST_INTS)
 S_HIST = 32               # s[32:35]: the block's words at the end of a step (the lane masks s30..s37 are dead between steps)
+# A THIRD block, struct umpcasm::StepImp, follows StepHist: the velocity IMPULSES (umpcBatchSetImpulses). `imp` points at slice
+# `cursor` of a table [steps][6][B] (null = no impulses), `impstep` is the bytes per slice; step k of the launch adds slice k
+# to dq (rows 12..17 of the state) after its last plant substep and ahead of its state store. The stream reads the block
+# through an SGPR offset, so the loads with an immediate offset >= HIST_OFF stay the two history loads.
+IMP_OFF = HIST_OFF + HIST_BYTES
+assert IMP_OFF % 8 == 0
+OFF["imp"], OFF["impstep"] = IMP_OFF, IMP_OFF + 8
+IMP_BYTES = 16            # pointer, stride, one word of padding (the block is read with one x4 load)
+S_IMP = 32                # s[32:33] the slice address, s34 the stride / low offset word, s35 the high offset word (dead lane masks)
 
 VFIRST, VEND = 2, 256
 XV_N, XV_B = 10, 246      # L entries kept in VGPRs beyond the loop's fixed layout (asmgen.XV_COUNT / XV_BASE)
@@ -386,6 +395,42 @@ class StepGen:
         e("s_cmp_lt_u32", sg(lo), sg(sstep))
         e("s_cselect_b32", sg(sstep), 1, 0)
         e("s_add_i32", sg(lo + 1), sg(lo + 1), sg(sstep))
+
+    def impulse(self, Y0, YS):
+        """Velocity impulse of this closed-loop step (umpcBatchSetImpulses): dq (v<Y0+12> .. v<Y0+17>) += slice S_STEP of the
+        table, one IEEE add per component, after the last plant substep (the quad RK4 has handed back to the one-lane
+        layout) and ahead of the state store. The slice address imp + S_STEP * impstep is formed here, in lane masks that
+        are dead from the end of phase C's stores to the end of the step, from the step counter: no pointer lives across
+        the step. The 64-bit add carries by an unsigned compare and a skipped increment (s_add_u32 / s_addc_u32 stay the
+        mark of the `ref` advance, s_cmp_lt_u32 / s_cselect_b32 that of the history advances); the rows of the slice are reached by
+        moving that scalar base, the lanes' offset stays v0. With a null table the step executes five scalar instructions
+        more and nothing else. The six words land in v<YS> .. v<YS+5>, free after the plant."""
+        e = self.e
+        lab_off = self.label()
+        lo, hi, st, oh = S_IMP, S_IMP + 1, S_IMP + 2, S_IMP + 3
+        e("s_mov_b32", sg(S_TMP), IMP_OFF)
+        e("s_load_dwordx4", "s[%d:%d]" % (S_IMP, S_IMP + 3), sp(S_PBLK), sg(S_TMP))
+        e("s_waitcnt", "lgkmcnt(0)")
+        e("s_cmp_eq_u64", sp(lo), 0)
+        e("s_cbranch_scc1", lab_off + "f")
+        e("s_mul_hi_u32", sg(oh), sg(S_STEP), sg(st))
+        e("s_mul_i32", sg(st), sg(S_STEP), sg(st))
+        e("s_add_i32", sg(hi), sg(hi), sg(oh))
+        for i in range(6):
+            # row i of the slice: the base moves on by the slice offset, then by `stride` per row -- scalar adds, so that
+            # the lanes' own offset stays v0 and no vector instruction forms an address
+            addend = st if i == 0 else S_INT["stride"]
+            lab_nc = self.label()
+            e("s_add_i32", sg(lo), sg(lo), sg(addend))
+            e("s_cmp_gt_u32", sg(addend), sg(lo))        # the low word wrapped exactly when the addend is above the sum
+            e("s_cbranch_scc0", lab_nc + "f")
+            e("s_add_i32", sg(hi), sg(hi), 1)
+            e("label", lab_nc)
+            e("global_load_dword", v(YS + i), "v0", sp(lo))
+        e("s_waitcnt", "vmcnt(0)")
+        for i in range(6):
+            e("v_add_f32", v(Y0 + 12 + i), v(Y0 + 12 + i), v(YS + i))
+        e("label", lab_off)
 
     def load_rows(self, ptr, first_row, regs, voff=None):
         own = voff is None
@@ -2032,6 +2077,7 @@ class StepGen:
         e("s_cmp_gt_i32", sg(S_SUB), 0)
         e("s_cbranch_scc1", top + "b")
         e("label", lab_done)
+        self.impulse(Y0, YS)
         # step history: both state loads of this step (phase A, phase C) are behind us and its only state store follows, so
         # the base moves on by `statestep` bytes HERE -- the store fills slice k + 1, which the next step's loads read. The
         # word is read from the second parameter block once per step (no SGPR is free for the whole kernel in the quad form).
@@ -2277,8 +2323,12 @@ def write(path=None, N=3, perm=None, quad=False):
                 "// step history (umpcBatchSetHistory): bytes the state / out / status / info pointers advance per closed-loop step,",
                 "// read by the stream at byte %d of the kernarg segment: the kernels take ONE StepArgs as their first argument" % HIST_OFF,
                 "struct StepHist {"] + ["  int32_t %s;" % n for n in HIST_INTS] + ["};",
-                "struct StepArgs {", "  StepParams p;", "  StepHist h;", "};",
+                "// velocity impulses (umpcBatchSetImpulses): slice `cursor` of the table [steps][6][B] (null: none) and the bytes per slice,",
+                "// read by the stream at byte %d of the kernarg segment" % IMP_OFF,
+                "struct StepImp {", "  const void *imp;", "  int32_t impstep;", "  int32_t pad_;", "};",
+                "struct StepArgs {", "  StepParams p;", "  StepHist h;", "  StepImp i;", "};",
                 "static_assert(offsetof(StepArgs, h) == %d && sizeof(StepHist) == %d, \"StepHist layout\");" % (HIST_OFF, HIST_BYTES),
+                "static_assert(offsetof(StepArgs, i) == %d && sizeof(StepImp) == %d && offsetof(StepImp, impstep) == 8, \"StepImp layout\");" % (IMP_OFF, IMP_BYTES),
                 "constexpr int STEP_LDS_BYTES_PER_LANE = %d;" % (NLDS * 4), "}  // namespace umpcasm",
                 "// inputs: v0 = 4 * robot, v1 = lane LDS address, s[4:5] = &StepParams (kernarg)",
                 "#define UMPC_STEP_ASM(voff, ldsaddr, params) asm volatile( \\"]
@@ -2326,9 +2376,9 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
     Returns the executed instruction count (pseudo-instructions excluded)."""
     import numpy as np
     from . import isasim
-    base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(PTRS)}
+    base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(PTRS + ["impulse"])}
     ptr_xform = ptr_xform or (lambda a: a)
-    blob = bytearray(HIST_OFF + HIST_BYTES)
+    blob = bytearray(IMP_OFF + IMP_BYTES)
     for n in PTRS:
         struct.pack_into("<Q", blob, OFF[n], ptr_xform(base_of[n]) if arrays.get(n) is not None else 0)
     allints = dict(ints, stride=STRIDE)
@@ -2340,8 +2390,12 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
         struct.pack_into("<i", blob, OFF[n], int(allints[n]))
     for n in FLOATS:
         struct.pack_into("<f", blob, OFF[n], float(floats[n]))
+    # the third block: arrays["impulse"] = a table of slices [6] per step (rows 6k .. 6k+5 = slice k), impstep = 6 * STRIDE
+    allints.setdefault("impstep", 6 * STRIDE if arrays.get("impulse") is not None else 0)
+    struct.pack_into("<Q", blob, OFF["imp"], ptr_xform(base_of["impulse"]) if arrays.get("impulse") is not None else 0)
+    struct.pack_into("<i", blob, OFF["impstep"], int(allints["impstep"]))
     regions = [(PBASE, 4, np.frombuffer(bytes(blob), np.uint32))] + \
-        [(base_of[n], 4 if n in FLAT else STRIDE, arrays[n]) for n in PTRS if arrays.get(n) is not None]
+        [(base_of[n], 4 if n in FLAT else STRIDE, arrays[n]) for n in PTRS + ["impulse"] if arrays.get(n) is not None]
     m = isasim.Machine(ins, regions=regions, sgpr={S_PARAM: PBASE & 0xFFFFFFFF, S_PARAM + 1: PBASE >> 32}, vgpr={0: 0},
                        lds=np.zeros((1, NLDS), np.uint32), max_exec=max_exec, quad=_quad())
     isasim.run(m)

@@ -120,6 +120,32 @@ def hover_initial_conditions_device(B, seed, dtype=torch.float32, tilt=0.5, inde
     return state.to(dtype).contiguous(), ref.to(dtype).contiguous(), (a, b)
 
 
+def impulse_table(steps, B, events, dtype=torch.float32, device="cpu"):
+    """Dense impulse table [steps, 6, B] for BatchUprightMPC.set_impulses from sparse events (step, robots, vec6): at the end
+    of closed-loop step `step` the robots `robots` (None = all, an index, a slice or a sequence of indices) get
+    (dv_world[3], domega_body[3]) = vec6, a [6] vector for all of them or [6, n] with one column per robot. Events that meet
+    on one (step, robot) add up, in the order given and in `dtype`. The reference's experiment, controlTest(tpert=t)
+    (template/uprightmpc2.py:130-133), is the single event (step of t, None, (0, 2, 0, 0, 0, 0))."""
+    tab = torch.zeros((int(steps), 6, int(B)), dtype=dtype, device=device)
+    for step, robots, vec in events:
+        step = int(step)
+        if not 0 <= step < int(steps):
+            raise ValueError("impulse_table: step %d is outside the table of %d steps" % (step, int(steps)))
+        vec = torch.as_tensor(np.asarray(vec, np.float64)).to(dtype).to(device)
+        if vec.shape[0] != 6 or vec.dim() > 2:
+            raise ValueError("impulse_table: an impulse is [6] or [6, n], got %r" % (tuple(vec.shape),))
+        if robots is None:
+            sel = slice(None)
+        elif isinstance(robots, slice):
+            sel = robots
+        else:
+            sel = torch.as_tensor(np.atleast_1d(np.asarray(robots, np.int64)), device=device)
+            if len(torch.unique(sel)) != len(sel):
+                raise ValueError("impulse_table: a robot is named twice in one event")
+        tab[step, :, sel] += vec[:, None] if vec.dim() == 1 else vec
+    return tab
+
+
 class BatchUprightMPC:
     """B independent uprightmpc2 controllers (+ plants), one GPU lane each."""
 
@@ -311,6 +337,44 @@ class BatchUprightMPC:
                        "metric": (float(met[0, c]), float(met[1, c]))}
         return logs
 
+    def set_impulses(self, tab, cursor0=0):
+        """A velocity kick per closed-loop step and per robot inside the rollout launch (umpcBatchSetImpulses): tab
+        [steps, 6, B] holds (dv_world[3], domega_body[3]); slice impulse_cursor + k is added to self.state[12:18] after the last
+        plant substep of step k of a rollout and before its state store -- the next step's controller, the state history's
+        slice k + 1 and self.state after the launch see the kicked state (the placement of controlTest(tpert=...),
+        template/uprightmpc2.py:130-133). One IEEE add per component: rollout(K) equals K times rollout(1) with
+        `state[12:18] += tab[c]` in between, bit for bit. The cursor starts at `cursor0` and advances with every rollout();
+        a rollout that would run past the table raises before anything is launched. reactive_rollout() honours the table
+        too (one slice per nsub substeps; nsteps must then be a multiple of nsub); update() and plant() do not. None
+        switches impulses off. impulse_table() builds a table from sparse events. Memory: 24 B x B x steps in fp32 -- chunk
+        long runs."""
+        if tab is None:
+            self._check(self.L.umpcBatchSetImpulses(self.h, None, 0, 0))
+            self._imptab = None
+            return
+        t = torch.as_tensor(tab, dtype=self.dtype).to(self.device).contiguous()
+        if t.dim() != 3 or tuple(t.shape[1:]) != (6, self.B):
+            raise ValueError("impulse table must be [steps, 6, %d], got %r" % (self.B, tuple(t.shape)))
+        self._check(self.L.umpcBatchSetImpulses(self.h, _ptr(t), int(t.shape[0]), int(cursor0)))
+        self._imptab = t  # keep alive: the library stores the pointer
+
+    def rewind_impulses(self, cursor=0):
+        """Apply the table of set_impulses again from slice `cursor` on (a repeated experiment, or a chunked run whose table was
+        refilled in place): no copy, no allocation."""
+        t = getattr(self, "_imptab", None)
+        if t is None:
+            raise RuntimeError("no impulses are set (set_impulses)")
+        self._check(self.L.umpcBatchSetImpulses(self.h, _ptr(t), int(t.shape[0]), int(cursor)))
+
+    @property
+    def impulse_cursor(self):
+        """The slice of the impulse table the next closed-loop step adds (umpcBatchImpulseCursor)."""
+        return int(self.L.umpcBatchImpulseCursor(self.h))
+
+    def impulse_table(self, steps, events):
+        """impulse_table() for this handle: [steps, 6, B] in its dtype, on its device."""
+        return impulse_table(steps, self.B, events, self.dtype, self.device)
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of
@@ -420,7 +484,7 @@ class BatchUprightMPC:
             self._check(self.L.umpcBatchTaskReference(self.h, float(t_ms), _ptr(self.ref), _ptr(out), self._stream()))
         return out
 
-    def control_test_log(self, tend, robots=(0,), use_mpc=True, gains=None, fire=None):
+    def control_test_log(self, tend, robots=(0,), use_mpc=True, gains=None, fire=None, impulses=None):
         """The log of controlTest (template/uprightmpc2.py:113,150-159) for the selected robots, in the reference's
         layout -- a dict {'t' [Nt], 'y' [Nt, 12] = (p, Rb[:, 2], dq), 'u' [Nt, 3], 'pdes' [Nt, 3], 'accdes' [Nt, 6]}
         per robot that viewControlTestLog / logMetric (:14-84, :161-175) take as is -- plus 'metric'. The loop runs
@@ -428,8 +492,20 @@ class BatchUprightMPC:
         fire: None = the fixed schedule (an MPC step every nsub substeps, the first at substep 0), or the substep
         indices at which the MPC fires -- the reference fires when `tt[ti] - thlPrev > hlInterval` (:136), which in
         floating point gives gaps of 25 / 26 substeps starting at substep 26; before the first fire the command is
-        zero (:118) and between fires it is held. Returns {robot: log}."""
+        zero (:118) and between fires it is held.
+        impulses: {substep: [6] or [6, B]} -- (dv_world, domega_body) added to the state AHEAD of that substep's fire and
+        plant, where the reference kicks (`dq[1] += 2` at the first substep past tpert, :130-133, is {ti: (0, 2, 0, 0, 0, 0)}).
+        This loop applies them itself; a table of set_impulses is for rollout() and must not be set on the handle here.
+        Returns {robot: log}."""
         nsub, dts = int(self.prm.nsub), float(self.prm.dtsim)
+        if getattr(self, "_imptab", None) is not None:
+            raise RuntimeError("control_test_log applies its own `impulses`; switch the table off first (set_impulses(None))")
+        kicks = {}
+        for k, vec in (impulses or {}).items():
+            vec = torch.as_tensor(np.asarray(vec, np.float64)).to(self.dtype).to(self.device)
+            if vec.shape not in ((6,), (6, self.B)):
+                raise ValueError("an impulse is [6] or [6, %d], got %r" % (self.B, tuple(vec.shape)))
+            kicks[int(k)] = vec[:, None] if vec.dim() == 1 else vec
         Nt = int(np.ceil(tend / dts - 1e-9))
         idx = torch.as_tensor(list(robots), device=self.device)
         rec = {k: [] for k in ("y", "u", "pdes", "accdes", "R")}
@@ -441,6 +517,8 @@ class BatchUprightMPC:
         for ti in range(Nt):
             t = t_start + ti * dts
             fire = (ti % nsub == 0) if fire_at is None else (ti in fire_at)
+            if ti in kicks:
+                self.state[12:18] += kicks[ti]
             if use_mpc and fire:
                 self._check(self.L.umpcBatchSetTask(self.h, self._task_id(), self._task_params(), t))
                 self.update()

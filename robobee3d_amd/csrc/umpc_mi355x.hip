@@ -70,6 +70,17 @@ __global__ __launch_bounds__(kBlock) void umpc_rollout_kernel(umpc::StepIO<T> a,
   for (int k = 0; k < K; ++k) umpc::closed_loop_step<T, kAsm || ASM64, LDSF, QUAD>(a, b, ldsaddr, ldsw, k, actualT0);
 }
 
+// Velocity impulses for the step-kernel forms that cannot add them in the kernel (umpcBatchSetImpulses; launch_steps issues
+// their steps one per launch): dq (rows 12..17 of the state) += one slice [6][B], one lane per robot, the same IEEE add.
+template <typename T>
+__global__ __launch_bounds__(256) void umpc_impulse_kernel(T *state, const T *slice, int B_) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B_) return;
+  const size_t B = (size_t)B_;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) state[(size_t)(12 + i) * B + b] += slice[(size_t)i * B + b];
+}
+
 // The all-assembly fp32 fast path (asmstep.py -> umpc_step_asm.h): the whole K-step loop of one wavefront is ONE
 // generated instruction stream; C++ only hands over the lane's offsets and the parameter block (kernarg).
 __global__ __launch_bounds__(kBlock) void umpc_rollout_asm_kernel(const umpcasm::StepArgs prm, int B, int skew_ticks,
@@ -268,7 +279,7 @@ __device__ __forceinline__ void reactive_controller(const T (&p)[3], const T (&R
 template <typename T>
 __global__ __launch_bounds__(kBlock) void umpc_reactive_kernel(DevParams<T> prm, int B_, int nsteps, int every, T t0,
                                                               T *state, const T *ref, const T *gains, const T *IbA,
-                                                              const T *gainA, T *out, T *stats) {
+                                                              const T *gainA, T *out, T *stats, const T *imp, int nsub) {
   const int b = blockIdx.x * kBlock + threadIdx.x;
   if (b >= B_) return;
   const size_t B = (size_t)B_;
@@ -305,6 +316,12 @@ __global__ __launch_bounds__(kBlock) void umpc_reactive_kernel(DevParams<T> prm,
     umpc::plant_step(p, R, dq, u, prm.dtsim, Ib, Ibinv, gain, prm.plant_mode);
     s_err += p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
     s_eff += u[1] * u[1] + u[2] * u[2];
+    // velocity impulses (umpcBatchSetImpulses): slice j of `imp` after substep (j + 1) * nsub - 1, where the rollout adds it
+    if (imp && (ti + 1) % nsub == 0) {
+      const T *const imp_j = imp + (size_t)((ti + 1) / nsub - 1) * 6 * B;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) dq[i] += imp_j[(size_t)i * B + b];
+    }
   }
 #pragma unroll
   for (int i = 0; i < 3; ++i) state[(size_t)i * B + b] = p[i];
@@ -428,6 +445,9 @@ struct umpc_batch {
   void *hist_info = nullptr;      // [steps][2][B]
   long long hist_steps = 0;       // ... steps the tables hold
   long long hist_cursor = 0;      // ... step the next rollout records first (advanced by every rollout with nsub > 0)
+  const void *imptab = nullptr;   // velocity impulses [steps][6][B] (umpcBatchSetImpulses), kept by pointer; null = off
+  long long imptab_steps = 0;     // ... slices it holds
+  long long imp_cursor = 0;       // ... slice the next closed-loop step adds (advanced by every rollout with nsub > 0)
   bool hist_on() const { return hist_state || hist_out || hist_status || hist_info; }
 };
 
@@ -480,6 +500,12 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
   a.B = h->B;
   a.state = (T *)state; a.ctrl = (T *)ctrl; a.ref = (const T *)ref; a.ref_step = (unsigned)ref_step;
   a.state_step = (unsigned)hs.state; a.out_step = (unsigned)hs.out; a.status_step = (unsigned)hs.status; a.info_step = (unsigned)hs.info;
+  // velocity impulses: step k of this launch adds slice cursor + k of the table after its last plant substep
+  const size_t imp_step = (size_t)6 * (size_t)h->B;
+  const bool imp_on = h->imptab && nsub > 0 && K >= 1;
+  a.imp = imp_on ? (const T *)h->imptab + (size_t)h->imp_cursor * imp_step : nullptr;
+  a.imp_step = imp_on ? (unsigned)imp_step : 0u;
+  if (imp_on) h->imp_cursor += K;
   a.prm.task = h->task;
   for (int i = 0; i < 4; ++i) a.prm.task_p[i] = (T)h->task_p[i];
   a.weights = (const T *)h->weights; a.t0 = (T)h->t_ms;
@@ -502,6 +528,7 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
       p.refstep = (int32_t)(ref_step * 4);        // bytes per step (9 rows x B x 4 < 2^31: `fits` bounds 127 rows)
       pa.h.statestep = (int32_t)(hs.state * 4); pa.h.outstep = (int32_t)(hs.out * 4);      // (18 rows at the most)
       pa.h.statusstep = (int32_t)(hs.status * 4); pa.h.infostep = (int32_t)(hs.info * 4);
+      pa.i.imp = a.imp; pa.i.impstep = (int32_t)(a.imp_step * 4); pa.i.pad_ = 0;           // (6 rows)
       // SURVEY 8(f) options of the same stream: task generator (a table of K entries written by a K-thread kernel ahead
       // of the launch, same stream), per-robot weights, the fused WL step
       if (h->task != 0) {
@@ -559,7 +586,10 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
         // stride, even a bare `state + state_step` for the store, its scratch frame passes the recorded 600 B --
         // so step k runs in place on state slice k + 1, which a device copy fills from slice k first. Same computation:
         // the fire time is the in-kernel expression, actualT0 goes to the first step only.
-        const bool split = hs.state || hs.out || hs.status || hs.info;
+        // Velocity impulses in this form: the same K launches (with or without a history), and umpc_impulse_kernel adds slice k
+        // to the state step k has just written -- with a state history that is slice k + 1, ahead of the copy that hands it
+        // to step k + 1.
+        const bool split = hs.state || hs.out || hs.status || hs.info || a.imp;
         for (int k = 0; k < (split ? K : 1); ++k) {
           umpc::StepIO<T> ak = a;
           if (split) {
@@ -573,13 +603,17 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
             if (a.status) ak.status = a.status + (size_t)k * hs.status;
             if (a.info) ak.info = a.info + (size_t)k * hs.info;
             ak.t0 = a.t0 + T(k) * (T(nsub) * a.prm.dtsim);
-            ak.ref_step = ak.state_step = ak.out_step = ak.status_step = ak.info_step = 0;
+            ak.ref_step = ak.state_step = ak.out_step = ak.status_step = ak.info_step = ak.imp_step = 0;
+            ak.imp = nullptr;
           }
           hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true, true>), dim3((h->B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
                              (hipStream_t)stream, ak, split ? 1 : K, k == 0 ? (const T *)actualT0 : nullptr, 0);
+          if (split && a.imp)
+            hipLaunchKernelGGL(umpc_impulse_kernel<T>, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, ak.state,
+                               a.imp + (size_t)k * imp_step, h->B);
           if (split) {      // (a failed step stops the sequence; launch_rollout puts the cursors and the clock back)
             const hipError_t el = hipGetLastError();
-            if (el != hipSuccess) return fail(el, "umpcBatchRollout: history");
+            if (el != hipSuccess) return fail(el, "umpcBatchRollout: history / impulses");
           }
         }
         h->last_kernel = "umpc_rollout_kernel<double, LDSF, ASM64, QUAD>";
@@ -622,9 +656,21 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
             " + K " + std::to_string(K) + " > steps " + std::to_string(h->hist_steps) + ")";
     return -1;
   }
+  if (h->imptab && nsub > 0 && K >= 1 && h->imp_cursor + (long long)K > h->imptab_steps) {
+    g_err = "umpcBatchRollout: the impulse table ends before the launch does (cursor " + std::to_string(h->imp_cursor) +
+            " + K " + std::to_string(K) + " > steps " + std::to_string(h->imptab_steps) + ")";
+    return -1;
+  }
   if (!state || !ctrl || (!ref && !h->reftab) || !out) { g_err = "umpcBatchRollout: null array"; return -1; }
   HistStep hs;
-  if (!hist) return launch_steps<T>(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info, hs, stream);
+  if (!hist) {
+    // (a HIP error leaves the cursors and the clock where they were, as with a history)
+    const long long ref_cursor0 = h->ref_cursor, imp_cursor0 = h->imp_cursor;
+    const double t_ms0 = h->t_ms;
+    const int rc = launch_steps<T>(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info, hs, stream);
+    if (rc) { h->ref_cursor = ref_cursor0; h->imp_cursor = imp_cursor0; h->t_ms = t_ms0; }
+    return rc;
+  }
   const size_t B = (size_t)h->B, c = (size_t)h->hist_cursor;
   const hipStream_t s = (hipStream_t)stream;
   T *st = (T *)state, *o = (T *)out, *inf = (T *)info;
@@ -641,7 +687,7 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
   if (h->hist_info) { hs.info = 2 * B; inf = (T *)h->hist_info + c * hs.info; }
   // a failure from here on (a HIP error of a copy or a launch) leaves the cursors and the clock where they were: the
   // tables and the arguments may hold part of the launch, the handle never claims steps it has not recorded
-  const long long ref_cursor0 = h->ref_cursor, hist_cursor0 = h->hist_cursor;
+  const long long ref_cursor0 = h->ref_cursor, hist_cursor0 = h->hist_cursor, imp_cursor0 = h->imp_cursor;
   const double t_ms0 = h->t_ms;
   int rc = launch_steps<T>(h, K, nsub, st, ctrl, ref, actualT0, Ib, gain, o, stats, sw, inf, hs, stream);
   if (!rc) {
@@ -655,7 +701,7 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *c
       e = hipMemcpyAsync(info, inf + last * hs.info, hs.info * sizeof(T), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) rc = fail(e, "umpcBatchRollout: history");
   }
-  if (rc) { h->ref_cursor = ref_cursor0; h->hist_cursor = hist_cursor0; h->t_ms = t_ms0; return rc; }
+  if (rc) { h->ref_cursor = ref_cursor0; h->hist_cursor = hist_cursor0; h->imp_cursor = imp_cursor0; h->t_ms = t_ms0; return rc; }
   h->hist_cursor = hist_cursor0 + K;
   return 0;
 }
@@ -669,12 +715,17 @@ static int launch_reactive(umpc_batch_t *h, int nsteps, int every, void *state, 
   prm.task = h->task;
   for (int i = 0; i < 4; ++i) prm.task_p[i] = (T)h->task_p[i];
   const int grid = (h->B + kBlock - 1) / kBlock;
+  // velocity impulses: slice cursor + j after substep (j + 1) * nsub - 1 (umpcBatchReactive has made the range checks)
+  const int nsub = h->prm.nsub;
+  const T *imp = h->imptab ? (const T *)h->imptab + (size_t)h->imp_cursor * 6 * (size_t)h->B : nullptr;
   hipLaunchKernelGGL(umpc_reactive_kernel<T>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, prm, h->B, nsteps, every,
                      (T)h->t_ms, (T *)state, (const T *)ref, (const T *)gains, (const T *)Ib, (const T *)gain, (T *)out,
-                     (T *)stats);
-  h->t_ms += (double)nsteps * h->prm.dtsim;
+                     (T *)stats, imp, nsub > 0 ? nsub : 1);
   hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchReactive");
+  if (e != hipSuccess) return fail(e, "umpcBatchReactive");      // (the clock and the cursor stay where they were)
+  h->t_ms += (double)nsteps * h->prm.dtsim;
+  if (imp) h->imp_cursor += nsteps / nsub;
+  return 0;
 }
 
 template <typename T>
@@ -800,6 +851,23 @@ int umpcBatchSetHistory(umpc_batch_t *h, void *state_hist, void *out_hist, int32
 }
 long long umpcBatchHistoryCursor(const umpc_batch_t *h) { return h ? h->hist_cursor : 0; }
 
+int umpcBatchSetImpulses(umpc_batch_t *h, const void *tab, long long steps, long long cursor0) {
+  if (!h) { g_err = "umpcBatchSetImpulses: bad argument"; return -1; }
+  if (!tab) {
+    h->imptab = nullptr; h->imptab_steps = 0; h->imp_cursor = 0;
+    return 0;
+  }
+  if (steps < 1 || cursor0 < 0 || cursor0 > steps) { g_err = "umpcBatchSetImpulses: bad argument (steps >= 1, 0 <= cursor0 <= steps)"; return -1; }
+  if (h->prm.nsub == 0) {
+    g_err = "umpcBatchSetImpulses: the handle has no plant (nsub = 0): its rollouts never write the state, there is nothing to push";
+    return -1;
+  }
+  if ((size_t)6 * (size_t)h->B > (size_t)0x7fffffff) { g_err = "umpcBatchSetImpulses: batch too large (a slice is a 32-bit stride)"; return -1; }
+  h->imptab = tab; h->imptab_steps = steps; h->imp_cursor = cursor0;
+  return 0;
+}
+long long umpcBatchImpulseCursor(const umpc_batch_t *h) { return h ? h->imp_cursor : 0; }
+
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
                        const void *ref, void *tab, void *stream) {
   if (!h || steps < 1 || !ref || !tab) { g_err = "umpcBatchTaskTable: bad argument"; return -1; }
@@ -880,6 +948,18 @@ int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const
                       const void *Ib, const void *gain, void *out, void *stats, void *stream) {
   if (!h || nsteps < 0 || every < 1 || !state || !ref) { g_err = "umpcBatchReactive: bad argument"; return -1; }
   if (h->reftab) { g_err = "umpcBatchReactive: a reference trajectory is set (it has one slice per MPC step, not per substep)"; return -1; }
+  if (h->imptab) {      // (set only on handles with nsub >= 1)
+    const int nsub = h->prm.nsub;
+    if (nsteps % nsub != 0) {
+      g_err = "umpcBatchReactive: impulses are set (one slice per nsub = " + std::to_string(nsub) + " substeps): nsteps must be a multiple of nsub";
+      return -1;
+    }
+    if (h->imp_cursor + (long long)(nsteps / nsub) > h->imptab_steps) {
+      g_err = "umpcBatchReactive: the impulse table ends before the launch does (cursor " + std::to_string(h->imp_cursor) + " + " +
+              std::to_string(nsteps / nsub) + " > steps " + std::to_string(h->imptab_steps) + ")";
+      return -1;
+    }
+  }
   return h->dtype == UMPC_F32 ? launch_reactive<float>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream)
                               : launch_reactive<double>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream);
 }
@@ -1169,6 +1249,7 @@ int umpcUpdate(UprightMPC_t *up, float uquad[3], float accdes[6], const float p0
     p = make_step_params(s.h, 1, 0, d + O_STATE, s.ctrl, d + O_REF, d + O_AT0, nullptr, nullptr, d + O_OUT, nullptr,
                          (int32_t *)(d + O_STATUS), d + O_INFO);
     pa.h = umpcasm::StepHist{0, 0, 0, 0};
+    pa.i = umpcasm::StepImp{nullptr, 0, 0};                 // (... and takes no impulses)
     p.done = d + O_DONE0; p.seq = (int)seq;
     // UMPC_DROPIN_TWO_STREAMS=1: round 4's form (step kernel + debug-field kernel on two streams, two completion words), A/B
     static const bool two_streams = getenv("UMPC_DROPIN_TWO_STREAMS") != nullptr;

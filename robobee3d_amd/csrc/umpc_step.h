@@ -468,6 +468,10 @@ struct StepIO {
   // state_step; its out / status / info stores go to slice k of their tables (elements: 18 B, 9 B, B, 2 B; all 0 = every
   // step overwrites the same arrays). 32 bits and last, for the same reason.
   unsigned state_step, out_step, status_step, info_step;
+  // Velocity impulses [steps][6][B] (umpcBatchSetImpulses): `imp` is slice `cursor` (null = none), and step k of the launch
+  // adds imp + k * imp_step (elements: 6 * B) to dq after its last plant substep, ahead of its state store. Last again.
+  unsigned imp_step;
+  const T *imp;
 };
 
 // One closed-loop step of robot b: controller step (= umpcUpdate) + nsub plant substeps.
@@ -1090,6 +1094,17 @@ __device__ __forceinline__ void closed_loop_step(const StepIO<T> &a, const int b
       plant_step(p0, R0, dq0, uc, prm.dtsim, Ib, Ibinv, gain, prm.plant_mode);
       s_err += p0[0] * p0[0] + p0[1] * p0[1] + p0[2] * p0[2];
       s_eff += uc[1] * uc[1] + uc[2] * uc[2];
+    }
+    // velocity impulse of this step (umpcBatchSetImpulses): one IEEE add per component, between the last substep and the
+    // store, so that the stored state, the next step's controller and the history's slice k + 1 all see it. The fp64 QUAD
+    // form takes no member more inside its recorded frame (see UMPC_STATE_IN): there the host adds the slice between its
+    // single-step launches (umpc_impulse_kernel).
+    if constexpr (!QUAD) {
+      if (a.imp) {
+        const T *const imp_k = a.imp + (size_t)step * a.imp_step;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) dq0[i] += GLD(imp_k, i);
+      }
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) GLD(UMPC_STATE_OUT, i) = p0[i];

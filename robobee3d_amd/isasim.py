@@ -510,6 +510,7 @@ SALU = {
     "s_cmp_lt_i32": lambda mc, t: setattr(mc, "scc", int(_signed(mc.s32(t[1])) < _signed(mc.s32(t[2])))),
     "s_cmp_gt_i32": lambda mc, t: setattr(mc, "scc", int(_signed(mc.s32(t[1])) > _signed(mc.s32(t[2])))),
     "s_cmp_lt_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) < mc.s32(t[2]))),
+    "s_cmp_gt_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) > mc.s32(t[2]))),
     "s_cselect_b32": lambda mc, t: _sdst(mc, t, mc.s32(t[2]) if mc.scc else mc.s32(t[3])),
     "s_cmp_lg_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) != mc.s32(t[2]))),
     "s_cmp_eq_u32": lambda mc, t: setattr(mc, "scc", int(mc.s32(t[1]) == mc.s32(t[2]))),
@@ -520,6 +521,7 @@ SALU = {
     "s_and_saveexec_b64": _s_and_saveexec,
     "s_branch": _cbranch(lambda mc: True),
     "s_cbranch_scc1": _cbranch(lambda mc: mc.scc),
+    "s_cbranch_scc0": _cbranch(lambda mc: not mc.scc),
     "s_cbranch_vccz": _cbranch(lambda mc: (mc.S[VCC] | mc.S[VCC + 1]) == 0),
     "s_cbranch_vccnz": _cbranch(lambda mc: (mc.S[VCC] | mc.S[VCC + 1]) != 0),
     "s_cbranch_execz": _cbranch(lambda mc: not mc.exec.any()),

@@ -72,6 +72,13 @@ def table_block(tab, lo, hi):
     return tab[..., lo:hi].contiguous()
 
 
+def impulse_block(tab, lo, hi):
+    """The block [lo, hi) of the robots of an impulse table [steps, 6, B] (BatchUprightMPC.set_impulses), contiguous -- a column
+    slice like table_block: a block of a job kicked with these columns equals the same columns of the undivided run bit for
+    bit."""
+    return table_block(tab, lo, hi)
+
+
 def history_block(hist, lo, hi):
     """The block [lo, hi) of the robots of a step history (BatchUprightMPC.history(): a dict of tables whose last axis is the
     robot index, None for a record that is off), table by table as table_block: the history of a block of a job equals these
