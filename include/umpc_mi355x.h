@@ -292,6 +292,66 @@ long long umpcBatchHistoryCursor(const umpc_batch_t *h);
 int umpcBatchSetImpulses(umpc_batch_t *h, const void *tab, long long steps, long long cursor0);
 long long umpcBatchImpulseCursor(const umpc_batch_t *h);
 
+/* Scoring: from the tables of a rollout (step history, reference trajectory) to one small score per robot and one row per
+ * group of robots, on the device -- the last stage of the reference's gainTuningSims, which ends in one cost and one effort
+ * per grid cell (costs[i,j], efforts[i,j] = logMetric(log), template/uprightmpc2.py:272-303). UMPC_STAT_ROWS measures
+ * sum |p|^2, the distance from the ORIGIN (the reference's logMetric, uprightmpc2.py:161-175); on a reference trajectory
+ * that is the path, not the tracking error, and the tables are too large to be scored with array expressions that
+ * materialise temporaries of their size.
+ * umpcBatchScore is a pure function of its arguments: it reads none of the handle's cursors and takes only B, the dtype and
+ * taulim from the handle. All tables are device arrays in the handle's dtype, robot index fastest, in the layouts of
+ * umpcBatchSetHistory and umpcBatchSetRefTrajectory:
+ *   state_hist  [..][18][B]        must be given
+ *   out_hist    [..][9][B]         or NULL: row 6 is left alone and `out` does not enter the finiteness test
+ *   status_hist [..][B] int32      or NULL: row 8 is left alone
+ *   ref_tab     [..][9][B]         a reference per step, or
+ *   ref         [9][B]             one constant reference; exactly ONE of the two is given
+ * The call scores steps c = first .. first + count - 1. after = 0: the state of step c is state slice c, the state the
+ * step fired on (when its reference slice was evaluated); after = 1: slice c + 1, the state the step produced -- the
+ * reference log's convention (log['y'][ti] after the plant, log['pdes'][ti] before it). The reference slice of step c is
+ * ref_first + (c - first), its out / status slice is c, and k = step0 + (c - first) is the caller's absolute step number.
+ * The caller keeps every slice inside its table.
+ * score [UMPC_SCORE_ROWS][B] is in/out and accumulates over calls (a long chunked run is scored chunk by chunk, in any
+ * order); umpcBatchScoreInit writes the identity (rows 9 and 10 = -1, all others 0). Per robot, with
+ * e_p = |p - pdes|^2 (state rows 0..2, reference rows 0..2), e_s = |s - sdes|^2 (s = state rows 9..11, reference rows 6..8),
+ * tau = out rows 1 and 2 clipped at +-taulim, as the plant saw them:
+ *   0  steps scored                 1  sum e_p           2  max e_p        3  e_p of the last scored step of the latest call
+ *   4  sum e_s                      5  max e_s           6  sum (tau1^2 + tau2^2)
+ *   7  sum |p|^2   (rows 7 / 0 and 6 / 0 are the reference's logMetric pair at step granularity)
+ *   8  steps with status != 1 (OSQP solved)
+ *   9  first k with e_p > tol_p^2, -1 if none ("left the path")
+ *  10  last k with e_p > tol_p^2, -1 if none (settled from k + 1 on)
+ *  11  steps skipped
+ * A step is skipped when any of the up to 14 values it reads is not finite; it is counted in row 11 and in no other row, so
+ * a robot that went to NaN stays visible and does not poison its group. Counts and step numbers are scalars of the dtype:
+ * a call whose step0 + count passes 2^24 in fp32 is refused. Row 0 lives on the device and the call does not synchronise, so
+ * the library cannot see it: it stays exact as long as step0 counts the steps of the run (row 0 <= step0 + count then, as in
+ * every use here); a caller who accumulates with another step0 keeps row 0 + count below 2^24 in fp32 themselves. Rows 0, 2, 3, 5, 8..11 do not depend on how a step range is cut into calls; the sum rows
+ * 1, 4, 6, 7 are sums of non-negative terms whose order depends on the cut (relative difference <= (steps + 8) u). Nothing
+ * crosses robots: a block of robots scored from column-sliced tables equals the same columns of the undivided batch bit for
+ * bit, and so do two runs.
+ * One pass: 15 words (60 B in fp32) read per robot-step, each once, 12 words written per robot; no temporaries, no atomics.
+ * Refused (-1, umpcLastError) BEFORE any launch: count, first, ref_first or step0 < 0 (a negative step number would collide with
+ * the -1 of rows 9 and 10); count > 2^31 - 17; tol_p < 0 or not
+ * finite; score or state_hist NULL; both or neither of ref_tab and ref. count == 0 is a successful no-op.
+ * Asynchronous on `stream`.
+ * umpcBatchScoreGroups: group [B] int32 names each robot's group (a grid cell); ids outside [0, G) are ignored. gstat
+ * [G][UMPC_GSCORE_ROWS] is DOUBLE whatever the handle's dtype and is overwritten. It holds raw sums, so the tables of the
+ * blocks of a sharded job combine by adding (row 3: by max):
+ *   0  robots in the group          1  of these, robots with score row 0 > 0; only they enter rows 2..5
+ *   2  sum row 1 / row 0            3  max row 2         4  sum row 6 / row 0     5  sum row 7 / row 0
+ *   6  robots with row 9 >= 0       7  sum row 8
+ * (rows 2 / 1, 5 / 1 and 4 / 1 are a cell's mean tracking cost, logMetric cost and effort). The result is the same bit for
+ * bit from run to run: a fixed reduction order, no floating-point atomics. One workgroup per group scans `group`: G x B id
+ * reads. */
+#define UMPC_SCORE_ROWS 12
+#define UMPC_GSCORE_ROWS 8
+int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream);
+int umpcBatchScore(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                   const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                   long long step0, double tol_p, int after, void *score, void *stream);
+int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *group, int G, double *gstat, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

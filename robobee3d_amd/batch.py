@@ -375,6 +375,65 @@ class BatchUprightMPC:
         """impulse_table() for this handle: [steps, 6, B] in its dtype, on its device."""
         return impulse_table(steps, self.B, events, self.dtype, self.device)
 
+    def score(self, first=0, count=None, tol=10.0, after=False, score=None, step0=None):
+        """The recorded steps first .. first + count - 1 of the step history as a per-robot score [12, B] (umpcBatchScore; rows:
+        robobee3d_amd/score.py -- steps, sum / max / last of e_p = |p - pdes|^2, sum / max of e_s = |s - sdes|^2, sum of
+        the clipped moments squared, sum |p|^2, steps not solved, first / last step with e_p > tol^2, steps skipped as not
+        finite), in ONE pass over the tables on the device: no temporary, nothing of the tables' size allocated.
+        count None = up to the history cursor. The reference of step c is slice `history start + c` of the table of
+        set_reference_trajectory, else the constant `self.ref`; a handle task has no table to read: build one with
+        task_table and set it with set_reference_trajectory before the run. after=False scores the state each step fired
+        on, after=True the state it produced (the convention of the reference's log). step0 (default `first`) is the step
+        number rows 9 and 10 report for step `first`. Passing a score back in accumulates: a chunked run is scored chunk by
+        chunk (rewind_history() in between, step0 = the steps already run). The out and status records enter when they are
+        on; without them rows 6 / 8 stay as they are."""
+        hist = getattr(self, "_hist", None)
+        if hist is None or hist["state"] is None:
+            raise RuntimeError("score needs a step history with the state record (record_history)")
+        cur = self.history_cursor
+        first = int(first)
+        count = cur - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > cur:
+            raise ValueError("score: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
+        reftab = getattr(self, "_reftab", None)
+        ref_first = 0
+        if reftab is not None:
+            ref_first = self._hist_ref0 + first
+            if ref_first < 0 or ref_first + count > int(reftab.shape[0]):
+                raise ValueError("score: the reference trajectory does not cover the steps asked for")
+        elif self._task_id() != 0:
+            raise RuntimeError("score: the handle follows a task generator, there is no reference table to read; build the "
+                               "table with task_table() and set it with set_reference_trajectory() before the run")
+        with torch.cuda.device(self.device):
+            if score is None:
+                score = torch.empty((_lib.SCORE_ROWS, self.B), dtype=self.dtype, device=self.device)
+                self._check(self.L.umpcBatchScoreInit(self.h, _ptr(score), self._stream()))
+            elif (tuple(score.shape) != (_lib.SCORE_ROWS, self.B) or score.dtype != self.dtype or score.device != self.state.device
+                  or not score.is_contiguous()):
+                raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
+            self._check(self.L.umpcBatchScore(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
+                                              _ptr(reftab), None if reftab is not None else _ptr(self.ref), first, count,
+                                              ref_first, first if step0 is None else int(step0), float(tol), int(bool(after)),
+                                              _ptr(score), self._stream()))
+        return score
+
+    def score_groups(self, score, group, G):
+        """[G, 8] float64 table of the scores of the robots of each group (umpcBatchScoreGroups; rows: robobee3d_amd/score.py):
+        group [B] int32 names each robot's group -- the grid cell of a gain sweep, ids outside [0, G) are ignored. Raw sums
+        (robots, robots scored, sum of the per-robot means of e_p / tau^2 / |p|^2, max e_p, robots that left the path, steps
+        not solved), so the tables of the blocks of a sharded job add up (score.combine_groups). Bit-identical from run to
+        run."""
+        group = torch.as_tensor(group).to(torch.int32).to(self.device).contiguous()
+        if tuple(group.shape) != (self.B,):
+            raise ValueError("group must be [%d]" % self.B)
+        if (tuple(score.shape) != (_lib.SCORE_ROWS, self.B) or score.dtype != self.dtype or score.device != self.state.device
+                or not score.is_contiguous()):
+            raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
+        gstat = torch.empty((int(G), _lib.GSCORE_ROWS), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchScoreGroups(self.h, _ptr(score), _ptr(group), int(G), _ptr(gstat), self._stream()))
+        return gstat
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

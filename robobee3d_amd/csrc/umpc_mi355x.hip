@@ -19,6 +19,7 @@
 #include UMPC_STEP_ASM_HEADER
 #include "umpc_step_asm_quad.h"   // the same stream with one robot per lane QUAD (asmquad.py): the latency-bound shapes
 #include "umpc_models.h"
+#include "umpc_score.h"    // scoring of recorded rollouts (umpcBatchScore / umpcBatchScoreGroups): stand-alone kernels
 #include "umpc_err.h"
 #include "umpc_n3_general.h"   // the N = 3 QP as data for the general-structure solver (compat bounds-reject path only)
 
@@ -745,6 +746,45 @@ static int launch_task_table(umpc_batch_t *h, long long steps, double t_ms, cons
   return e == hipSuccess ? 0 : fail(e, "umpcBatchTaskTable");
 }
 
+// UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
+static bool score_nt() {
+  static const bool v = [] { const char *e_ = getenv("UMPC_SCORE_NT"); return e_ && atoi(e_) != 0; }();
+  return v;
+}
+
+// umpcBatchScore has checked the arguments; the table pointers are moved to the first slice of the call here
+template <typename T>
+static int launch_score(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                        const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                        long long step0, double tol_p, int after, void *score, void *stream) {
+  const size_t B = (size_t)h->B;
+  umpc::ScoreArgs<T> a;
+  a.state = (const T *)state_hist + (size_t)(first + (after ? 1 : 0)) * 18 * B;
+  a.out = out_hist ? (const T *)out_hist + (size_t)first * 9 * B : nullptr;
+  a.status = status_hist ? status_hist + (size_t)first * B : nullptr;
+  a.reftab = ref_tab ? (const T *)ref_tab + (size_t)ref_first * 9 * B : nullptr;
+  a.ref = (const T *)ref;
+  a.score = (T *)score;
+  a.B = h->B; a.count = (int)count; a.step0 = step0;
+  a.tol2 = (T)(tol_p * tol_p); a.taulim = (T)h->prm.taulim;
+  const dim3 grid((unsigned)((h->B + 63) / 64)), block(64, umpc::kScoreSlices);
+  // which tables there are is decided HERE, once: each combination is a kernel of its own whose loop has no branch
+  const int form = (score_nt() ? 8 : 0) | (a.reftab ? 4 : 0) | (a.out ? 2 : 0) | (a.status ? 1 : 0);
+#define UMPC_SCORE_FORM(f)                                                                                              \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_score_kernel<T, ((f) & 8) != 0, ((f) & 4) != 0, ((f) & 2) != 0, ((f) & 1) != 0>), grid, \
+                       block, 0, (hipStream_t)stream, a);                                                               \
+    break;
+  switch (form) {
+    UMPC_SCORE_FORM(0) UMPC_SCORE_FORM(1) UMPC_SCORE_FORM(2) UMPC_SCORE_FORM(3) UMPC_SCORE_FORM(4) UMPC_SCORE_FORM(5)
+    UMPC_SCORE_FORM(6) UMPC_SCORE_FORM(7) UMPC_SCORE_FORM(8) UMPC_SCORE_FORM(9) UMPC_SCORE_FORM(10) UMPC_SCORE_FORM(11)
+    UMPC_SCORE_FORM(12) UMPC_SCORE_FORM(13) UMPC_SCORE_FORM(14) UMPC_SCORE_FORM(15)
+  }
+#undef UMPC_SCORE_FORM
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, "umpcBatchScore");
+}
+
 extern "C" {
 
 const char *umpcLastError(void) { return g_err.c_str(); }
@@ -867,6 +907,47 @@ int umpcBatchSetImpulses(umpc_batch_t *h, const void *tab, long long steps, long
   return 0;
 }
 long long umpcBatchImpulseCursor(const umpc_batch_t *h) { return h ? h->imp_cursor : 0; }
+
+int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
+  if (!h || !score) { g_err = "umpcBatchScoreInit: bad argument"; return -1; }
+  const dim3 grid((unsigned)((h->B + 255) / 256));
+  if (h->dtype == UMPC_F32) hipLaunchKernelGGL(umpc::umpc_score_init_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (float *)score, h->B);
+  else hipLaunchKernelGGL(umpc::umpc_score_init_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (double *)score, h->B);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, "umpcBatchScoreInit");
+}
+int umpcBatchScore(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                   const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                   long long step0, double tol_p, int after, void *score, void *stream) {
+  if (!h) { g_err = "umpcBatchScore: bad argument (no handle)"; return -1; }
+  if (!score || !state_hist) { g_err = "umpcBatchScore: bad argument (score and state_hist must be given)"; return -1; }
+  if ((ref_tab != nullptr) == (ref != nullptr)) {
+    g_err = "umpcBatchScore: exactly one of ref_tab (a reference per step) and ref (a constant reference) must be given";
+    return -1;
+  }
+  if (count < 0 || first < 0 || ref_first < 0 || step0 < 0) { g_err = "umpcBatchScore: bad argument (count, first, ref_first, step0 >= 0)"; return -1; }
+  if (!(tol_p >= 0) || !(tol_p <= 1.79769313486231570815e308)) { g_err = "umpcBatchScore: bad argument (tol_p must be finite and >= 0)"; return -1; }
+  if (count > 0x7fffffffLL - 2 * umpc::kScoreSlices) { g_err = "umpcBatchScore: count too large for one call (2^31 - 17 steps at the most)"; return -1; }
+  // counts and step numbers are scalars of the dtype: fp32 holds integers exactly up to 2^24. Row 0 never exceeds the
+  // number of steps scored, which is at most step0 + count when step0 counts the steps from the start of the run.
+  if (h->dtype == UMPC_F32 && step0 + count > (1LL << 24)) {
+    g_err = "umpcBatchScore: step0 + count passes 2^24, the largest step number and count an fp32 score holds exactly (score in fp64, or in parts)";
+    return -1;
+  }
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32
+             ? launch_score<float>(h, state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, step0, tol_p, after, score, stream)
+             : launch_score<double>(h, state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, step0, tol_p, after, score, stream);
+}
+int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *group, int G, double *gstat, void *stream) {
+  if (!h || !score || !group || !gstat || G < 1) { g_err = "umpcBatchScoreGroups: bad argument (score, group, gstat and G >= 1 must be given)"; return -1; }
+  if (h->dtype == UMPC_F32)
+    hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<float>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float *)score, group, h->B, gstat);
+  else
+    hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<double>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const double *)score, group, h->B, gstat);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, "umpcBatchScoreGroups");
+}
 
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
                        const void *ref, void *tab, void *stream) {

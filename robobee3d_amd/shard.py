@@ -86,6 +86,14 @@ def history_block(hist, lo, hi):
     return {k: None if v is None else table_block(v, lo, hi) for k, v in hist.items()}
 
 
+def score_block(score, lo, hi):
+    """The block [lo, hi) of the robots of a score [12, B] (BatchUprightMPC.score), contiguous -- a column slice like
+    table_block: the score of a block of a job equals these columns of the undivided job's score bit for bit. Scores gather
+    over ranks like the statistics (gather_stats); the group tables of blocks (BatchUprightMPC.score_groups on each block's
+    own group ids) combine with score.combine_groups."""
+    return table_block(score, lo, hi)
+
+
 def max_over_ranks(value, device="cpu"):
     t = torch.tensor([float(value)], dtype=torch.float64, device=device)
     if dist.is_initialized():
