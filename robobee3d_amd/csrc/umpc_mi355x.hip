@@ -35,6 +35,11 @@ int fail(hipError_t e, const char *what) {
   g_err = std::string(what) + ": " + hipGetErrorString(e);
   return (int)e;
 }
+// after a kernel launch: 0, or the launch error under the entry point's name
+int launch_status(const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(e, what);
+}
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -420,13 +425,32 @@ DevParams<T> make_dev(const umpc_batch_params_t &p) {
 
 }  // namespace
 
+// A table the handle keeps by pointer and walks with a cursor (reference trajectory, step history, impulses): `steps` slices,
+// the next closed-loop step uses slice `cursor`. One rule for all of them: a setter takes 0 <= cursor0 <= steps, and a launch
+// that would pass the end is refused before anything is launched or copied.
+struct CursorTable {
+  long long steps = 0, cursor = 0;
+  static bool valid(const char *setter, long long steps, long long cursor0) {
+    if (steps >= 1 && cursor0 >= 0 && cursor0 <= steps) return true;
+    g_err = std::string(setter) + ": bad argument (steps >= 1, 0 <= cursor0 <= steps)";
+    return false;
+  }
+  // do the n slices of a launch fit? `n_name` is what the message calls n ("K " in a rollout)
+  bool fits(const char *who, const char *table, const char *n_name, long long n) const {
+    if (cursor + n <= steps) return true;
+    g_err = std::string(who) + ": the " + table + " ends before the launch does (cursor " + std::to_string(cursor) + " + " + n_name +
+            std::to_string(n) + " > steps " + std::to_string(steps) + ")";
+    return false;
+  }
+};
+
 struct umpc_batch {
   umpc_batch_params_t prm;
   int B, dtype;
   long long global_B = 0;        // size of the whole (sharded) job, umpcBatchSetGlobalBatch; the lane / quad choice is made from it
   int task = 0;
   double task_p[4] = {0, 0, 0, 0};
-  double t_ms = 0;               // time of the next MPC step (advanced by every rollout)
+  double t_ms = 0;               // time of the next MPC step
   const void *weights = nullptr;  // [8][B] device table or null
   void *ws;  // [WS_ROWS][B] scratch the step parks Ruiz scalings / x_prev / delta_y in
   int step_kernel = 0;            // 0 = automatic, 1 = always the C++ / loop-assembly kernel, 2 / 3 = the all-assembly stream with one lane / one lane quad per robot
@@ -437,33 +461,60 @@ struct umpc_batch {
   float *taskf = nullptr;         // task table of the all-assembly kernel: 8 floats per step of a launch
   int taskf_cap = 0;              // ... steps it holds
   const void *reftab = nullptr;   // reference trajectory [steps][9][B] (umpcBatchSetRefTrajectory), kept by pointer; null = off
-  long long reftab_steps = 0;     // ... slices it holds
-  long long ref_cursor = 0;       // ... slice the next closed-loop step reads (advanced by every rollout with nsub > 0)
+  CursorTable ref_c;              // ... its slices; the cursor is the slice the next closed-loop step reads
   // step history (umpcBatchSetHistory), kept by pointer; each may be null = that record is off
   void *hist_state = nullptr;     // [steps+1][18][B]
   void *hist_out = nullptr;       // [steps][9][B]
   int32_t *hist_status = nullptr; // [steps][B]
   void *hist_info = nullptr;      // [steps][2][B]
-  long long hist_steps = 0;       // ... steps the tables hold
-  long long hist_cursor = 0;      // ... step the next rollout records first (advanced by every rollout with nsub > 0)
+  CursorTable hist_c;             // ... the steps the tables hold; the cursor is the step the next rollout records first
   const void *imptab = nullptr;   // velocity impulses [steps][6][B] (umpcBatchSetImpulses), kept by pointer; null = off
-  long long imptab_steps = 0;     // ... slices it holds
-  long long imp_cursor = 0;       // ... slice the next closed-loop step adds (advanced by every rollout with nsub > 0)
-  bool hist_on() const { return hist_state || hist_out || hist_status || hist_info; }
+  CursorTable imp_c;              // ... its slices; the cursor is the slice the next closed-loop step adds
+  // the history and the impulses belong to closed-loop steps with a plant: only those are recorded, kicked and range-checked,
+  // and only they advance the two cursors (the reference trajectory is read, and checked, by every call)
+  bool hist_on(int K, int nsub) const { return (hist_state || hist_out || hist_status || hist_info) && nsub > 0 && K >= 1; }
+  bool imp_on(int K, int nsub) const { return imptab && nsub > 0 && K >= 1; }
+  // THE place the clock and the cursors advance: callers come here after every launch and copy of their call has returned
+  // hipSuccess, so a refused or failed call leaves the handle where it was
+  void advance(double ms, long long ref_n, long long hist_n, long long imp_n) {
+    t_ms += ms; ref_c.cursor += ref_n; hist_c.cursor += hist_n; imp_c.cursor += imp_n;
+  }
+};
+
+// the caller's arrays of one umpcBatchRollout / umpcBatchUpdate, by name (null = not given)
+struct RolloutArrays {
+  void *state = nullptr, *ctrl = nullptr;
+  const void *ref = nullptr, *actualT0 = nullptr, *Ib = nullptr, *gain = nullptr;
+  void *out = nullptr, *stats = nullptr;
+  int32_t *status = nullptr;
+  void *info = nullptr;
 };
 
 // elements the state / out / status / info pointers advance per closed-loop step of one launch (0 = in place)
 struct HistStep { size_t state = 0, out = 0, status = 0, info = 0; };
 
+// DevParams of a handle, its task included
+template <typename T>
+static DevParams<T> make_dev_task(const umpc_batch_t *h) {
+  DevParams<T> d = make_dev<T>(h->prm);
+  d.task = h->task;
+  for (int i = 0; i < 4; ++i) d.task_p[i] = (T)h->task_p[i];
+  return d;
+}
+
+// after a launch: the kernel's name for umpcBatchKernelName, and the launch error if there is one
+static int launched(umpc_batch_t *h, const char *kernel) {
+  h->last_kernel = kernel;
+  return launch_status("umpcBatchRollout");
+}
+
 // Parameter block of the all-assembly step kernel (umpcasm::StepParams, read by the stream with scalar loads)
-static umpcasm::StepParams make_step_params(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
-                                            const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
-                                            int32_t *status, void *info) {
+static umpcasm::StepParams make_step_params(umpc_batch_t *h, int K, int nsub, const RolloutArrays &io) {
   umpcasm::StepParams p;
-  p.state = state; p.ctrl = ctrl; p.ref = ref; p.out = out; p.stats = stats; p.status = status;
+  p.state = io.state; p.ctrl = io.ctrl; p.ref = io.ref; p.out = io.out; p.stats = io.stats; p.status = io.status;
   // (the kernel's workspace pointer is the row it parks D, E, c in: 32-bit lane offsets stay inside one array)
   p.ws = (char *)h->ws + (size_t)umpcasm::WS_DS * (size_t)h->B * 4;
-  p.info = info; p.Ib = Ib; p.gain = gain; p.aT0 = actualT0;
+  p.info = io.info; p.Ib = io.Ib; p.gain = io.gain; p.aT0 = io.actualT0;
   p.taskf = nullptr; p.weights = h->weights; p.wl = h->wl; p.wlu = h->wlu; p.wlw = h->wlw;
   p.done = nullptr; p.seq = 0; p.refstep = 0;
   p.stride = h->B * 4; p.K = K; p.maxIter = h->prm.maxIter; p.nsub = nsub; p.plant = h->prm.plant_mode;
@@ -483,38 +534,69 @@ static umpcasm::StepParams make_step_params(umpc_batch_t *h, int K, int nsub, vo
   return p;
 }
 
-// the launch itself; launch_rollout (below) has made the range checks of the reference trajectory and the history
+// The fp64 quad form with a step history or impulses: K launches of one step on moved pointers. The kernel cannot move them
+// itself -- with any stride, even a bare `state + state_step` for the store, its scratch frame passes the recorded 600 B
+//  -- so step k runs in place on state slice k + 1, which a device copy fills from slice k first. Same
+// computation: the fire time is the in-kernel expression, actualT0 goes to the first step only.
+// Velocity impulses in this form: the same K launches (with or without a history), and umpc_impulse_kernel adds slice k
+// to the state step k has just written -- with a state history that is slice k + 1, ahead of the copy that hands it
+// to step k + 1.
 template <typename T>
-static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
-                        const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
-                        int32_t *status, void *info, const HistStep &hs, void *stream) {
-  // reference trajectory: step k of this launch reads slice cursor + k of the table (`ref` is not read)
+static int launch_quad64_stepwise(const umpc::StepIO<T> &a, int K, const T *actualT0, const HistStep &hs, hipStream_t stream) {
+  for (int k = 0; k < K; ++k) {
+    umpc::StepIO<T> ak = a;
+    if (hs.state) {
+      ak.state = a.state + ((size_t)k + 1) * hs.state;
+      const hipError_t ec = hipMemcpyAsync(ak.state, a.state + (size_t)k * hs.state, hs.state * sizeof(T),
+                                           hipMemcpyDeviceToDevice, stream);
+      if (ec != hipSuccess) return fail(ec, "umpcBatchRollout: history");
+    }
+    ak.ref = a.ref + (size_t)k * a.ref_step; ak.out = a.out + (size_t)k * hs.out;
+    if (a.status) ak.status = a.status + (size_t)k * hs.status;
+    if (a.info) ak.info = a.info + (size_t)k * hs.info;
+    ak.t0 = a.t0 + T(k) * (T(a.prm.nsub) * a.prm.dtsim);
+    ak.ref_step = ak.state_step = ak.out_step = ak.status_step = ak.info_step = ak.imp_step = 0;
+    ak.imp = nullptr;
+    hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true, true>), dim3((a.B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
+                       stream, ak, 1, k == 0 ? actualT0 : nullptr, 0);
+    if (a.imp)
+      hipLaunchKernelGGL(umpc_impulse_kernel<T>, dim3((a.B + 255) / 256), dim3(256), 0, stream, ak.state,
+                         a.imp + (size_t)k * a.imp_step, a.B);
+    // (a failed step stops the sequence: the cursors and the clock have not moved)
+    const hipError_t el = hipGetLastError();
+    if (el != hipSuccess) return fail(el, "umpcBatchRollout: history / impulses");
+  }
+  return 0;
+}
+
+// The launch itself: the slices of the reference trajectory and of the impulses from the cursors, then the first step-kernel
+// form that applies. launch_rollout (below) has made the range checks and aimed state / out / status / info; nothing here
+// moves a cursor or the clock.
+template <typename T>
+static int launch_steps(umpc_batch_t *h, int K, int nsub, RolloutArrays io, const HistStep &hs, void *stream) {
+  // reference trajectory: step k of this launch reads slice cursor + k of the table (the caller's `ref` is not read)
   size_t ref_step = 0;
   if (h->reftab) {
     ref_step = (size_t)9 * (size_t)h->B;
-    ref = (const T *)h->reftab + (size_t)h->ref_cursor * ref_step;
+    io.ref = (const T *)h->reftab + (size_t)h->ref_c.cursor * ref_step;
   }
-  if (h->reftab && nsub > 0) h->ref_cursor += K;
   umpc::StepIO<T> a;
-  a.prm = make_dev<T>(h->prm);
+  a.prm = make_dev_task<T>(h);
   a.prm.nsub = nsub;
   a.B = h->B;
-  a.state = (T *)state; a.ctrl = (T *)ctrl; a.ref = (const T *)ref; a.ref_step = (unsigned)ref_step;
+  a.state = (T *)io.state; a.ctrl = (T *)io.ctrl; a.ref = (const T *)io.ref; a.ref_step = (unsigned)ref_step;
   a.state_step = (unsigned)hs.state; a.out_step = (unsigned)hs.out; a.status_step = (unsigned)hs.status; a.info_step = (unsigned)hs.info;
   // velocity impulses: step k of this launch adds slice cursor + k of the table after its last plant substep
   const size_t imp_step = (size_t)6 * (size_t)h->B;
-  const bool imp_on = h->imptab && nsub > 0 && K >= 1;
-  a.imp = imp_on ? (const T *)h->imptab + (size_t)h->imp_cursor * imp_step : nullptr;
+  const bool imp_on = h->imp_on(K, nsub);
+  a.imp = imp_on ? (const T *)h->imptab + (size_t)h->imp_c.cursor * imp_step : nullptr;
   a.imp_step = imp_on ? (unsigned)imp_step : 0u;
-  if (imp_on) h->imp_cursor += K;
-  a.prm.task = h->task;
-  for (int i = 0; i < 4; ++i) a.prm.task_p[i] = (T)h->task_p[i];
   a.weights = (const T *)h->weights; a.t0 = (T)h->t_ms;
-  if (nsub > 0) h->t_ms += (double)K * nsub * h->prm.dtsim;
-  a.Ib = (const T *)Ib; a.gain = (const T *)gain; a.ws = (T *)h->ws; a.out = (T *)out; a.stats = (T *)stats;
-  a.status = status; a.info = (T *)info;
+  a.Ib = (const T *)io.Ib; a.gain = (const T *)io.gain; a.ws = (T *)h->ws; a.out = (T *)io.out; a.stats = (T *)io.stats;
+  a.status = io.status; a.info = (T *)io.info;
   a.wl = h->wl; a.wlu = (T *)h->wlu; a.wlw = (T *)h->wlw;
-  const int grid = (h->B + kBlock - 1) / kBlock;
+  const hipStream_t s = (hipStream_t)stream;
+  const int grid = (h->B + kBlock - 1) / kBlock, qgrid = (h->B + kBlock / 4 - 1) / (kBlock / 4);
   if constexpr (sizeof(T) == 4) {
     // all-assembly fast path: fp32, no task generator, batch-constant weights, no WL coupling, >= 1 iteration, row
     // offsets within 31 bits (either plant); UMPC_NO_ASM_STEP=1 forces the C++ / assembly-loop kernel
@@ -525,7 +607,7 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
     if (!no_asm && h->step_kernel != 1 && fits && K >= 1 && h->prm.maxIter >= 1) {
       umpcasm::StepArgs pa;
       umpcasm::StepParams &p = pa.p;
-      p = make_step_params(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info);
+      p = make_step_params(h, K, nsub, io);
       p.refstep = (int32_t)(ref_step * 4);        // bytes per step (9 rows x B x 4 < 2^31: `fits` bounds 127 rows)
       pa.h.statestep = (int32_t)(hs.state * 4); pa.h.outstep = (int32_t)(hs.out * 4);      // (18 rows at the most)
       pa.h.statusstep = (int32_t)(hs.status * 4); pa.h.infostep = (int32_t)(hs.info * 4);
@@ -541,31 +623,23 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
           if (em != hipSuccess) return fail(em, "umpcBatchRollout: task table");
           h->taskf_cap = cap;
         }
-        hipLaunchKernelGGL(umpc_taskf_kernel, dim3((K + 255) / 256), dim3(256), 0, (hipStream_t)stream, a.prm, K, a.t0, h->taskf);
+        hipLaunchKernelGGL(umpc_taskf_kernel, dim3((K + 255) / 256), dim3(256), 0, s, a.prm, K, a.t0, h->taskf);
         p.taskf = h->taskf;
+      }
+      if (h->step_kernel == 3 || (h->step_kernel == 0 && h->global_B <= quad_max_b())) {
+        hipLaunchKernelGGL(umpc_rollout_asm_quad_kernel, dim3(qgrid), dim3(kBlock), 0, s, pa, h->B);
+        return launched(h, "umpc_rollout_asm_quad_kernel");
       }
       // wave-group start skew (see the kernel): UMPC_ASM_SKEW_US / UMPC_ASM_SKEW_GROUPS override the measured default
       static const int skew_us10 = [] { const char *e_ = getenv("UMPC_ASM_SKEW_US"); return e_ ? (int)(atof(e_) * 10) : 0; }();
       static const int skew_groups = [] { const char *e_ = getenv("UMPC_ASM_SKEW_GROUPS"); return e_ ? atoi(e_) : 4; }();
       const int skew_ticks = (h->B >= 32768 && K >= 2) ? skew_us10 * 10 : 0;
-      if (h->step_kernel == 3 || (h->step_kernel == 0 && h->global_B <= quad_max_b())) {
-        hipLaunchKernelGGL(umpc_rollout_asm_quad_kernel, dim3((h->B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
-                           (hipStream_t)stream, pa, h->B);
-        h->last_kernel = "umpc_rollout_asm_quad_kernel";
-        hipError_t eq = hipGetLastError();
-        return eq == hipSuccess ? 0 : fail(eq, "umpcBatchRollout");
-      }
-      hipLaunchKernelGGL(umpc_rollout_asm_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pa, h->B, skew_ticks,
+      hipLaunchKernelGGL(umpc_rollout_asm_kernel, dim3(grid), dim3(kBlock), 0, s, pa, h->B, skew_ticks,
                          skew_groups < 1 ? 1 : skew_groups);
-      h->last_kernel = "umpc_rollout_asm_kernel";
-      hipError_t e = hipGetLastError();
-      return e == hipSuccess ? 0 : fail(e, "umpcBatchRollout");
+      return launched(h, "umpc_rollout_asm_kernel");
     }
   }
-  // stagger wave groups by ~1/4 step when a launch carries many steps: the last group ends 3 x skew later than the
-  // first, so the stagger only pays when that tail is small against the launch (off below 64 steps)
-  const char *env = getenv("UMPC_SKEW_US");
-  const int skew_us = env ? atoi(env) : (K >= 64 && sizeof(T) == 4 && h->B >= 32768 ? 80 : 0);
+  const T *const aT0 = (const T *)io.actualT0;
   if constexpr (sizeof(T) == 8) {
     // fp64 (BASELINE configs[1]: B = 4096 = one wave per CU at most): L and 1/D in LDS, not in scratch
     static const bool no_ldsf = getenv("UMPC_NO_F64_LDS") != nullptr;
@@ -576,134 +650,71 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, void *state, void *ctr
     static const int ldsf_max_grid = [] { const char *e_ = getenv("UMPC_F64_LDS_MAX_GRID"); return e_ ? atoi(e_) : 0x7fffffff; }();
     if (!no_ldsf && grid <= ldsf_max_grid) {
       // ... and the ADMM phase as generated fp64 assembly (needs >= 1 iteration and 31-bit row offsets)
-      const bool fits = (size_t)umpc::WS_ROWS * (size_t)h->B * 8 < ((size_t)1 << 31);
+      const bool asm64 = !no_asm64 && h->step_kernel != 1 && (size_t)umpc::WS_ROWS * (size_t)h->B * 8 < ((size_t)1 << 31);
       // ... with one robot per lane quad when that still is one round of workgroups (256 CUs x 16 robots): BASELINE
       // config 2's 4 096 robots are then 256 waves instead of 64, each iteration ~0.55 of the one-lane loop's time
       // (asmquad64.py). UMPC_QUAD64=0 keeps the lane form, UMPC_QUAD64=<n> moves the switch-over batch size.
       static const int quad64_max_b = [] { const char *e_ = getenv("UMPC_QUAD64"); return e_ ? atoi(e_) : 4096; }();
       const bool want_quad = h->step_kernel == 3 || (h->step_kernel == 0 && h->global_B <= quad64_max_b);
-      if (!no_asm64 && h->step_kernel != 1 && h->prm.maxIter >= 2 && fits && want_quad) {
-        // Step history in this form: K launches of one step on moved pointers. The kernel cannot move them itself -- with any
-        // stride, even a bare `state + state_step` for the store, its scratch frame passes the recorded 600 B --
-        // so step k runs in place on state slice k + 1, which a device copy fills from slice k first. Same computation:
-        // the fire time is the in-kernel expression, actualT0 goes to the first step only.
-        // Velocity impulses in this form: the same K launches (with or without a history), and umpc_impulse_kernel adds slice k
-        // to the state step k has just written -- with a state history that is slice k + 1, ahead of the copy that hands it
-        // to step k + 1.
-        const bool split = hs.state || hs.out || hs.status || hs.info || a.imp;
-        for (int k = 0; k < (split ? K : 1); ++k) {
-          umpc::StepIO<T> ak = a;
-          if (split) {
-            if (hs.state) {
-              ak.state = a.state + ((size_t)k + 1) * hs.state;
-              const hipError_t ec = hipMemcpyAsync(ak.state, a.state + (size_t)k * hs.state, hs.state * sizeof(T),
-                                                   hipMemcpyDeviceToDevice, (hipStream_t)stream);
-              if (ec != hipSuccess) return fail(ec, "umpcBatchRollout: history");
-            }
-            ak.ref = a.ref + (size_t)k * ref_step; ak.out = a.out + (size_t)k * hs.out;
-            if (a.status) ak.status = a.status + (size_t)k * hs.status;
-            if (a.info) ak.info = a.info + (size_t)k * hs.info;
-            ak.t0 = a.t0 + T(k) * (T(nsub) * a.prm.dtsim);
-            ak.ref_step = ak.state_step = ak.out_step = ak.status_step = ak.info_step = ak.imp_step = 0;
-            ak.imp = nullptr;
-          }
-          hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true, true>), dim3((h->B + kBlock / 4 - 1) / (kBlock / 4)), dim3(kBlock), 0,
-                             (hipStream_t)stream, ak, split ? 1 : K, k == 0 ? (const T *)actualT0 : nullptr, 0);
-          if (split && a.imp)
-            hipLaunchKernelGGL(umpc_impulse_kernel<T>, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, ak.state,
-                               a.imp + (size_t)k * imp_step, h->B);
-          if (split) {      // (a failed step stops the sequence; launch_rollout puts the cursors and the clock back)
-            const hipError_t el = hipGetLastError();
-            if (el != hipSuccess) return fail(el, "umpcBatchRollout: history / impulses");
-          }
-        }
-        h->last_kernel = "umpc_rollout_kernel<double, LDSF, ASM64, QUAD>";
-      } else if (!no_asm64 && h->step_kernel != 1 && h->prm.maxIter >= 1 && fits) {
-        hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, K,
-                           (const T *)actualT0, 0);
-        h->last_kernel = "umpc_rollout_kernel<double, LDSF, ASM64>";
-      } else {
-        hipLaunchKernelGGL((umpc_rollout_kernel<T, true, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, K,
-                           (const T *)actualT0, 0);
-        h->last_kernel = "umpc_rollout_kernel<double, LDSF>";
+      if (asm64 && h->prm.maxIter >= 2 && want_quad) {
+        const bool moved = hs.state || hs.out || hs.status || hs.info || a.imp;      // this form moves no pointer itself
+        if (!moved) hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true, true>), dim3(qgrid), dim3(kBlock), 0, s, a, K, aT0, 0);
+        else if (const int rc = launch_quad64_stepwise<T>(a, K, aT0, hs, s)) return rc;
+        return launched(h, "umpc_rollout_kernel<double, LDSF, ASM64, QUAD>");
       }
-      hipError_t e2 = hipGetLastError();
-      return e2 == hipSuccess ? 0 : fail(e2, "umpcBatchRollout");
+      if (asm64 && h->prm.maxIter >= 1) {
+        hipLaunchKernelGGL((umpc_rollout_kernel<T, true, true>), dim3(grid), dim3(kBlock), 0, s, a, K, aT0, 0);
+        return launched(h, "umpc_rollout_kernel<double, LDSF, ASM64>");
+      }
+      hipLaunchKernelGGL((umpc_rollout_kernel<T, true, false>), dim3(grid), dim3(kBlock), 0, s, a, K, aT0, 0);
+      return launched(h, "umpc_rollout_kernel<double, LDSF>");
     }
   }
-  hipLaunchKernelGGL((umpc_rollout_kernel<T, false, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, K,
-                     (const T *)actualT0, skew_us * 100);
-  h->last_kernel = sizeof(T) == 4 ? "umpc_rollout_kernel<float>" : "umpc_rollout_kernel<double>";
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchRollout");
+  // stagger wave groups by ~1/4 step when a launch carries many steps: the last group ends 3 x skew later than the
+  // first, so the stagger only pays when that tail is small against the launch (off below 64 steps)
+  const char *env = getenv("UMPC_SKEW_US");
+  const int skew_us = env ? atoi(env) : (K >= 64 && sizeof(T) == 4 && h->B >= 32768 ? 80 : 0);
+  hipLaunchKernelGGL((umpc_rollout_kernel<T, false, false>), dim3(grid), dim3(kBlock), 0, s, a, K, aT0, skew_us * 100);
+  return launched(h, sizeof(T) == 4 ? "umpc_rollout_kernel<float>" : "umpc_rollout_kernel<double>");
 }
 
 // umpcBatchRollout / umpcBatchUpdate: the refusals (before anything is launched or copied), then the launch -- in place, or,
 // with a step history set (umpcBatchSetHistory) and a plant (nsub > 0), through the tables: the kernels' own stores of step k
 // land in slice cursor + k (state: cursor + k + 1), and stream-ordered device copies keep the caller's arrays what they are
-// without a history (state in; state, out, status, info back: five copies per launch at the most, none per step).
+// without a history (state in; state, out, status, info back: five copies per launch at the most, none per step). Without a
+// history every stride is 0 and no copy is issued.
 template <typename T>
-static int launch_rollout(umpc_batch_t *h, int K, int nsub, void *state, void *ctrl, const void *ref,
-                          const void *actualT0, const void *Ib, const void *gain, void *out, void *stats,
-                          int32_t *status, void *info, void *stream) {
-  if (h->reftab && h->ref_cursor + (long long)K > h->reftab_steps) {
-    g_err = "umpcBatchRollout: the reference trajectory ends before the launch does (cursor " + std::to_string(h->ref_cursor) +
-            " + K " + std::to_string(K) + " > steps " + std::to_string(h->reftab_steps) + ")";
-    return -1;
-  }
-  const bool hist = h->hist_on() && nsub > 0 && K >= 1;
-  if (hist && h->hist_cursor + (long long)K > h->hist_steps) {
-    g_err = "umpcBatchRollout: the step history ends before the launch does (cursor " + std::to_string(h->hist_cursor) +
-            " + K " + std::to_string(K) + " > steps " + std::to_string(h->hist_steps) + ")";
-    return -1;
-  }
-  if (h->imptab && nsub > 0 && K >= 1 && h->imp_cursor + (long long)K > h->imptab_steps) {
-    g_err = "umpcBatchRollout: the impulse table ends before the launch does (cursor " + std::to_string(h->imp_cursor) +
-            " + K " + std::to_string(K) + " > steps " + std::to_string(h->imptab_steps) + ")";
-    return -1;
-  }
-  if (!state || !ctrl || (!ref && !h->reftab) || !out) { g_err = "umpcBatchRollout: null array"; return -1; }
+static int launch_rollout(umpc_batch_t *h, int K, int nsub, const RolloutArrays &io, void *stream) {
+  const bool hist = h->hist_on(K, nsub), imp = h->imp_on(K, nsub);
+  if (h->reftab && !h->ref_c.fits("umpcBatchRollout", "reference trajectory", "K ", K)) return -1;
+  if (hist && !h->hist_c.fits("umpcBatchRollout", "step history", "K ", K)) return -1;
+  if (imp && !h->imp_c.fits("umpcBatchRollout", "impulse table", "K ", K)) return -1;
+  if (!io.state || !io.ctrl || (!io.ref && !h->reftab) || !io.out) { g_err = "umpcBatchRollout: null array"; return -1; }
+  // the arrays the kernels work on: the caller's, or for the records that are on the table slices at the cursor
+  RolloutArrays t = io;
   HistStep hs;
-  if (!hist) {
-    // (a HIP error leaves the cursors and the clock where they were, as with a history)
-    const long long ref_cursor0 = h->ref_cursor, imp_cursor0 = h->imp_cursor;
-    const double t_ms0 = h->t_ms;
-    const int rc = launch_steps<T>(h, K, nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info, hs, stream);
-    if (rc) { h->ref_cursor = ref_cursor0; h->imp_cursor = imp_cursor0; h->t_ms = t_ms0; }
-    return rc;
-  }
-  const size_t B = (size_t)h->B, c = (size_t)h->hist_cursor;
+  const size_t B = (size_t)h->B, c = (size_t)h->hist_c.cursor, last = (size_t)K - 1;
+  if (hist && h->hist_state) { hs.state = 18 * B; t.state = (T *)h->hist_state + c * hs.state; }
+  if (hist && h->hist_out) { hs.out = 9 * B; t.out = (T *)h->hist_out + c * hs.out; }
+  if (hist && h->hist_status) { hs.status = B; t.status = h->hist_status + c * hs.status; }
+  if (hist && h->hist_info) { hs.info = 2 * B; t.info = (T *)h->hist_info + c * hs.info; }
+  // a failure from here on (a HIP error of a copy or a launch) returns before the cursors and the clock move: the tables and
+  // the arguments may hold part of the launch, the handle never claims steps it has not recorded
   const hipStream_t s = (hipStream_t)stream;
-  T *st = (T *)state, *o = (T *)out, *inf = (T *)info;
-  int32_t *sw = status;
   hipError_t e = hipSuccess;
-  if (h->hist_state) {
-    hs.state = 18 * B;
-    st = (T *)h->hist_state + c * hs.state;
-    if (st != (T *)state) e = hipMemcpyAsync(st, state, hs.state * sizeof(T), hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return fail(e, "umpcBatchRollout: history");
-  }
-  if (h->hist_out) { hs.out = 9 * B; o = (T *)h->hist_out + c * hs.out; }
-  if (h->hist_status) { hs.status = B; sw = h->hist_status + c * hs.status; }
-  if (h->hist_info) { hs.info = 2 * B; inf = (T *)h->hist_info + c * hs.info; }
-  // a failure from here on (a HIP error of a copy or a launch) leaves the cursors and the clock where they were: the
-  // tables and the arguments may hold part of the launch, the handle never claims steps it has not recorded
-  const long long ref_cursor0 = h->ref_cursor, hist_cursor0 = h->hist_cursor, imp_cursor0 = h->imp_cursor;
-  const double t_ms0 = h->t_ms;
-  int rc = launch_steps<T>(h, K, nsub, st, ctrl, ref, actualT0, Ib, gain, o, stats, sw, inf, hs, stream);
-  if (!rc) {
-    const size_t last = (size_t)K - 1;
-    if (h->hist_state && st + (size_t)K * hs.state != (T *)state)
-      e = hipMemcpyAsync(state, st + (size_t)K * hs.state, hs.state * sizeof(T), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && h->hist_out) e = hipMemcpyAsync(out, o + last * hs.out, hs.out * sizeof(T), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && h->hist_status && status)
-      e = hipMemcpyAsync(status, sw + last * hs.status, hs.status * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && h->hist_info && info)
-      e = hipMemcpyAsync(info, inf + last * hs.info, hs.info * sizeof(T), hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) rc = fail(e, "umpcBatchRollout: history");
-  }
-  if (rc) { h->ref_cursor = ref_cursor0; h->hist_cursor = hist_cursor0; h->imp_cursor = imp_cursor0; h->t_ms = t_ms0; return rc; }
-  h->hist_cursor = hist_cursor0 + K;
+  if (hs.state && t.state != io.state) e = hipMemcpyAsync(t.state, io.state, hs.state * sizeof(T), hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return fail(e, "umpcBatchRollout: history");
+  if (const int rc = launch_steps<T>(h, K, nsub, t, hs, stream)) return rc;
+  T *const st_end = (T *)t.state + (size_t)K * hs.state;
+  if (hs.state && st_end != (T *)io.state) e = hipMemcpyAsync(io.state, st_end, hs.state * sizeof(T), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && hs.out)
+    e = hipMemcpyAsync(io.out, (T *)t.out + last * hs.out, hs.out * sizeof(T), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && hs.status && io.status)
+    e = hipMemcpyAsync(io.status, t.status + last * hs.status, hs.status * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && hs.info && io.info)
+    e = hipMemcpyAsync(io.info, (T *)t.info + last * hs.info, hs.info * sizeof(T), hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return fail(e, "umpcBatchRollout: history");
+  if (nsub > 0) h->advance((double)K * nsub * h->prm.dtsim, h->reftab ? K : 0, hist ? K : 0, imp ? K : 0);
   return 0;
 }
 
@@ -712,38 +723,30 @@ void umpc_set_error(const char *msg) { g_err = msg; }
 template <typename T>
 static int launch_reactive(umpc_batch_t *h, int nsteps, int every, void *state, const void *ref, const void *gains,
                            const void *Ib, const void *gain, void *out, void *stats, void *stream) {
-  DevParams<T> prm = make_dev<T>(h->prm);
-  prm.task = h->task;
-  for (int i = 0; i < 4; ++i) prm.task_p[i] = (T)h->task_p[i];
   const int grid = (h->B + kBlock - 1) / kBlock;
   // velocity impulses: slice cursor + j after substep (j + 1) * nsub - 1 (umpcBatchReactive has made the range checks)
   const int nsub = h->prm.nsub;
-  const T *imp = h->imptab ? (const T *)h->imptab + (size_t)h->imp_cursor * 6 * (size_t)h->B : nullptr;
-  hipLaunchKernelGGL(umpc_reactive_kernel<T>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, prm, h->B, nsteps, every,
+  const T *imp = h->imptab ? (const T *)h->imptab + (size_t)h->imp_c.cursor * 6 * (size_t)h->B : nullptr;
+  hipLaunchKernelGGL(umpc_reactive_kernel<T>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, make_dev_task<T>(h), h->B, nsteps, every,
                      (T)h->t_ms, (T *)state, (const T *)ref, (const T *)gains, (const T *)Ib, (const T *)gain, (T *)out,
                      (T *)stats, imp, nsub > 0 ? nsub : 1);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(e, "umpcBatchReactive");      // (the clock and the cursor stay where they were)
-  h->t_ms += (double)nsteps * h->prm.dtsim;
-  if (imp) h->imp_cursor += nsteps / nsub;
+  h->advance((double)nsteps * h->prm.dtsim, 0, 0, imp ? nsteps / nsub : 0);
   return 0;
 }
 
 template <typename T>
 static int launch_task_table(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
                              const void *ref, void *tab, void *stream) {
-  DevParams<T> prm = make_dev<T>(h->prm);
-  prm.task = h->task;
-  for (int i = 0; i < 4; ++i) prm.task_p[i] = (T)h->task_p[i];
   // enough blocks in y to fill the device when B is small, never more than the steps there are (or the grid limit)
   const unsigned gx = (unsigned)((h->B + 255) / 256);
   long long gy = (2048 + gx - 1) / gx;
   if (gy > steps) gy = steps;
   if (gy > 65535) gy = 65535;
-  hipLaunchKernelGGL(umpc_task_table_kernel<T>, dim3(gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, prm, h->B, steps,
+  hipLaunchKernelGGL(umpc_task_table_kernel<T>, dim3(gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, make_dev_task<T>(h), h->B, steps,
                      (T)t_ms, task, (const T *)params, (const T *)ref, (T *)tab);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchTaskTable");
+  return launch_status("umpcBatchTaskTable");
 }
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
@@ -781,8 +784,7 @@ static int launch_score(umpc_batch_t *h, const void *state_hist, const void *out
     UMPC_SCORE_FORM(12) UMPC_SCORE_FORM(13) UMPC_SCORE_FORM(14) UMPC_SCORE_FORM(15)
   }
 #undef UMPC_SCORE_FORM
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchScore");
+  return launch_status("umpcBatchScore");
 }
 
 extern "C" {
@@ -859,62 +861,61 @@ int umpcBatchSetTask(umpc_batch_t *h, int task, const double params[4], double t
 int umpcBatchSetRefTrajectory(umpc_batch_t *h, const void *tab, long long steps, long long cursor0) {
   if (!h) { g_err = "umpcBatchSetRefTrajectory: bad argument"; return -1; }
   if (!tab) {
-    h->reftab = nullptr; h->reftab_steps = 0; h->ref_cursor = 0;
+    h->reftab = nullptr; h->ref_c = {};
     return 0;
   }
-  if (steps < 1 || cursor0 < 0 || cursor0 > steps) { g_err = "umpcBatchSetRefTrajectory: bad argument (steps >= 1, 0 <= cursor0 <= steps)"; return -1; }
+  if (!CursorTable::valid("umpcBatchSetRefTrajectory", steps, cursor0)) return -1;
   if (h->task != 0) {
     g_err = "umpcBatchSetRefTrajectory: a task generator is set (umpcBatchSetTask); a handle follows one or the other";
     return -1;
   }
-  h->reftab = tab; h->reftab_steps = steps; h->ref_cursor = cursor0;
+  h->reftab = tab; h->ref_c = {steps, cursor0};
   return 0;
 }
-long long umpcBatchRefCursor(const umpc_batch_t *h) { return h ? h->ref_cursor : 0; }
+long long umpcBatchRefCursor(const umpc_batch_t *h) { return h ? h->ref_c.cursor : 0; }
 
 int umpcBatchSetHistory(umpc_batch_t *h, void *state_hist, void *out_hist, int32_t *status_hist, void *info_hist,
                         long long steps, long long cursor0) {
   if (!h) { g_err = "umpcBatchSetHistory: bad argument"; return -1; }
   if (!state_hist && !out_hist && !status_hist && !info_hist) {
-    h->hist_state = h->hist_out = h->hist_info = nullptr; h->hist_status = nullptr; h->hist_steps = 0; h->hist_cursor = 0;
+    h->hist_state = h->hist_out = h->hist_info = nullptr; h->hist_status = nullptr; h->hist_c = {};
     return 0;
   }
-  if (steps < 1 || cursor0 < 0 || cursor0 > steps) { g_err = "umpcBatchSetHistory: bad argument (steps >= 1, 0 <= cursor0 <= steps)"; return -1; }
+  if (!CursorTable::valid("umpcBatchSetHistory", steps, cursor0)) return -1;
   if (h->prm.nsub == 0) {
     g_err = "umpcBatchSetHistory: the handle has no plant (nsub = 0): its rollouts never write the state, there is no trajectory to record";
     return -1;
   }
   if ((size_t)18 * (size_t)h->B > (size_t)0x7fffffff) { g_err = "umpcBatchSetHistory: batch too large (a slice is a 32-bit stride)"; return -1; }
   h->hist_state = state_hist; h->hist_out = out_hist; h->hist_status = status_hist; h->hist_info = info_hist;
-  h->hist_steps = steps; h->hist_cursor = cursor0;
+  h->hist_c = {steps, cursor0};
   return 0;
 }
-long long umpcBatchHistoryCursor(const umpc_batch_t *h) { return h ? h->hist_cursor : 0; }
+long long umpcBatchHistoryCursor(const umpc_batch_t *h) { return h ? h->hist_c.cursor : 0; }
 
 int umpcBatchSetImpulses(umpc_batch_t *h, const void *tab, long long steps, long long cursor0) {
   if (!h) { g_err = "umpcBatchSetImpulses: bad argument"; return -1; }
   if (!tab) {
-    h->imptab = nullptr; h->imptab_steps = 0; h->imp_cursor = 0;
+    h->imptab = nullptr; h->imp_c = {};
     return 0;
   }
-  if (steps < 1 || cursor0 < 0 || cursor0 > steps) { g_err = "umpcBatchSetImpulses: bad argument (steps >= 1, 0 <= cursor0 <= steps)"; return -1; }
+  if (!CursorTable::valid("umpcBatchSetImpulses", steps, cursor0)) return -1;
   if (h->prm.nsub == 0) {
     g_err = "umpcBatchSetImpulses: the handle has no plant (nsub = 0): its rollouts never write the state, there is nothing to push";
     return -1;
   }
   if ((size_t)6 * (size_t)h->B > (size_t)0x7fffffff) { g_err = "umpcBatchSetImpulses: batch too large (a slice is a 32-bit stride)"; return -1; }
-  h->imptab = tab; h->imptab_steps = steps; h->imp_cursor = cursor0;
+  h->imptab = tab; h->imp_c = {steps, cursor0};
   return 0;
 }
-long long umpcBatchImpulseCursor(const umpc_batch_t *h) { return h ? h->imp_cursor : 0; }
+long long umpcBatchImpulseCursor(const umpc_batch_t *h) { return h ? h->imp_c.cursor : 0; }
 
 int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
   if (!h || !score) { g_err = "umpcBatchScoreInit: bad argument"; return -1; }
   const dim3 grid((unsigned)((h->B + 255) / 256));
   if (h->dtype == UMPC_F32) hipLaunchKernelGGL(umpc::umpc_score_init_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (float *)score, h->B);
   else hipLaunchKernelGGL(umpc::umpc_score_init_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (double *)score, h->B);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchScoreInit");
+  return launch_status("umpcBatchScoreInit");
 }
 int umpcBatchScore(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
                    const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
@@ -945,8 +946,7 @@ int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *grou
     hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<float>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float *)score, group, h->B, gstat);
   else
     hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<double>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const double *)score, group, h->B, gstat);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchScoreGroups");
+  return launch_status("umpcBatchScoreGroups");
 }
 
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
@@ -991,38 +991,30 @@ int umpcBatchInitCtrl(umpc_batch_t *h, void *ctrl, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   if (h->dtype == UMPC_F32) hipLaunchKernelGGL(umpc_init_ctrl_kernel<float>, dim3(256), dim3(256), 0, s, h->B, (float *)ctrl);
   else hipLaunchKernelGGL(umpc_init_ctrl_kernel<double>, dim3(256), dim3(256), 0, s, h->B, (double *)ctrl);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchInitCtrl");
+  return launch_status("umpcBatchInitCtrl");
 }
 
 int umpcBatchRollout(umpc_batch_t *h, int K, void *state, void *ctrl, const void *ref, const void *actualT0,
                      const void *Ib, const void *gain, void *out, void *stats, int32_t *status, void *info,
                      void *stream) {
   if (K < 0) { g_err = "umpcBatchRollout: K < 0"; return -1; }
-  return h->dtype == UMPC_F32
-             ? launch_rollout<float>(h, K, h->prm.nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info, stream)
-             : launch_rollout<double>(h, K, h->prm.nsub, state, ctrl, ref, actualT0, Ib, gain, out, stats, status, info, stream);
+  const RolloutArrays io = {.state = state, .ctrl = ctrl, .ref = ref, .actualT0 = actualT0, .Ib = Ib, .gain = gain,
+                            .out = out, .stats = stats, .status = status, .info = info};
+  return h->dtype == UMPC_F32 ? launch_rollout<float>(h, K, h->prm.nsub, io, stream)
+                              : launch_rollout<double>(h, K, h->prm.nsub, io, stream);
 }
 
 int umpcBatchTaskReference(umpc_batch_t *h, double t_ms, const void *ref, void *out, void *stream) {
   if (!h || !ref || !out) { g_err = "umpcBatchTaskReference: bad argument"; return -1; }
   if (h->reftab) { g_err = "umpcBatchTaskReference: a reference trajectory is set (its slices ARE the reference)"; return -1; }
   const int grid = (h->B + 255) / 256;
-  if (h->dtype == UMPC_F32) {
-    DevParams<float> prm = make_dev<float>(h->prm);
-    prm.task = h->task;
-    for (int i = 0; i < 4; ++i) prm.task_p[i] = (float)h->task_p[i];
-    hipLaunchKernelGGL(umpc_taskref_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, prm, h->B, (float)t_ms,
-                       (const float *)ref, (float *)out);
-  } else {
-    DevParams<double> prm = make_dev<double>(h->prm);
-    prm.task = h->task;
-    for (int i = 0; i < 4; ++i) prm.task_p[i] = h->task_p[i];
-    hipLaunchKernelGGL(umpc_taskref_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, prm, h->B, t_ms,
-                       (const double *)ref, (double *)out);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchTaskReference");
+  if (h->dtype == UMPC_F32)
+    hipLaunchKernelGGL(umpc_taskref_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, make_dev_task<float>(h), h->B,
+                       (float)t_ms, (const float *)ref, (float *)out);
+  else
+    hipLaunchKernelGGL(umpc_taskref_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, make_dev_task<double>(h), h->B,
+                       t_ms, (const double *)ref, (double *)out);
+  return launch_status("umpcBatchTaskReference");
 }
 
 int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const void *ref, const void *gains,
@@ -1035,11 +1027,7 @@ int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const
       g_err = "umpcBatchReactive: impulses are set (one slice per nsub = " + std::to_string(nsub) + " substeps): nsteps must be a multiple of nsub";
       return -1;
     }
-    if (h->imp_cursor + (long long)(nsteps / nsub) > h->imptab_steps) {
-      g_err = "umpcBatchReactive: the impulse table ends before the launch does (cursor " + std::to_string(h->imp_cursor) + " + " +
-              std::to_string(nsteps / nsub) + " > steps " + std::to_string(h->imptab_steps) + ")";
-      return -1;
-    }
+    if (!h->imp_c.fits("umpcBatchReactive", "impulse table", "", nsteps / nsub)) return -1;
   }
   return h->dtype == UMPC_F32 ? launch_reactive<float>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream)
                               : launch_reactive<double>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream);
@@ -1047,9 +1035,10 @@ int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const
 
 int umpcBatchUpdate(umpc_batch_t *h, const void *state, void *ctrl, const void *ref, const void *actualT0,
                     const void *Ib, void *out, int32_t *status, void *info, void *stream) {
-  return h->dtype == UMPC_F32
-             ? launch_rollout<float>(h, 1, 0, (void *)state, ctrl, ref, actualT0, Ib, nullptr, out, nullptr, status, info, stream)
-             : launch_rollout<double>(h, 1, 0, (void *)state, ctrl, ref, actualT0, Ib, nullptr, out, nullptr, status, info, stream);
+  // one step without a plant (nsub = 0): the state is only read, there is no thrust gain and there are no statistics
+  const RolloutArrays io = {.state = (void *)state, .ctrl = ctrl, .ref = ref, .actualT0 = actualT0, .Ib = Ib,
+                            .out = out, .status = status, .info = info};
+  return h->dtype == UMPC_F32 ? launch_rollout<float>(h, 1, 0, io, stream) : launch_rollout<double>(h, 1, 0, io, stream);
 }
 
 int umpcBatchPlant(umpc_batch_t *h, int nsub, void *state, const void *u, const void *Ib, const void *gain,
@@ -1063,8 +1052,7 @@ int umpcBatchPlant(umpc_batch_t *h, int nsub, void *state, const void *u, const 
     hipLaunchKernelGGL(umpc_plant_kernel<double>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
                        make_dev<double>(h->prm), h->B, nsub, (double *)state, (const double *)u, (const double *)Ib,
                        (const double *)gain);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchPlant");
+  return launch_status("umpcBatchPlant");
 }
 
 static int assemble_launch(umpc_batch_t *h, const void *state, const void *ctrl, const void *ref, const void *Ib,
@@ -1080,8 +1068,7 @@ static int assemble_launch(umpc_batch_t *h, const void *state, const void *ctrl,
                        make_dev<double>(h->prm), h->B, (const double *)state, (const double *)ctrl,
                        (const double *)ref, (const double *)Ib, (const double *)actualT0, (double *)l, (double *)u,
                        (double *)q, (double *)Px, (double *)Ax);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchAssemble");
+  return launch_status("umpcBatchAssemble");
 }
 
 int umpcBatchAssemble(umpc_batch_t *h, const void *state, const void *ctrl, const void *ref, const void *Ib,
@@ -1327,8 +1314,8 @@ int umpcUpdate(UprightMPC_t *up, float uquad[3], float accdes[6], const float p0
     const unsigned seq = ++s.seq ? s.seq : ++s.seq;       // never 0 (the words start at 0)
     umpcasm::StepArgs pa;                                  // (the drop-in records no history: strides 0)
     umpcasm::StepParams &p = pa.p;
-    p = make_step_params(s.h, 1, 0, d + O_STATE, s.ctrl, d + O_REF, d + O_AT0, nullptr, nullptr, d + O_OUT, nullptr,
-                         (int32_t *)(d + O_STATUS), d + O_INFO);
+    p = make_step_params(s.h, 1, 0, {.state = d + O_STATE, .ctrl = s.ctrl, .ref = d + O_REF, .actualT0 = d + O_AT0, .out = d + O_OUT,
+                                     .status = (int32_t *)(d + O_STATUS), .info = d + O_INFO});
     pa.h = umpcasm::StepHist{0, 0, 0, 0};
     pa.i = umpcasm::StepImp{nullptr, 0, 0};                 // (... and takes no impulses)
     p.done = d + O_DONE0; p.seq = (int)seq;
@@ -1519,8 +1506,7 @@ int umpcBatchWLUpdate(const WLCon_t *wl, int B, int dtype, void *u, const void *
   else
     hipLaunchKernelGGL(umpc_wl_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, d, B, (double *)u,
                        (const double *)h0, (const double *)pdotdes, (double *)w0);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchWLUpdate");
+  return launch_status("umpcBatchWLUpdate");
 }
 
 int umpcBatchSetWL(umpc_batch_t *h, const WLCon_t *wl, const double Mdiag[6], void *u4, void *w0) {
@@ -1560,8 +1546,7 @@ int umpcBatchModel(int model, int B, int dtype, int nsub, double dt, void *y, co
     else
       hipLaunchKernelGGL((umpc_model_kernel<double, 1>), grid, blk, 0, s, B, nsub, dt, (double *)y, (const double *)u, (double *)aux);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, "umpcBatchModel");
+  return launch_status("umpcBatchModel");
 }
 
 void wlConInit(WLCon_t *wl, const float u0[4], const float umin[4], const float umax[4], const float dumax[4],
