@@ -36,10 +36,11 @@ qdldl_interface.c:322-369, qdldl.c:250-293, proj.c:4-14.
 the CPU test-suite can check the schedule (register reuse, fetch distances,
 packed-operand selects) against the oracle without a GPU.
 """
+import functools
 import os
 import struct
 
-from . import symbolic
+from . import asmtext, symbolic
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -811,23 +812,7 @@ def program(N=3, perm=None):
     return e.ins, s
 
 
-def fmt(t):
-    m = t[0]
-    if m == "label":
-        return "%s:" % t[1]
-    mods = ""
-    if isinstance(t[-1], dict):
-        d = t[-1]
-        t = t[:-1]
-        mods = " " + " ".join("%s:[%s]" % (k, ",".join(map(str, d[k]))) for k in ("op_sel", "op_sel_hi", "neg_lo", "neg_hi"))
-    a = [("0x%x" % x if (m == "s_mov_b32" and isinstance(x, int)) else str(x)) for x in t[1:]]
-    if m in ("ds_read_b128", "ds_write_b128", "ds_write_b32"):
-        return "%s %s, %s offset:%s" % (m, a[0], a[1], a[2])
-    if m in ("global_load_dword", "global_store_dword"):
-        return "%s %s, %s, %s" % (m, a[0], a[1], a[2])
-    if m == "s_waitcnt":
-        return "s_waitcnt " + " ".join(a)
-    return "%s %s%s" % (m, ", ".join(a), mods)
+fmt = functools.partial(asmtext.fmt, hex_ints=("s_mov_b32",))       # this generator's integer spelling (asmtext.py)
 
 
 def write(path=None, N=3, perm=None):
@@ -837,34 +822,25 @@ def write(path=None, N=3, perm=None):
     store_l = " ".join("LDSW_(%d) = -LX_(%d);" % (lpos[j], j) if lpos[j] < NLDS else "ROW_(%d) = -LX_(%d);" % (FAC_L + lpos[j], j)
                        for j in range(len(lpos)))
     used_s = [S_P, S_P + 1, S_CNT, S_P2, S_P2 + 1] + list(range(S_ALPHA, S_RHO + 2))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in range(2, V_END)] + \
-           ['"a%d"' % i for i in range(256)] + ['"s%d"' % i for i in used_s]
-    lab7 = [k for k, t in enumerate(ins) if t == ("label", "7")][0]
-    lab8 = [k for k, t in enumerate(ins) if t == ("label", "8")][0]
-    out = ["// GENERATED by robobee3d_amd/asmgen.py -- do not edit.", switch_banner(),
-           "// ADMM phase of the fp32 step kernel: %d instructions, middle-iteration body %d." % (len(ins), lab8 - lab7),
-           "#pragma once",
-           "namespace umpcasm {",
-           "constexpr int FAC_L = %d, FAC_DI = %d, FAC_Q = %d, FAC_LOEQ = %d, FAC_M = %d, FAC_ROWS = %d;" %
-           (FAC_L, FAC_DI, FAC_Q, FAC_LOEQ, FAC_M, FAC_ROWS),
-           "constexpr int WS_DS = %d, WS_ES = %d, WS_C = %d, WS_XPREV = %d, WS_DY = %d, WS_ROWS = %d;" %
-           (WS_DS, WS_ES, WS_C, WS_XPREV, WS_DY, WS_ROWS),
-           "constexpr int LDS_BYTES_PER_LANE = %d;" % (NLDS * 4),
-           "}  // namespace umpcasm",
-           "// Phase A -> loop hand-off of the factor: entry j of L (CSC order) goes NEGATED to its storage position (asmgen.solve_plan):",
-           "// LDS word LDSW_(p) for p < %d, workspace row ROW_(FAC_L + p) (-> AGPR) otherwise." % NLDS,
-           "#define UMPC_ASM_STORE_L(LDSW_, ROW_, LX_) do { %s } while (0)" % store_l,
-           "// inputs: v0 = 4*robot, v1 = lane LDS address, s[4:5] = workspace, s[6:7] = ctrl, s10 = 4*B, s11 = maxIter",
-           "#define UMPC_ADMM_ASM(voff, ldsaddr, ws, ctrl, stride, iters) asm volatile( \\"]
-    for t in ins:
-        out.append('  "%s\\n" \\' % fmt(t))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s[6:7]}"(ctrl), "{s10}"(stride), "{s11}"(iters) \\')
-    out.append("  : " + ", ".join(clob) + ")")
-    txt = "\n".join(out) + "\n"
-    old = open(path).read() if os.path.exists(path) else None
-    if old != txt:
-        with open(path, "w") as fh:
-            fh.write(txt)
+    head = ["// GENERATED by robobee3d_amd/asmgen.py -- do not edit.", switch_banner(),
+            "// ADMM phase of the fp32 step kernel: %d instructions, middle-iteration body %d."
+            % (len(ins), asmtext.label_index(ins, "8") - asmtext.label_index(ins, "7")),
+            "#pragma once",
+            "namespace umpcasm {",
+            "constexpr int FAC_L = %d, FAC_DI = %d, FAC_Q = %d, FAC_LOEQ = %d, FAC_M = %d, FAC_ROWS = %d;" %
+            (FAC_L, FAC_DI, FAC_Q, FAC_LOEQ, FAC_M, FAC_ROWS),
+            "constexpr int WS_DS = %d, WS_ES = %d, WS_C = %d, WS_XPREV = %d, WS_DY = %d, WS_ROWS = %d;" %
+            (WS_DS, WS_ES, WS_C, WS_XPREV, WS_DY, WS_ROWS),
+            "constexpr int LDS_BYTES_PER_LANE = %d;" % (NLDS * 4),
+            "}  // namespace umpcasm",
+            "// Phase A -> loop hand-off of the factor: entry j of L (CSC order) goes NEGATED to its storage position (asmgen.solve_plan):",
+            "// LDS word LDSW_(p) for p < %d, workspace row ROW_(FAC_L + p) (-> AGPR) otherwise." % NLDS,
+            "#define UMPC_ASM_STORE_L(LDSW_, ROW_, LX_) do { %s } while (0)" % store_l,
+            "// inputs: v0 = 4*robot, v1 = lane LDS address, s[4:5] = workspace, s[6:7] = ctrl, s10 = 4*B, s11 = maxIter"]
+    asmtext.write_if_changed(path, asmtext.asm_block(
+        head, "UMPC_ADMM_ASM(voff, ldsaddr, ws, ctrl, stride, iters)", ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s[6:7]}"(ctrl), "{s10}"(stride), "{s11}"(iters)',
+        asmtext.clobbers(range(2, V_END), range(256), used_s), fmt))
     return path, len(ins)
 
 

@@ -32,10 +32,11 @@ Reference mapping: auxil.c:164-228 (compute_rhs, update_x, update_z, update_y), 
 qdldl.c:250-293, proj.c:4-14.
 
 `simulate()` interprets the emitted list in exact-rounded float64 for the CPU tests."""
+import functools
 import os
 import struct
 
-from . import asmgen, symbolic
+from . import asmgen, asmtext, symbolic
 from .asmgen import (Emit, _row_ptr, _adv, FAC_Q, FAC_LOEQ, FAC_M, WS_DS, WS_ES, WS_ROWS,
                      S_WS, S_CTRL, S_STRIDE, S_ITERS, S_P, S_CNT, S_P2, S_ALPHA, S_OMA, S_SIGMA, S_RINV, S_RHO)
 
@@ -655,38 +656,11 @@ def program(N=3, perm=None, quad=False):
     return e.ins, s
 
 
-def fmt(t):
-    m = t[0]
-    if m == "label":
-        return "%s:" % t[1]
-    a = [("0x%x" % x if isinstance(x, int) and m in ("s_mov_b32", "v_add_u32", "v_mov_b32", "v_cndmask_b32") else str(x)) for x in t[1:]]
-    if m.startswith("ds_read") or m.startswith("ds_write"):
-        return "%s %s, %s offset:%s" % (m, a[0], a[1], a[2])
-    if m == "s_waitcnt":
-        return "s_waitcnt " + " ".join(a)
-    if m.endswith("_dpp") or (isinstance(t[-1], str) and t[-1].startswith("offset:")):     # trailing control / offset: no comma
-        return "%s %s %s" % (m, ", ".join(a[:-1]), t[-1])
-    return "%s %s" % (m, ", ".join(a))
+fmt = functools.partial(asmtext.fmt, hex_ints=("s_mov_b32", "v_add_u32", "v_mov_b32", "v_cndmask_b32"))   # this generator's integer spelling
 
 
 PSEUDO = ("quad_begin", "quad_end")
-
-
-def used_registers(ins):
-    """(AGPR numbers, VGPR numbers) that appear in ANY operand of the instruction list: an over-approximation of what an
-    `asm volatile` block of it may write, for exact clobber lists"""
-    import re
-    A, V = set(), set()
-    for t in ins:
-        for x in t[1:]:
-            if not isinstance(x, str):
-                continue
-            for m_ in re.finditer(r"\b([av])\[(\d+):(\d+)\]|\b([av])(\d+)\b", x):
-                if m_.group(1):
-                    (A if m_.group(1) == "a" else V).update(range(int(m_.group(2)), int(m_.group(3)) + 1))
-                else:
-                    (A if m_.group(4) == "a" else V).add(int(m_.group(5)))
-    return A, V
+_USED_S = [S_P, S_P + 1, S_CNT, S_P2, S_P2 + 1] + list(range(S_ALPHA, S_RHO + 2))     # SGPRs the ADMM block writes
 
 
 def write_quad(path=None, N=3, perm=None):
@@ -696,44 +670,32 @@ def write_quad(path=None, N=3, perm=None):
     path = path or os.path.join(HERE, "csrc", "umpc_admm_asm64_quad.h")
     ins, s = program(N, perm, quad=True)
     ins = [t for t in ins if t[0] not in PSEUDO]
-    used_s = [S_P, S_P + 1, S_CNT, S_P2, S_P2 + 1] + list(range(S_ALPHA, S_RHO + 2)) + list(range(30, 38))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in range(2, V_END)] + \
-           ['"a%d"' % i for i in range(256)] + ['"s%d"' % i for i in used_s]
-    l17 = [k for k, t in enumerate(ins) if t == ("label", "17")][0]
-    l18 = [k for k, t in enumerate(ins) if t == ("label", "18")][0]
-    out = ["// GENERATED by robobee3d_amd/asmgen64.py (quad=True) + asmquad64.py -- do not edit.", asmgen.switch_banner(),
-           "// ADMM phase of the fp64 small-batch step kernel, ONE ROBOT PER LANE QUAD: %d instructions, middle-iteration body %d."
-           % (len(ins), l18 - l17),
-           "#pragma once",
-           "// inputs: v0 = 8*robot (the same in the four lanes of a quad), v1 = lane LDS address (16*lane), s[4:5] = workspace,",
-           "// s[6:7] = ctrl, s[8:9] = umpcquad64::kTab, s10 = 8*B, s11 = maxIter >= 1",
-           "#define UMPC_ADMM_ASM64_QUAD(voff, ldsaddr, ws, ctrl, tab, stride, iters) asm volatile( \\"]
-    for t in ins:
-        out.append('  "%s\\n" \\' % fmt(t))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s[6:7]}"(ctrl), "{s[8:9]}"(tab), "{s10}"(stride), "{s11}"(iters) \\')
-    out.append("  : " + ", ".join(clob) + ")")
+    body = asmtext.label_index(ins, "18") - asmtext.label_index(ins, "17")
+    txt = asmtext.asm_block(
+        ["// GENERATED by robobee3d_amd/asmgen64.py (quad=True) + asmquad64.py -- do not edit.", asmgen.switch_banner(),
+         "// ADMM phase of the fp64 small-batch step kernel, ONE ROBOT PER LANE QUAD: %d instructions, middle-iteration body %d."
+         % (len(ins), body),
+         "#pragma once",
+         "// inputs: v0 = 8*robot (the same in the four lanes of a quad), v1 = lane LDS address (16*lane), s[4:5] = workspace,",
+         "// s[6:7] = ctrl, s[8:9] = umpcquad64::kTab, s10 = 8*B, s11 = maxIter >= 1"],
+        "UMPC_ADMM_ASM64_QUAD(voff, ldsaddr, ws, ctrl, tab, stride, iters)", ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s[6:7]}"(ctrl), "{s[8:9]}"(tab), "{s10}"(stride), "{s11}"(iters)',
+        asmtext.clobbers(range(2, V_END), range(256), _USED_S + list(range(30, 38))), fmt)
     # the Ruiz passes on the quad
     rins, _ = asmquad64.ruiz_program(N, perm)
     rins = [t for t in rins if t[0] not in PSEUDO]
-    r27 = [k for k, t_ in enumerate(rins) if t_ == ("label", "27")][0]
     rend = [k for k, t_ in enumerate(rins) if t_[0] == "s_cbranch_scc1"][-1]
     # exact VGPR clobbers (round 5: the quad passes touch v2..v187 and no AGPR; what lives across them stays in registers)
-    rclob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in sorted(used_registers(rins)[1] - {0, 1})] + \
-            ['"s%d"' % i for i in [S_CNT] + list(range(30, 42))]
-    assert not used_registers(rins)[0]
-    out += ["// The Ruiz passes of the fp64 step on the lane quad (asmquad64.ruiz_program): %d instructions, %d per pass (one-lane"
-            % (len(rins), rend - r27),
-            "// block: 2 546 per pass). LDS words in and out as UMPC_RUIZ_ASM64; every lane's slice ends with the whole result.",
-            "// inputs: v1 = lane LDS address (16*lane), s11 = passes >= 1",
-            "#define UMPC_RUIZ_ASM64_QUAD(ldsaddr, passes) asm volatile( \\"]
-    for t_ in rins:
-        out.append('  "%s\\n" \\' % fmt(t_))
-    out.append('  : : "{v1}"(ldsaddr), "{s11}"(passes) \\')
-    out.append("  : " + ", ".join(rclob) + ")")
-    txt = "\n".join(out) + "\n"
-    if not os.path.exists(path) or open(path).read() != txt:
-        with open(path, "w") as fh:
-            fh.write(txt)
+    ra, rv = asmtext.used_registers(rins)
+    assert not ra
+    txt += asmtext.asm_block(
+        ["// The Ruiz passes of the fp64 step on the lane quad (asmquad64.ruiz_program): %d instructions, %d per pass (one-lane"
+         % (len(rins), rend - asmtext.label_index(rins, "27")),
+         "// block: 2 546 per pass). LDS words in and out as UMPC_RUIZ_ASM64; every lane's slice ends with the whole result.",
+         "// inputs: v1 = lane LDS address (16*lane), s11 = passes >= 1"],
+        "UMPC_RUIZ_ASM64_QUAD(ldsaddr, passes)", rins, '"{v1}"(ldsaddr), "{s11}"(passes)',
+        asmtext.clobbers(sorted(rv - {0, 1}), s=[S_CNT] + list(range(30, 42))), fmt)
+    asmtext.write_if_changed(path, txt)
     tab = asmquad64.table(asmquad64.plan_for(s))
     tpath = os.path.join(os.path.dirname(path), "umpc_quad64_tab.h")
     ttxt = "// GENERATED by robobee3d_amd/asmgen64.py (write_quad) -- do not edit.\n#pragma once\n#include <stdint.h>\n" \
@@ -741,76 +703,59 @@ def write_quad(path=None, N=3, perm=None):
            "// instruction q of the quad loop (asmquad64.table); the zero word where it has none\n" \
            "namespace umpcquad64 {\n__device__ const uint32_t kTab[4][%d] = {\n%s\n};\n}  // namespace umpcquad64\n" % (
                tab.shape[1], ",\n".join("  {" + ", ".join(str(int(x)) for x in row) + "}" for row in tab))
-    if not os.path.exists(tpath) or open(tpath).read() != ttxt:
-        with open(tpath, "w") as fh:
-            fh.write(ttxt)
-    return path, len(ins), l18 - l17
+    asmtext.write_if_changed(tpath, ttxt)
+    return path, len(ins), body
 
 
 def write(path=None, N=3, perm=None):
     path = path or os.path.join(HERE, "csrc", "umpc_admm_asm64.h")
     ins, s = program(N, perm)
-    used_s = [S_P, S_P + 1, S_CNT, S_P2, S_P2 + 1] + list(range(S_ALPHA, S_RHO + 2)) + \
-             (list(range(36, 48)) if os.environ.get("UMPC_ASM64_TIMING") == "1" else [])
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in range(2, V_END)] + \
-           ['"a%d"' % i for i in range(256)] + ['"s%d"' % i for i in used_s]
-    lab7 = [k for k, t in enumerate(ins) if t == ("label", "7")][0]
-    lab8 = [k for k, t in enumerate(ins) if t == ("label", "8")][0]
-    out = ["// GENERATED by robobee3d_amd/asmgen64.py -- do not edit.", asmgen.switch_banner(),
-           "// ADMM phase of the fp64 small-batch step kernel: %d instructions, middle-iteration body %d." % (len(ins), lab8 - lab7),
-           "#pragma once",
-           "namespace umpcasm64 {",
-           "constexpr int LDS_BYTES_PER_LANE = %d, LW_X = %d, LW_Y = %d;" % (LDS_BYTES_PER_LANE, LW_X, LW_Y),
-           "// LDS words phase C reads after the loop: D, E of phase A, z, x_prev and delta_y of the last iteration, lo3, up3",
-           "constexpr int PC_DS = %d, PC_ES = %d, PC_Z = %d, PC_XP = %d, PC_DY = %d, PC_LO3 = %d, PC_UP3 = %d;"
-           % (PC_DS, PC_ES, PC_Z, PC_XP, PC_DY, PC_LO3, PC_UP3),
-           "}  // namespace umpcasm64",
-           "// inputs: v0 = 8*robot, v1 = lane LDS address (16*lane), s[4:5] = workspace, s[6:7] = ctrl, s10 = 8*B, s11 = maxIter >= 1",
-           "#define UMPC_ADMM_ASM64(voff, ldsaddr, ws, ctrl, stride, iters) asm volatile( \\"]
-    for t in ins:
-        out.append('  "%s\\n" \\' % fmt(t))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s[6:7]}"(ctrl), "{s10}"(stride), "{s11}"(iters) \\')
-    out.append("  : " + ", ".join(clob) + ")")
+    body = asmtext.label_index(ins, "8") - asmtext.label_index(ins, "7")
+    timing_s = list(range(36, 48)) if os.environ.get("UMPC_ASM64_TIMING") == "1" else []
+    txt = asmtext.asm_block(
+        ["// GENERATED by robobee3d_amd/asmgen64.py -- do not edit.", asmgen.switch_banner(),
+         "// ADMM phase of the fp64 small-batch step kernel: %d instructions, middle-iteration body %d." % (len(ins), body),
+         "#pragma once",
+         "namespace umpcasm64 {",
+         "constexpr int LDS_BYTES_PER_LANE = %d, LW_X = %d, LW_Y = %d;" % (LDS_BYTES_PER_LANE, LW_X, LW_Y),
+         "// LDS words phase C reads after the loop: D, E of phase A, z, x_prev and delta_y of the last iteration, lo3, up3",
+         "constexpr int PC_DS = %d, PC_ES = %d, PC_Z = %d, PC_XP = %d, PC_DY = %d, PC_LO3 = %d, PC_UP3 = %d;"
+         % (PC_DS, PC_ES, PC_Z, PC_XP, PC_DY, PC_LO3, PC_UP3),
+         "}  // namespace umpcasm64",
+         "// inputs: v0 = 8*robot, v1 = lane LDS address (16*lane), s[4:5] = workspace, s[6:7] = ctrl, s10 = 8*B, s11 = maxIter >= 1"],
+        "UMPC_ADMM_ASM64(voff, ldsaddr, ws, ctrl, stride, iters)", ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s[6:7]}"(ctrl), "{s10}"(stride), "{s11}"(iters)',
+        asmtext.clobbers(range(2, V_END), range(256), _USED_S + timing_s), fmt)
     # the Ruiz passes
     rins, _ = ruiz_program(N, perm)
-    rclob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in range(2, V_END)] + ['"a%d"' % i for i in range(256)] + \
-            ['"s%d"' % i for i in [S_CNT, S_MINS, S_MINS + 1, S_MAXS, S_MAXS + 1]]
-    rl7 = [k for k, t_ in enumerate(rins) if t_ == ("label", "7")][0]
-    out += ["// The Ruiz passes of the fp64 step (scaling.c:44-156): %d instructions, %d per pass. LDS words (LDSF_W layout):"
-            % (len(rins), sum(1 for t_ in rins[rl7:] if t_[0] in ("s_cbranch_scc1",)) and
-               [k for k, t_ in enumerate(rins) if t_[0] == "s_cbranch_scc1"][0] - rl7),
-            "// P at RZ_P.., q at RZ_Q.., A at RZ_A.. on entry and exit, the accumulated cost scaling c at RZ_C on exit.",
-            "namespace umpcasm64 { constexpr int RZ_P = %d, RZ_C = %d, RZ_Q = %d, RZ_A = %d; }" % (RZ_P, RZ_C, RZ_Q, RZ_A),
-            "// inputs: v1 = lane LDS address (16*lane), s11 = passes >= 1",
-            "#define UMPC_RUIZ_ASM64(ldsaddr, passes) asm volatile( \\"]
-    for t_ in rins:
-        out.append('  "%s\\n" \\' % fmt(t_))
-    out.append('  : : "{v1}"(ldsaddr), "{s11}"(passes) \\')
-    out.append("  : " + ", ".join(rclob) + ")")
+    rl7 = asmtext.label_index(rins, "7")
+    txt += asmtext.asm_block(
+        ["// The Ruiz passes of the fp64 step (scaling.c:44-156): %d instructions, %d per pass. LDS words (LDSF_W layout):"
+         % (len(rins), sum(1 for t_ in rins[rl7:] if t_[0] in ("s_cbranch_scc1",)) and
+            [k for k, t_ in enumerate(rins) if t_[0] == "s_cbranch_scc1"][0] - rl7),
+         "// P at RZ_P.., q at RZ_Q.., A at RZ_A.. on entry and exit, the accumulated cost scaling c at RZ_C on exit.",
+         "namespace umpcasm64 { constexpr int RZ_P = %d, RZ_C = %d, RZ_Q = %d, RZ_A = %d; }" % (RZ_P, RZ_C, RZ_Q, RZ_A),
+         "// inputs: v1 = lane LDS address (16*lane), s11 = passes >= 1"],
+        "UMPC_RUIZ_ASM64(ldsaddr, passes)", rins, '"{v1}"(ldsaddr), "{s11}"(passes)',
+        asmtext.clobbers(range(2, V_END), range(256), [S_CNT, S_MINS, S_MINS + 1, S_MAXS, S_MAXS + 1]), fmt)
     # the residual norms
     sins, _ = resid_program(N, perm)
     # exact AGPR clobbers (round 5): the block touches 70 AGPRs; the compiler may keep what lives across it (state, weights,
     # row pointers) in the other 186 -- v_accvgpr_write / read instead of scratch stores / loads around the block
-    sclob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in sorted(used_registers(sins)[1] - {0, 1})] + ['"a%d"' % i for i in sorted(used_registers(sins)[0])] + \
-            ['"s%d"' % i for i in [S_P, S_P + 1]]
-    out += ["// The residual norms of the fp64 step (auxil.c:243-307): %d instructions. LDS words in: x, y, z, D, E where the ADMM"
-            % len(sins),
-            "// block left them, RS_PAR.. (T0 dt, s0 dt[3], Btau dt[6]), RS_C c, RS_W.. the eight weights, RS_DT dt; out: RS_OUT..",
-            "// = pri_res, dua_res before the division by c, |z|, |Ax|, |q|, |A'y|, |Px| norms, NaN accumulator.",
-            "namespace umpcasm64 { constexpr int RS_PAR = %d, RS_C = %d, RS_W = %d, RS_DT = %d, RS_OUT = %d; }"
-            % (RS_PAR, RS_C, RS_W, RS_DT, RS_OUT),
-            "// inputs: v0 = 8*robot, v1 = lane LDS address (16*lane), s[4:5] = workspace, s10 = 8*B",
-            "#define UMPC_RESID_ASM64(voff, ldsaddr, ws, stride) asm volatile( \\"]
-    for t_ in sins:
-        out.append('  "%s\\n" \\' % fmt(t_))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s10}"(stride) \\')
-    out.append("  : " + ", ".join(sclob) + ")")
-    txt = "\n".join(out) + "\n"
-    old = open(path).read() if os.path.exists(path) else None
-    if old != txt:
-        with open(path, "w") as fh:
-            fh.write(txt)
-    return path, len(ins), lab8 - lab7
+    sa, sv = asmtext.used_registers(sins)
+    txt += asmtext.asm_block(
+        ["// The residual norms of the fp64 step (auxil.c:243-307): %d instructions. LDS words in: x, y, z, D, E where the ADMM"
+         % len(sins),
+         "// block left them, RS_PAR.. (T0 dt, s0 dt[3], Btau dt[6]), RS_C c, RS_W.. the eight weights, RS_DT dt; out: RS_OUT..",
+         "// = pri_res, dua_res before the division by c, |z|, |Ax|, |q|, |A'y|, |Px| norms, NaN accumulator.",
+         "namespace umpcasm64 { constexpr int RS_PAR = %d, RS_C = %d, RS_W = %d, RS_DT = %d, RS_OUT = %d; }"
+         % (RS_PAR, RS_C, RS_W, RS_DT, RS_OUT),
+         "// inputs: v0 = 8*robot, v1 = lane LDS address (16*lane), s[4:5] = workspace, s10 = 8*B"],
+        "UMPC_RESID_ASM64(voff, ldsaddr, ws, stride)", sins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(ws), "{s10}"(stride)',
+        asmtext.clobbers(sorted(sv - {0, 1}), sorted(sa), [S_P, S_P + 1]), fmt)
+    asmtext.write_if_changed(path, txt)
+    return path, len(ins), body
 
 
 # ---------------------------------------------------------------------------

@@ -43,11 +43,13 @@ The W registers a wavefront no longer needs hold its entries of L and its other 
 four wavefronts at work the CU's one LDS pipe is the second bottleneck. Still bit-identical to the one-wavefront block. And
 asmgen.Emit keeps the one hazard nobody checks for inline assembly out of every stream (a VALU write to the data registers of a
 ds_write_b128 within two wait states)."""
+import functools
 import os
 import struct
 
 import numpy as np
 
+from . import asmtext
 from .asmgen import Emit, f32bits, pk as _pk
 from .isasim import AddressFault  # noqa: F401  (raised by the interpreter; the tests catch it from here)
 
@@ -1949,27 +1951,8 @@ def loop_group_program(s, eq_rows, res, nw=4, loose=True):
 S_LWAVE = 33                       # loop_group_program: s33 = the wave's index in its workgroup
 
 
-def fmt(t):
-    m = t[0]
-    if m == "label":
-        return "%s:" % t[1]
-    if isinstance(t[-1], dict):          # VOP3P (packed) instruction: operands + op_sel / op_sel_hi / neg_lo / neg_hi
-        d = t[-1]
-        return "%s %s %s" % (m, ", ".join(str(x) for x in t[1:-1]),
-                             " ".join("%s:[%s]" % (k, ",".join(map(str, d[k]))) for k in ("op_sel", "op_sel_hi", "neg_lo", "neg_hi")))
-    a = [("0x%x" % x if isinstance(x, int) and m in ("s_mov_b32", "v_add_u32", "v_and_b32", "v_mov_b32") else str(x)) for x in t[1:]]
-    if m.startswith("ds_"):
-        return "%s %s, %s offset:%s" % (m, a[0], a[1], a[2])
-    if m.startswith("global_"):
-        # cache policy (round 5, tools/ab_qp_nt.sh): "rows" = the caller's [row][B] arrays (lane offset v0: read or written once
-        # per tick), "stream" = the kernel's own per-workgroup stream blocks (written once, read once, by the same workgroup)
-        off = a[1] if m == "global_load_dword" else a[0]
-        kind = "rows" if off == "v0" else "stream"
-        nt = (len(a) > 4 and a[4] == "nt") or kind in NT_KINDS
-        return "%s %s, %s, %s offset:%s%s" % (m, a[0], a[1], a[2], a[3], " nt" if nt else "")
-    if m == "s_waitcnt":
-        return "s_waitcnt " + " ".join(a)
-    return "%s %s" % (m, ", ".join(a))
+# this generator's integer spelling; its global_* tuples are (dst, off, ptr, offset[, "nt"]), cache policy by NT_KINDS
+fmt = functools.partial(asmtext.fmt, hex_ints=("s_mov_b32", "v_add_u32", "v_and_b32", "v_mov_b32"), nt_kinds=NT_KINDS)
 
 
 # ---------------------------------------------------------------------------

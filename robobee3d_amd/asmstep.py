@@ -27,10 +27,11 @@ round 3 -- the SURVEY 8(f) workloads as options of the same stream: a task table
 step, scalar loads), per-robot objective weights (gain sweeps; parked in AGPRs across Ruiz and the loop), the fused WL step
 (funapprox.c:118-165) and a completion word for hosts that poll (the B = 1 drop-in). umpc_mi355x.hip dispatches.
 """
+import functools
 import os
 import struct
 
-from . import asmgen, symbolic
+from . import asmgen, asmtext, symbolic
 from .asmgen import (A_D, A_L, A_LO, A_M, A_Q, NLDS, NVZ, S_ALPHA, S_CNT, S_ITERS, S_OMA, S_RHO, S_RINV, S_SIGMA,
                      V_W, V_WZ, V_X, V_Y, V_Z, Emit, f32bits, pk, _sb, _vp)
 
@@ -2252,38 +2253,7 @@ class StepGen:
 # ----------------------------------------------------------------------------------------------------------
 # Text output
 # ----------------------------------------------------------------------------------------------------------
-def fmt(t):
-    m = t[0]
-    if m == "label":
-        return "%s:" % t[1]
-    mods = ""
-    if isinstance(t[-1], dict):
-        d = t[-1]
-        t = t[:-1]
-        keys = ("op_sel",) if m == "v_pk_mov_b32" else ("op_sel", "op_sel_hi", "neg_lo", "neg_hi")
-        mods = " " + " ".join("%s:[%s]" % (k, ",".join(map(str, d[k]))) for k in keys)
-
-    def a_(x):
-        if isinstance(x, float):
-            return repr(x)
-        if isinstance(x, int):
-            return ("0x%x" % x) if x > 64 else str(x)
-        return str(x)
-    a = [a_(x) for x in t[1:]]
-    if m in ("ds_read_b128", "ds_write_b128", "ds_write_b32", "ds_read_b32"):
-        return "%s %s, %s offset:%s" % (m, a[0], a[1], t[3])
-    if m.startswith("s_load_"):
-        return "%s %s, %s, %s%s" % (m, a[0], a[1], ("0x%x" % t[3]) if isinstance(t[3], int) else t[3],
-                                    (" " + t[4]) if len(t) > 4 else "")
-    if m.startswith("global_") and isinstance(t[-1], str) and (t[-1].startswith("offset:") or t[-1].startswith("sc") or t[-1].startswith("nt")):
-        return "%s %s %s" % (m, ", ".join(a[:-1]), t[-1])
-    if m == "buffer_wbl2":
-        return "buffer_wbl2 %s" % t[1]
-    if m == "s_waitcnt":
-        return "s_waitcnt " + " ".join(a)
-    if m.endswith("_dpp"):          # the DPP control follows the operands without a comma
-        return "%s %s %s" % (m, ", ".join(a[:-1]), t[-1])
-    return "%s %s%s" % (m, ", ".join(a), mods)
+fmt = functools.partial(asmtext.fmt, hex_ints=asmtext.HEX_ABOVE_64)       # this generator's integer spelling
 
 
 PSEUDO = ("kill", "quad_begin", "quad_end")      # markers for the CPU interpreters, not instructions
@@ -2295,31 +2265,27 @@ def write(path=None, N=3, perm=None, quad=False):
     path = path or os.path.join(HERE, "csrc", "umpc_step_asm_quad.h" if quad else "umpc_step_asm.h")
     g = StepGen(N, perm, quad=quad)
     ins = [t for t in g.program() if t[0] not in PSEUDO]
-    used_s = sorted(set(range(4, 102)))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in range(2, 256)] + ['"a%d"' % i for i in range(256)] + \
-           ['"s%d"' % i for i in used_s]
     if quad:
-        out = ["// GENERATED by robobee3d_amd/asmstep.py (quad=True) + asmquad.py -- do not edit.", asmgen.switch_banner(),
+        head = ["// GENERATED by robobee3d_amd/asmstep.py (quad=True) + asmquad.py -- do not edit.", asmgen.switch_banner(),
                "// The all-assembly fp32 step kernel body, ONE ROBOT PER LANE QUAD (16 robots per wavefront): %d instructions."
                % len(ins),
                "// Every lane of a quad gets the same v0 (= 4 * robot) and its own LDS slice; include umpc_step_asm.h first (StepParams).",
-               "#pragma once",
-               "#define UMPC_STEP_ASM_QUAD(voff, ldsaddr, params) asm volatile( \\"]
+               "#pragma once"]
     else:
-        out = ["// GENERATED by robobee3d_amd/asmstep.py -- do not edit.", asmgen.switch_banner(),
+        head = ["// GENERATED by robobee3d_amd/asmstep.py -- do not edit.", asmgen.switch_banner(),
                "// The all-assembly fp32 step kernel body: %d instructions (K closed-loop steps of one wavefront)." % len(ins),
                "#pragma once", "#include <stddef.h>", "#include <stdint.h>", "namespace umpcasm {",
                "// parameter block read by the kernel with s_load (byte offsets are part of the generated code)",
                "struct StepParams {"]
         for n in PTRS:
-            out.append("  const void *%s;" % n)
+            head.append("  const void *%s;" % n)
         for n in INTS:
-            out.append("  int32_t %s;" % n)
+            head.append("  int32_t %s;" % n)
         for n in FLOATS:
-            out.append("  float %s;" % n)
+            head.append("  float %s;" % n)
         for n in TAIL_INTS:
-            out.append("  int32_t %s;" % n)
-        out += ["};", "static_assert(sizeof(StepParams) == %d, \"StepParams layout\");" % ((PARAM_BYTES + 7) // 8 * 8),
+            head.append("  int32_t %s;" % n)
+        head += ["};", "static_assert(sizeof(StepParams) == %d, \"StepParams layout\");" % ((PARAM_BYTES + 7) // 8 * 8),
                 "// step history (umpcBatchSetHistory): bytes the state / out / status / info pointers advance per closed-loop step,",
                 "// read by the stream at byte %d of the kernarg segment: the kernels take ONE StepArgs as their first argument" % HIST_OFF,
                 "struct StepHist {"] + ["  int32_t %s;" % n for n in HIST_INTS] + ["};",
@@ -2330,17 +2296,11 @@ def write(path=None, N=3, perm=None, quad=False):
                 "static_assert(offsetof(StepArgs, h) == %d && sizeof(StepHist) == %d, \"StepHist layout\");" % (HIST_OFF, HIST_BYTES),
                 "static_assert(offsetof(StepArgs, i) == %d && sizeof(StepImp) == %d && offsetof(StepImp, impstep) == 8, \"StepImp layout\");" % (IMP_OFF, IMP_BYTES),
                 "constexpr int STEP_LDS_BYTES_PER_LANE = %d;" % (NLDS * 4), "}  // namespace umpcasm",
-                "// inputs: v0 = 4 * robot, v1 = lane LDS address, s[4:5] = &StepParams (kernarg)",
-                "#define UMPC_STEP_ASM(voff, ldsaddr, params) asm volatile( \\"]
-    for t in ins:
-        out.append('  "%s\\n" \\' % fmt(t))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(params) \\')
-    out.append("  : " + ", ".join(clob) + ")")
-    txt = "\n".join(out) + "\n"
-    old = open(path).read() if os.path.exists(path) else None
-    if old != txt:
-        with open(path, "w") as fh:
-            fh.write(txt)
+                "// inputs: v0 = 4 * robot, v1 = lane LDS address, s[4:5] = &StepParams (kernarg)"]
+    asmtext.write_if_changed(path, asmtext.asm_block(
+        head, "UMPC_STEP_ASM%s(voff, ldsaddr, params)" % ("_QUAD" if quad else ""), ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(params)',
+        asmtext.clobbers(range(2, 256), range(256), range(4, 102)), fmt))
     return path, len(ins)
 
 

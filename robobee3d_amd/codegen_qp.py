@@ -10,7 +10,7 @@ template QP N = 3, UprightMPC2 N = 5.
 """
 import os
 
-from . import batchqp, qpstruct
+from . import asmtext, batchqp, qpstruct
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -561,165 +561,131 @@ def _stamp_clobbers():
 
 def glue_macro(name, ins, group=False):
     from . import asmqp
-    clob = ['"memory"', '"scc"', '"vcc"'] + _stamp_clobbers() + ['"v%d"' % i for i in [2, 3] + list(range(9, asmqp.V_END))] + \
-           ['"s%d"' % i for i in (asmqp.S_P, asmqp.S_P + 1)] + ['"s%d"' % (q + h) for q in asmqp.GLUE_PTRS for h in (0, 1)]
-    out = ["// Glue between the Ruiz block and the loop (asmqp.glue_program): rho classification, scaled bounds, the loop's stream,",
-           "// LDS word %d = 1 iff the wave may take the all-assembly route. %d instructions." % (asmqp.GLUE_FLAG, len(ins)),
-           "// inputs: v0 = 4*robot, v1 = lane LDS address, v4 = 4*lane, s[4:5] / s[8:9] / s[24:25] / s[26:27] = l, u, Eprev, z rows,",
-           "// s[6:7] = the wave's stream block, s10 = 4*B, v5..v8 = rho, 1/rho, rho_eq, 1/rho_eq (floats)",
-           "#define BQP_%s_GLUE_ASM(voff, ldsaddr, lane4, lp, sblk, up, stride, ep, zp, rho0, rinv0, rhoeq, rinveq) asm volatile( \\" % name.upper()]
+    head = ["// Glue between the Ruiz block and the loop (asmqp.glue_program): rho classification, scaled bounds, the loop's stream,",
+            "// LDS word %d = 1 iff the wave may take the all-assembly route. %d instructions." % (asmqp.GLUE_FLAG, len(ins)),
+            "// inputs: v0 = 4*robot, v1 = lane LDS address, v4 = 4*lane, s[4:5] / s[8:9] / s[24:25] / s[26:27] = l, u, Eprev, z rows,",
+            "// s[6:7] = the wave's stream block, s10 = 4*B, v5..v8 = rho, 1/rho, rho_eq, 1/rho_eq (floats)"]
     if group:
-        out = ["// The glue block SHARED by the %d wavefronts of a workgroup (asmqp.glue_group_program): each a quarter of the rows and of q,"
-               % ASM_GROUP_WAVES,
-               "// the two flag words combined with LDS float-min atomics between two barriers; s%d = the wavefront's index. %d instructions."
-               % (asmqp.S_GWAVE, len(ins)),
-               "#define BQP_%s_GLUE4_ASM(voff, ldsaddr, lane4, lp, sblk, up, stride, ep, zp, rho0, rinv0, rhoeq, rinveq, wave) asm volatile( \\" % name.upper()]
-    for t_ in ins:
-        out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[4:5]}"(lp), "{s[6:7]}"(sblk), "{s[8:9]}"(up), "{s10}"(stride), '
-               '"{s[24:25]}"(ep), "{s[26:27]}"(zp), "{v5}"(rho0), "{v6}"(rinv0), "{v7}"(rhoeq), "{v8}"(rinveq)%s \\'
-               % (', "{s%d}"(wave)' % asmqp.S_GWAVE if group else ""))
-    out.append("  : " + ", ".join(clob) + ")")
-    return "\n".join(out) + "\n"
+        head = ["// The glue block SHARED by the %d wavefronts of a workgroup (asmqp.glue_group_program): each a quarter of the rows and of q,"
+                % ASM_GROUP_WAVES,
+                "// the two flag words combined with LDS float-min atomics between two barriers; s%d = the wavefront's index. %d instructions."
+                % (asmqp.S_GWAVE, len(ins))]
+    return asmtext.asm_block(
+        head, "BQP_%s_GLUE%s_ASM(voff, ldsaddr, lane4, lp, sblk, up, stride, ep, zp, rho0, rinv0, rhoeq, rinveq%s)"
+        % (name.upper(), "4" if group else "", ", wave" if group else ""), ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[4:5]}"(lp), "{s[6:7]}"(sblk), "{s[8:9]}"(up), "{s10}"(stride), '
+        '"{s[24:25]}"(ep), "{s[26:27]}"(zp), "{v5}"(rho0), "{v6}"(rinv0), "{v7}"(rhoeq), "{v8}"(rinveq)%s'
+        % (', "{s%d}"(wave)' % asmqp.S_GWAVE if group else ""),
+        asmtext.clobbers([2, 3] + list(range(9, asmqp.V_END)),
+                         s=[asmqp.S_P, asmqp.S_P + 1] + [q + h for q in asmqp.GLUE_PTRS for h in (0, 1)], extra=_stamp_clobbers()),
+        asmqp.fmt)
 
 
 def asm_macro(name, ins, plan, loose=False, group=None):
     """csrc/gen/bqp_<name>_asm.h: the instruction stream of asmqp.program as one asm volatile statement
     (loose: the variant for waves whose inequality rows are all loose rows, asmqp.S_RIMIN; same interface, fast start only;
-    group: an asmqp.LoopSplit -- the loose variant shared by the workgroup's wavefronts, asmqp.loop_group_program)"""
-    from . import asmqp
+    group: an asmqp.LoopSplit -- the variant shared by the workgroup's wavefronts, asmqp.loop_group_program: one more input,
+    the wavefront's index, the loose variant's SGPRs and the stamp registers of the diagnostic builds)"""
+    from . import asmgen, asmqp
     if group is not None:
-        used_s = [asmqp.S_P, asmqp.S_P + 1, asmqp.S_CNT, asmqp.S_SP, asmqp.S_SP + 1, asmqp.S_RIMIN, asmqp.S_RHOMIN, asmqp.S_DLEAF]
-        clob = ['"memory"', '"scc"', '"vcc"'] + _stamp_clobbers() + ['"v%d"' % i for i in [2, 3] + list(range(5, asmqp.V_END))] + \
-               ['"a%d"' % i for i in range(256)] + ['"s%d"' % i for i in used_s]
         nv = [sum(1 for w_ in group.varw if w_ == w) for w in range(group.active)]
         nk_ = [sum(1 for w_ in group.kw if w_ == w) for w in range(group.active)]
-        out = ["// The %s variant SHARED by the workgroup's wavefronts (asmqp.loop_group_program / LoopSplit): the QP's connected" % ("LOOSE" if loose else "GENERAL"),
-               "// components are independent QPs, dealt out to the wavefronts (%s of %d variables, %s of %d KKT unknowns); they meet at"
-               % (" + ".join(map(str, nv)), len(group.varw), " + ".join(map(str, nk_)), len(group.kw)),
-               "// %d barriers, none inside the loop; same LDS layout, disjoint words, bit-identical"
-               % (sum(t_[0] == "s_barrier" for t_ in ins) // group.nw),
-               "// words. s%d = the wavefront's index; the other inputs as BQP_%s_ASM_LOOSE. %d instructions."
-               % (asmqp.S_LWAVE, name.upper(), len(ins)),
-               "#define BQP_%s_ASM%s4(voff, ldsaddr, lane4, ws, sblk, stride, iters, alpha, oma, sigma, rinveq, xi, yi, zi, fast, rho0, rinv0, rhoeq, wave) asm volatile( \\" % (name.upper(), "_LOOSE" if loose else "")]
-        for t_ in ins:
-            out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-        out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[4:5]}"(ws), "{s[6:7]}"(sblk), "{s10}"(stride), '
-                   '"{s11}"(iters), "{s20}"(alpha), "{s21}"(oma), "{s22}"(sigma), "{s23}"(rinveq), "{s[24:25]}"(xi), "{s[26:27]}"(yi), '
-                   '"{s[28:29]}"(zi), "{s30}"(fast), "{s31}"(rho0), "{s34}"(rinv0), "{s35}"(rhoeq), "{s%d}"(wave) \\' % asmqp.S_LWAVE)
-        out.append("  : " + ", ".join(clob) + ")")
-        return "\n".join(out) + "\n"
-    used_s = [asmqp.S_P, asmqp.S_P + 1, asmqp.S_CNT, asmqp.S_SP, asmqp.S_SP + 1] + ([asmqp.S_RIMIN, asmqp.S_RHOMIN, asmqp.S_DLEAF] if loose else [])
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in [2, 3] + list(range(5, asmqp.V_END))] + \
-           ['"a%d"' % i for i in range(256)] + ['"s%d"' % i for i in used_s]
-    lab7 = [k for k, t_ in enumerate(ins) if t_ == ("label", "7")][0]
-    from . import asmgen
-    out = ["// GENERATED by robobee3d_amd/asmqp.py via codegen_qp.py -- do not edit.", asmgen.switch_banner(),
-           "// %s ADMM iterations of the %s structure, fp32, one lane per robot, one wave per CU: %d instructions, %d"
-           % ("LOOSE variant (every inequality row a loose row: nothing streamed per row, no clipping) of the" if loose else "Middle",
-              name, len(ins), sum(1 for t_ in ins[lab7:] if t_[0] != "label")),
-           "// from the loop label on (loop body + epilogue). Stream block: %d items per iteration + %d loaded once."
-           % (plan.n_stream, len(plan.extra))] + ([] if loose else [
-           "#pragma once",
-           "constexpr int BQP_%s_ASM_STREAM_ITEMS = %d, BQP_%s_ASM_ROWS = %d;" % (name.upper(), plan.n_stream + len(plan.extra),
-                                                                          name.upper(), plan.R_END)]) + [
-           "// inputs: v0 = 4*robot, v1 = lane LDS address, v4 = 4*lane, s[4:5] = row workspace, s[6:7] = the wave's stream",
-           "// block, s10 = 4*B, s11 = iterations (>= 1), s20..s23 = alpha, 1 - alpha, sigma, 1/rho_eq (float bits);",
-           "// s30 != 0: fast start (asmqp.prologue_fast: the block factorises; no hand-off rows) with s[24:25], s[26:27], s[28:29] =",
-           "// the caller's x, y, z rows; min |d_k| of the factorisation -> LDS word %d;" % asmqp.FAC_MIN,
-           "// s31 / s34 / s35 = rho, 1/rho, rho_eq (float bits): rho of a row is selected from its streamed 1/rho",
-           "#define BQP_%s_ASM%s(voff, ldsaddr, lane4, ws, sblk, stride, iters, alpha, oma, sigma, rinveq, xi, yi, zi, fast, rho0, rinv0, rhoeq) asm volatile( \\" % (name.upper(), "_LOOSE" if loose else "")]
-    for t_ in ins:
-        out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[4:5]}"(ws), "{s[6:7]}"(sblk), "{s10}"(stride), '
-               '"{s11}"(iters), "{s20}"(alpha), "{s21}"(oma), "{s22}"(sigma), "{s23}"(rinveq), "{s[24:25]}"(xi), "{s[26:27]}"(yi), '
-               '"{s[28:29]}"(zi), "{s30}"(fast), "{s31}"(rho0), "{s34}"(rinv0), "{s35}"(rhoeq) \\')
-    out.append("  : " + ", ".join(clob) + ")")
-    return "\n".join(out) + "\n"
+        head = ["// The %s variant SHARED by the workgroup's wavefronts (asmqp.loop_group_program / LoopSplit): the QP's connected" % ("LOOSE" if loose else "GENERAL"),
+                "// components are independent QPs, dealt out to the wavefronts (%s of %d variables, %s of %d KKT unknowns); they meet at"
+                % (" + ".join(map(str, nv)), len(group.varw), " + ".join(map(str, nk_)), len(group.kw)),
+                "// %d barriers, none inside the loop; same LDS layout, disjoint words, bit-identical"
+                % (sum(t_[0] == "s_barrier" for t_ in ins) // group.nw),
+                "// words. s%d = the wavefront's index; the other inputs as BQP_%s_ASM_LOOSE. %d instructions."
+                % (asmqp.S_LWAVE, name.upper(), len(ins))]
+    else:
+        head = ["// GENERATED by robobee3d_amd/asmqp.py via codegen_qp.py -- do not edit.", asmgen.switch_banner(),
+                "// %s ADMM iterations of the %s structure, fp32, one lane per robot, one wave per CU: %d instructions, %d"
+                % ("LOOSE variant (every inequality row a loose row: nothing streamed per row, no clipping) of the" if loose else "Middle",
+                   name, len(ins), sum(1 for t_ in ins[asmtext.label_index(ins, "7"):] if t_[0] != "label")),
+                "// from the loop label on (loop body + epilogue). Stream block: %d items per iteration + %d loaded once."
+                % (plan.n_stream, len(plan.extra))] + ([] if loose else [
+                "#pragma once",
+                "constexpr int BQP_%s_ASM_STREAM_ITEMS = %d, BQP_%s_ASM_ROWS = %d;" % (name.upper(), plan.n_stream + len(plan.extra),
+                                                                               name.upper(), plan.R_END)]) + [
+                "// inputs: v0 = 4*robot, v1 = lane LDS address, v4 = 4*lane, s[4:5] = row workspace, s[6:7] = the wave's stream",
+                "// block, s10 = 4*B, s11 = iterations (>= 1), s20..s23 = alpha, 1 - alpha, sigma, 1/rho_eq (float bits);",
+                "// s30 != 0: fast start (asmqp.prologue_fast: the block factorises; no hand-off rows) with s[24:25], s[26:27], s[28:29] =",
+                "// the caller's x, y, z rows; min |d_k| of the factorisation -> LDS word %d;" % asmqp.FAC_MIN,
+                "// s31 / s34 / s35 = rho, 1/rho, rho_eq (float bits): rho of a row is selected from its streamed 1/rho"]
+    shared = group is not None
+    used_s = [asmqp.S_P, asmqp.S_P + 1, asmqp.S_CNT, asmqp.S_SP, asmqp.S_SP + 1] + \
+             ([asmqp.S_RIMIN, asmqp.S_RHOMIN, asmqp.S_DLEAF] if loose or shared else [])
+    return asmtext.asm_block(
+        head, "BQP_%s_ASM%s%s(voff, ldsaddr, lane4, ws, sblk, stride, iters, alpha, oma, sigma, rinveq, xi, yi, zi, fast, rho0, rinv0, rhoeq%s)"
+        % (name.upper(), "_LOOSE" if loose else "", "4" if shared else "", ", wave" if shared else ""), ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[4:5]}"(ws), "{s[6:7]}"(sblk), "{s10}"(stride), '
+        '"{s11}"(iters), "{s20}"(alpha), "{s21}"(oma), "{s22}"(sigma), "{s23}"(rinveq), "{s[24:25]}"(xi), "{s[26:27]}"(yi), '
+        '"{s[28:29]}"(zi), "{s30}"(fast), "{s31}"(rho0), "{s34}"(rinv0), "{s35}"(rhoeq)%s' % (', "{s%d}"(wave)' % asmqp.S_LWAVE if shared else ""),
+        asmtext.clobbers([2, 3] + list(range(5, asmqp.V_END)), range(256), used_s, extra=_stamp_clobbers() if shared else []),
+        asmqp.fmt)
 
 
 def res_macro(name, ins, group=False):
     from . import asmqp
-    clob = ['"memory"', '"scc"', '"vcc"'] + _stamp_clobbers() + ['"v%d"' % i for i in [2, 3] + list(range(5, asmqp.V_END))] + \
-           ['"a%d"' % i for i in range(256)] + ['"s%d"' % i for i in [asmqp.S_SP, asmqp.S_SP + 1] + list(range(42, 54)) + [56, 57, 58, 59]]
-    out = ["// Residuals, strict termination test and solution stores after the loop (asmqp.res_program): %d instructions." % len(ins),
-           "// inputs: v0 = 4*robot, v1 = lane LDS address, v4 = 4*lane, s[6:7] = the wave's stream block, s10 = 4*B,",
-           "// s[24:25] .. s[36:37] = x, y, z, sol_x, sol_y, status, info rows, s38 / s39 = eps_abs / eps_rel (float bits), s40 = max_iter,",
-           "// s[54:55] = Eprev rows (E of this solve is stored there)",
-           "#define BQP_%s_RES_ASM(voff, ldsaddr, lane4, sblk, stride, xo, yo, zo, sxo, syo, sto, ino, epsa, epsr, maxit, epo) asm volatile( \\" % name.upper()]
+    head = ["// Residuals, strict termination test and solution stores after the loop (asmqp.res_program): %d instructions." % len(ins),
+            "// inputs: v0 = 4*robot, v1 = lane LDS address, v4 = 4*lane, s[6:7] = the wave's stream block, s10 = 4*B,",
+            "// s[24:25] .. s[36:37] = x, y, z, sol_x, sol_y, status, info rows, s38 / s39 = eps_abs / eps_rel (float bits), s40 = max_iter,",
+            "// s[54:55] = Eprev rows (E of this solve is stored there)"]
     if group:
-        out = ["// The residual block SHARED by the workgroup's wavefronts (asmqp.res_group_program): each a quarter of the rows (A x, the row",
-               "// norms) and a quarter of the columns (A' y, P x, q) -- every accumulation in the one-wavefront block's order --, the partial",
-               "// norms folded by wavefront 0 between two barriers; s%d = the wavefront's index. %d instructions." % (asmqp.S_XWAVE, len(ins)),
-               "#define BQP_%s_RES4_ASM(voff, ldsaddr, lane4, sblk, stride, xo, yo, zo, sxo, syo, sto, ino, epsa, epsr, maxit, epo, wave) asm volatile( \\" % name.upper()]
-    for t_ in ins:
-        out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[6:7]}"(sblk), "{s10}"(stride), "{s[24:25]}"(xo), '
-               '"{s[26:27]}"(yo), "{s[28:29]}"(zo), "{s[30:31]}"(sxo), "{s[32:33]}"(syo), "{s[34:35]}"(sto), "{s[36:37]}"(ino), '
-               '"{s38}"(epsa), "{s39}"(epsr), "{s40}"(maxit), "{s[54:55]}"(epo)%s \\' % (', "{s%d}"(wave)' % asmqp.S_XWAVE if group else ""))
-    out.append("  : " + ", ".join(clob) + ")")
-    return "\n".join(out) + "\n"
+        head = ["// The residual block SHARED by the workgroup's wavefronts (asmqp.res_group_program): each a quarter of the rows (A x, the row",
+                "// norms) and a quarter of the columns (A' y, P x, q) -- every accumulation in the one-wavefront block's order --, the partial",
+                "// norms folded by wavefront 0 between two barriers; s%d = the wavefront's index. %d instructions." % (asmqp.S_XWAVE, len(ins))]
+    return asmtext.asm_block(
+        head, "BQP_%s_RES%s_ASM(voff, ldsaddr, lane4, sblk, stride, xo, yo, zo, sxo, syo, sto, ino, epsa, epsr, maxit, epo%s)"
+        % (name.upper(), "4" if group else "", ", wave" if group else ""), ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{v4}"(lane4), "{s[6:7]}"(sblk), "{s10}"(stride), "{s[24:25]}"(xo), '
+        '"{s[26:27]}"(yo), "{s[28:29]}"(zo), "{s[30:31]}"(sxo), "{s[32:33]}"(syo), "{s[34:35]}"(sto), "{s[36:37]}"(ino), '
+        '"{s38}"(epsa), "{s39}"(epsr), "{s40}"(maxit), "{s[54:55]}"(epo)%s' % (', "{s%d}"(wave)' % asmqp.S_XWAVE if group else ""),
+        asmtext.clobbers([2, 3] + list(range(5, asmqp.V_END)), range(256),
+                         [asmqp.S_SP, asmqp.S_SP + 1] + list(range(42, 54)) + [56, 57, 58, 59], extra=_stamp_clobbers()),
+        asmqp.fmt)
 
 
 def ruiz_macro(name, ins, rp, rs=False, group=False):
+    """rs: the passes also write the residual stream (two more inputs: v<V_RLANE> = 4*lane, which the block then keeps, and the
+    stream block); group: that block shared by the workgroup's wavefronts (one more input, the wavefront's index)"""
     from . import asmqp
+    rs = rs or group
     if group:
-        clob = ['"memory"', '"scc"', '"vcc"'] + _stamp_clobbers() + ['"v%d"' % i for i in range(2, asmqp.V_END) if i != asmqp.V_RLANE] + \
-               ['"a%d"' % i for i in range(256)] + \
-               ['"s%d"' % i for i in (asmqp.S_P, asmqp.S_P + 1, asmqp.S_CNT, asmqp.S_RMIN, asmqp.S_RMAX)]
-        nbar = sum(t_[0] == "s_barrier" for t_ in ins)
-        out = ["// The passes and the residual stream as above, SHARED by the %d wavefronts of a workgroup that own the same 64 robots"
-               % ASM_GROUP_WAVES,
-               "// (asmqp.ruiz_group_program / RuizSplit: each wavefront takes a stretch of the columns; two s_barrier per pass; s26 = the",
-               "// wavefront's index). %d instructions in %d sections; every word left in LDS and in the stream is bit-identical to the"
-               % (len(ins), ASM_GROUP_WAVES),
-               "// one-wavefront block's. Ends behind a barrier: whichever wavefront continues sees all of it.",
-               "#define BQP_%s_RUIZ_RS4_ASM(voff, ldsaddr, lane4, av, pv, qv, sblk, stride, passes, wave) asm volatile( \\" % name.upper()]
-        assert nbar % ASM_GROUP_WAVES == 0
-        for t_ in ins:
-            out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-        out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{v%d}"(lane4), "{s[4:5]}"(av), "{s[6:7]}"(pv), "{s[8:9]}"(qv), '
-                   '"{s[24:25]}"(sblk), "{s10}"(stride), "{s11}"(passes), "{s%d}"(wave) \\' % (asmqp.V_RLANE, asmqp.S_RWAVE))
-        out.append("  : " + ", ".join(clob) + ")")
-        return "\n".join(out) + "\n"
-    clob = ['"memory"', '"scc"', '"vcc"'] + _stamp_clobbers() + ['"v%d"' % i for i in range(2, asmqp.V_END) if not (rs and i == asmqp.V_RLANE)] + \
-           ['"a%d"' % i for i in range(256)] + \
-           ['"s%d"' % i for i in (asmqp.S_P, asmqp.S_P + 1, asmqp.S_CNT, asmqp.S_RMIN, asmqp.S_RMAX)]
-    if rs:
-        lab7 = [k for k, t_ in enumerate(ins) if t_ == ("label", "7")][0]
-        out = ["// The same passes, and the equilibrated A, E, D, q, P, c written to the wave's residual stream (s[24:25], v%d = 4*lane)." % asmqp.V_RLANE,
-               "#define BQP_%s_RUIZ_RS_ASM(voff, ldsaddr, lane4, av, pv, qv, sblk, stride, passes) asm volatile( \\" % name.upper()]
-        for t_ in ins:
-            out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-        out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{v%d}"(lane4), "{s[4:5]}"(av), "{s[6:7]}"(pv), "{s[8:9]}"(qv), '
-                   '"{s[24:25]}"(sblk), "{s10}"(stride), "{s11}"(passes) \\' % asmqp.V_RLANE)
-        out.append("  : " + ", ".join(clob) + ")")
-        return "\n".join(out) + "\n"
-    lab7 = [k for k, t_ in enumerate(ins) if t_ == ("label", "7")][0]
-    br = [k for k, t_ in enumerate(ins) if t_[0] == "s_cbranch_scc1"][0]
-    out = ["// The Ruiz passes of the %s structure (asmqp.ruiz_program), fp32: %d instructions, %d per pass." % (name, len(ins), br - lab7),
-           "// inputs: v0 = 4*robot, v1 = lane LDS address, s[4:5] = Av rows, s[6:7] = Pv rows, s[8:9] = q rows, s10 = 4*B, s11 = passes >= 1",
-           "#define BQP_%s_RUIZ_ASM(voff, ldsaddr, av, pv, qv, stride, passes) asm volatile( \\" % name.upper()]
-    for t_ in ins:
-        out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(av), "{s[6:7]}"(pv), "{s[8:9]}"(qv), "{s10}"(stride), "{s11}"(passes) \\')
-    out.append("  : " + ", ".join(clob) + ")")
-    return "\n".join(out) + "\n"
+        assert sum(t_[0] == "s_barrier" for t_ in ins) % ASM_GROUP_WAVES == 0
+        head = ["// The passes and the residual stream as above, SHARED by the %d wavefronts of a workgroup that own the same 64 robots"
+                % ASM_GROUP_WAVES,
+                "// (asmqp.ruiz_group_program / RuizSplit: each wavefront takes a stretch of the columns; two s_barrier per pass; s26 = the",
+                "// wavefront's index). %d instructions in %d sections; every word left in LDS and in the stream is bit-identical to the"
+                % (len(ins), ASM_GROUP_WAVES),
+                "// one-wavefront block's. Ends behind a barrier: whichever wavefront continues sees all of it."]
+    elif rs:
+        head = ["// The same passes, and the equilibrated A, E, D, q, P, c written to the wave's residual stream (s[24:25], v%d = 4*lane)." % asmqp.V_RLANE]
+    else:
+        br = [k for k, t_ in enumerate(ins) if t_[0] == "s_cbranch_scc1"][0]
+        head = ["// The Ruiz passes of the %s structure (asmqp.ruiz_program), fp32: %d instructions, %d per pass."
+                % (name, len(ins), br - asmtext.label_index(ins, "7")),
+                "// inputs: v0 = 4*robot, v1 = lane LDS address, s[4:5] = Av rows, s[6:7] = Pv rows, s[8:9] = q rows, s10 = 4*B, s11 = passes >= 1"]
+    return asmtext.asm_block(
+        head, "BQP_%s_RUIZ%s_ASM(voff, ldsaddr, %sav, pv, qv, %sstride, passes%s)"
+        % (name.upper(), ("_RS4" if group else "_RS") if rs else "", "lane4, " if rs else "", "sblk, " if rs else "", ", wave" if group else ""),
+        ins,
+        '"{v0}"(voff), "{v1}"(ldsaddr), %s"{s[4:5]}"(av), "{s[6:7]}"(pv), "{s[8:9]}"(qv), %s"{s10}"(stride), "{s11}"(passes)%s'
+        % ('"{v%d}"(lane4), ' % asmqp.V_RLANE if rs else "", '"{s[24:25]}"(sblk), ' if rs else "",
+           ', "{s%d}"(wave)' % asmqp.S_RWAVE if group else ""),
+        asmtext.clobbers([i for i in range(2, asmqp.V_END) if not (rs and i == asmqp.V_RLANE)], range(256),
+                         (asmqp.S_P, asmqp.S_P + 1, asmqp.S_CNT, asmqp.S_RMIN, asmqp.S_RMAX), extra=_stamp_clobbers()),
+        asmqp.fmt)
 
 
 def loader_macro(name, tag, groups):
     from . import asmqp
-    ins = asmqp.loader_program(groups)
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"v%d"' % i for i in range(2, asmqp.V_END)] + \
-           ['"s%d"' % i for i in (asmqp.S_P, asmqp.S_P + 1)]
-    out = ["// Batched loader (asmqp.loader_program): rows %s of the arrays at s[4:5], s[6:7], s[8:9] -> LDS words, one round trip"
-           % ", ".join("%d -> %d.." % g for g in groups),
-           "#define BQP_%s_LOAD_%s(voff, ldsaddr, p0, p1, p2, stride) asm volatile( \\" % (name.upper(), tag)]
-    for t_ in ins:
-        out.append('  "%s\\n" \\' % asmqp.fmt(t_))
-    out.append('  : : "{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(p0), "{s[6:7]}"(p1), "{s[8:9]}"(p2), "{s10}"(stride) \\')
-    out.append("  : " + ", ".join(clob) + ")")
-    return "\n".join(out) + "\n"
+    return asmtext.asm_block(
+        ["// Batched loader (asmqp.loader_program): rows %s of the arrays at s[4:5], s[6:7], s[8:9] -> LDS words, one round trip"
+         % ", ".join("%d -> %d.." % g for g in groups)],
+        "BQP_%s_LOAD_%s(voff, ldsaddr, p0, p1, p2, stride)" % (name.upper(), tag), asmqp.loader_program(groups),
+        '"{v0}"(voff), "{v1}"(ldsaddr), "{s[4:5]}"(p0), "{s[6:7]}"(p1), "{s[8:9]}"(p2), "{s10}"(stride)',
+        asmtext.clobbers(range(2, asmqp.V_END), s=(asmqp.S_P, asmqp.S_P + 1)), asmqp.fmt)
 
 
 def generate():
@@ -799,11 +765,7 @@ def write():
     os.makedirs(os.path.join(csrc, "gen"), exist_ok=True)
     files = generate()
     for rel, src in files.items():
-        path = os.path.join(csrc, rel)
-        old = open(path).read() if os.path.exists(path) else None
-        if old != src:
-            with open(path, "w") as f:
-                f.write(src)
+        asmtext.write_if_changed(os.path.join(csrc, rel), src)
     keep = {os.path.basename(r) for r in files if r.startswith("gen/")}
     for fn in os.listdir(os.path.join(csrc, "gen")):
         if fn not in keep:
