@@ -135,7 +135,7 @@ def build(force=False, verbose=False):
     # root being built, so the variable cannot unlock the tree it was not meant for; tools/build_qp_variant.sh)
     if sw and os.environ.get("UMPC_VARIANT_ROOT") != ROOT:
         # build() REWRITES the tracked generated headers and the shipped .so: a stray A/B switch in a test, bench or
-        # profile shell must not change the kernels silently (one of them, UMPC_ASM_LIMIT_FAST, changes the numerics).
+        # profile shell must not change the kernels silently (UMPC_QP_NT_KINDS, for one, changes the cache policy of a stream).
         # Variants are built by tools/build_variant.py into robobee3d_amd/variants/ and selected with UMPC_LIB.
         raise RuntimeError("generator switches are set in the environment (%s): refusing to regenerate the shipped kernels; "
                            "unset them, or build a variant with tools/build_variant.py" % " ".join("%s=%s" % kv for kv in sw.items()))

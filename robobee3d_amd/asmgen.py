@@ -36,6 +36,7 @@ qdldl_interface.c:322-369, qdldl.c:250-293, proj.c:4-14.
 the CPU test-suite can check the schedule (register reuse, fetch distances,
 packed-operand selects) against the oracle without a GPU.
 """
+import collections
 import functools
 import os
 import struct
@@ -44,13 +45,17 @@ from . import asmtext, symbolic
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
-# Generation-time switches are read from the environment when the generator modules are imported (A/B timing of kernel
-# variants, tools/build_variant.py). Everything that matches these prefixes changes the emitted instruction streams;
-# the names below it are RUN-time diagnostics of the host side and do not.
+# Generation-time switches are read from the environment when the generators run (diagnostic builds, tools/build_variant.py).
+# Everything that matches these prefixes counts as one: build() refuses to regenerate the shipped kernels under it. SWITCHES
+# are the ones the generators read -- stamps and phase timers of the diagnostic builds, and the cache policy of the QP
+# stream (DESIGN.md has the table); the A/B experiments of rounds 2-5 are decided and gone. NOT_SWITCHES are RUN-time
+# variables of the host side that happen to match a prefix.
 SWITCH_PREFIXES = ("UMPC_ASM_", "UMPC_ASM64_", "UMPC_QP_", "UMPC_X_")
+SWITCHES = ("UMPC_ASM64_TIMING", "UMPC_QP_TIMING", "UMPC_QP_RES_STAMPS", "UMPC_QP_RUIZ_STAMPS", "UMPC_QP_LOOP_STAMPS",
+            "UMPC_QP_NT", "UMPC_QP_NT_KINDS")
 # RUN-time variables that happen to match a prefix (read with getenv() by the host code in csrc/, or by batchqp.py, when a
 # kernel is launched; they select among kernels that exist, they do not change an emitted stream).
-# tests/test_generated_headers.py greps csrc/ and keeps this list honest.
+# tests/test_generated_headers.py greps csrc/ and the generators and keeps both lists honest.
 NOT_SWITCHES = ("UMPC_QP_KERNEL", "UMPC_QP_NO_ASM", "UMPC_ASM_SKEW_US", "UMPC_ASM_SKEW_GROUPS")
 
 
@@ -64,7 +69,6 @@ def switch_banner():
     sw = generator_switches()
     return "// generator switches: " + (" ".join("%s=%s" % kv for kv in sw.items()) if sw else "none (defaults = the shipped kernels)")
 
-XV_COUNT, XV_BASE = 0, 246   # asmstep.py: storage positions NLDS+NVZ .. +XV_COUNT-1 of L live in VGPRs XV_BASE.. (free there)
 NLDS = 160  # L storage positions kept in LDS
 NVZ = 36    # positions NLDS .. NLDS+NVZ-1 move into the z registers of the dynamics rows after the first iteration
 # workspace rows shared with the C++ phases (see umpc_step.h)
@@ -76,9 +80,14 @@ WS_ROWS = 559
 V_W, V_WZ, V_X, V_Y, V_Z = 2, 48, 88, 134, 174
 V_RING, V_AT, V_TT, V_END = 214, 230, 238, 246
 N_ATP = 4  # AGPR-read temporaries, in pairs
-# LDS ring slots of the Fetcher. EXPERIMENT (asmstep.py, UMPC_ASM_RING=6 together with UMPC_ASM_XV=0): two more slots in
-# v246..v253 instead of ten L words there; set by asmstep for its own stream only (module state, like XV_COUNT)
-NRING = 4
+# What a stream keeps beyond the loop's fixed layout: nring slots of the Fetcher's LDS read ring (four in v214..v229, a fifth
+# and sixth in v246..v253: ring_base), and the storage positions NLDS+NVZ .. +xv_count-1 of L in VGPRs xv_base.. . The
+# defaults are the stream of the C++ step kernel (program()); asmstep.py passes its own for its own stream.
+Homes = collections.namedtuple("Homes", "nring xv_count xv_base", defaults=(4, 0, 246))
+# by ring size: (ops between a ds_read and its first consumer, later reads one wait also covers if they are already issued).
+# Measured on the MI355X (profiles/README.md, K = 500, ms per step). Four slots: look-ahead 8 0.1252, 12 0.1220, 16 / 20 /
+# 24 the same; merge 0 0.1234, 1 0.1222, 2 0.1331, 3 0.1383. Six slots: 12 / 1 0.1220, 20 / 2 0.1204, merge 3 0.1223, 4 0.1270.
+LDS_AHEAD_MERGE = {4: (12, 1), 6: (20, 2)}
 
 
 def ring_base(slot):
@@ -208,15 +217,7 @@ def w_reg(s, k, xs, zs):
     return V_W + xs[o] if o < s.nx else V_WZ + zs[o - s.nx]
 
 
-# EXPERIMENT, off by default (UMPC_ASM_BCAST=1): broadcast-source pairs in the solves -- two entries of one column whose rows
-# are slot partners (forwards), two entries of one row whose columns are (backwards) as ONE packed instruction with the
-# source broadcast: 150 -> 140 / 141 instructions per solve, 778 -> 759 per iteration. Measured on the MI355X (same box,
-# K = 500): 0.12145 / 0.12175 ms per step against 0.1220 / 0.1224 -- 0.4 % for 2.4 % fewer instructions (the packed ops
-# lengthen dependent chains), and it moves the rounding of every iterate. Not shipped.
-BCAST = os.environ.get("UMPC_ASM_BCAST", "0") == "1"
-
-
-def solve_schedule(s, reg, direction, allowed=None, same_src=False):
+def solve_schedule(s, reg, direction, allowed=None):
     """List-schedules one triangular solve. Ops are the L entries j = (row r, column c): forward W[r] -= L_j W[c]
     (ready once W[c] is final), backward W[c] -= L_j W[r] (ready once W[r] is final). Two ready ops whose destination
     registers AND source registers each form an aligned pair are issued as one packed instruction; an op whose
@@ -229,10 +230,8 @@ def solve_schedule(s, reg, direction, allowed=None, same_src=False):
         ops = [(c, r, j) for (r, c, j) in ops]
 
     def ok(o, o2):
-        # partner destinations; partner sources, or (same_src) ONE source broadcast to both halves: two entries of one
-        # column whose rows are slot partners
-        return (o2[2] != o[2] and reg[o2[0]] == (reg[o[0]] ^ 1)
-                and (reg[o2[1]] == (reg[o[1]] ^ 1) or (same_src and o2[1] == o[1]))
+        # partner destinations and partner sources
+        return (o2[2] != o[2] and reg[o2[0]] == (reg[o[0]] ^ 1) and reg[o2[1]] == (reg[o[1]] ^ 1)
                 and (allowed is None or frozenset((o[2], o2[2])) in allowed))
     indeg = {k: 0 for k in range(nk)}
     for (d, _, _) in ops:
@@ -278,73 +277,19 @@ def solve_plan(s):
     even position (an LDS float4 holds two pairs; an AGPR pair is fetched with two v_accvgpr_read)."""
     xs, zs, _, _ = slot_maps(s)
     reg = [w_reg(s, k, xs, zs) for k in range(s.nk)]
-    fwd = solve_schedule(s, reg, "fwd", same_src=BCAST)
-    # Broadcast couples for the BACKWARD solve: two forward singles (r <- c), (r <- c') into the same unknown r whose
-    # columns c, c' are slot partners become, backwards, (c <- r), (c' <- r): partner destinations, one source -- one
-    # packed instruction with the source broadcast, if their L entries are an aligned pair in storage. The earlier of the
-    # two forward ops is moved next to the later one (legal: W[r] is read by nobody before all its updates are done, and
-    # the source of the delayed op stays final), so the storage order below makes them adjacent.
-    couples, late = {}, {}
-    if BCAST:
-        singles = [(k, g[0]) for k, g in enumerate(fwd) if len(g) == 1]
-        used = set()
-        for a_, (ka, oa) in enumerate(singles):
-            if oa[2] in used:
-                continue
-            for kb, ob in singles[a_ + 1:]:
-                if ob[2] not in used and ob[0] == oa[0] and reg[ob[1]] == (reg[oa[1]] ^ 1):
-                    couples[oa[2]] = ob[2]
-                    used.update((oa[2], ob[2]))
-                    break
-        moved = {j for j in couples}                    # the earlier op of every couple leaves its place ...
-        late = {jb: ja for ja, jb in couples.items()}   # ... and is re-inserted right before its partner
-        byj = {g[0][2]: g for g in fwd if len(g) == 1}
-        out = []
-        for g in fwd:
-            if len(g) == 1 and g[0][2] in moved:
-                continue
-            if len(g) == 1 and g[0][2] in late:
-                out.append(byj[late[g[0][2]]])
-            out.append(g)
-        fwd = out
+    fwd = solve_schedule(s, reg, "fwd")
     # The reversed forward order with the roles of row and column swapped is a legal backward order (an entry of
     # column r follows every entry of row r in the forward solve) with the same pairs, and it walks the storage
-    # backwards: each LDS float4 is fetched once per solve. A forward pair with ONE source (two rows of a column) has ONE
-    # destination backwards: two singles there; a couple is two singles forwards and one pair backwards.
+    # backwards: each LDS float4 is fetched once per solve.
     bwd = []
-    k = len(fwd) - 1
-    while k >= 0:
-        g = fwd[k]
-        if len(g) == 1 and g[0][2] in late:                         # (its partner is fwd[k - 1])
-            ob, oa = g[0], fwd[k - 1][0]
-            h = [(oa[1], oa[0], oa[2]), (ob[1], ob[0], ob[2])]      # (dst c, src r, j), (dst c', src r, j')
-            if reg[h[0][0]] % 2:
-                h.reverse()
-            bwd.append(tuple(h))
-            k -= 2
-            continue
+    for g in reversed(fwd):
         h = [(sr, d, j) for (d, sr, j) in g]
-        if len(h) == 2 and h[0][0] == h[1][0]:                      # one destination: not a pair in this direction
-            bwd.append((h[1],))
-            bwd.append((h[0],))
-        else:
-            if len(h) == 2 and reg[h[0][0]] % 2:
-                h.reverse()
-            bwd.append(tuple(h))
-        k -= 1
-    # storage: in order of first use by the forward solve; pairs and couples adjacent on an even position
-    units = []
-    k = 0
-    while k < len(fwd):
-        g = fwd[k]
-        if len(g) == 1 and g[0][2] in couples and k + 1 < len(fwd) and len(fwd[k + 1]) == 1 and fwd[k + 1][0][2] == couples[g[0][2]]:
-            units.append([g[0][2], fwd[k + 1][0][2]])
-            k += 2
-        else:
-            units.append([o[2] for o in g])
-            k += 1
+        if len(h) == 2 and reg[h[0][0]] % 2:
+            h.reverse()
+        bwd.append(tuple(h))
+    # storage: in order of first use by the forward solve; pairs adjacent on an even position
     order, pending = [], []
-    for u in units:
+    for u in ([o[2] for o in g] for g in fwd):
         if len(u) == 2 and len(order) % 2:
             pending.append(u)      # wait for a single to restore the parity
             continue
@@ -417,17 +362,16 @@ class Fetcher:
     """Issues the L / 1-over-D / q operand fetches a fixed distance ahead of their consumers.
     src: None | ('A', a) -> one VGPR | ('A2', a_lo, a_hi) -> an aligned VGPR pair | ('L', lds_word)."""
 
-    def __init__(self, e, la=3):
-        self.e, self.la = e, la
+    def __init__(self, e, la=3, nring=4):
+        self.e, self.la, self.nring = e, la, nring
         self.nds = 0          # ds_reads issued so far in this body
         self.waited = -1      # issue index of the last ds_read known to have returned
-        self.lds_ahead = int(os.environ.get("UMPC_ASM_LDS_AHEAD", "12" if NRING == 4 else "20"))  # ops between a ds_read and its first consumer
-        self.merge = int(os.environ.get("UMPC_ASM_LDS_MERGE", "1" if NRING == 4 else "2"))   # also wait for this many later reads if they are already issued
+        self.lds_ahead, self.merge = LDS_AHEAD_MERGE[nring]
 
     def run(self, ops):
-        e = self.e
+        e, NRING = self.e, self.nring
         n = len(ops)
-        # LDS instances: a quad stays resident in one of the 4 ring slots until it is the least recently used
+        # LDS instances: a quad stays resident in one of the ring slots until it is the least recently used
         # one when another quad needs a slot (the backward solve revisits quads that straddle two rows)
         inst_of = [None] * n
         insts = []  # dict(quad, first, last, slot, prev, issued)
@@ -521,40 +465,14 @@ def pk(e, mnem, dst, srcs, neg=None):
     e(mnem, "v[%d:%d]" % (dst, dst + 1), *[s_[0] for s_ in srcs], mods)
 
 
-def despace(ops, window=int(os.environ.get("UMPC_ASM_WINDOW", "12"))):
-    """EXPERIMENT, off by default (UMPC_ASM_DESPACE=1): reorders the op list so that an instruction does not read what
-    the previous one (or the one before) wrote (back-to-back dependencies 124 -> 32 per iteration). Measured on the
-    MI355X it is SLOWER (0.182 vs 0.176 ms per step): in the real loop the dependent-issue penalty seen in
-    tools/microbench.hip is hidden behind the AGPR / LDS operand fetches, and the reordering costs fetch locality.
-    Greedy, register-exact: an op may move ahead of earlier ops it has no RAW / WAR / WAW
-    relation with, inside a window; among the movable ones the first that is independent of the last two issued wins."""
-    pending, out = list(ops), []
-    last = [frozenset(), frozenset()]   # registers written by the previous two issued ops
-    while pending:
-        best, bscore = 0, None
-        blocked_w, blocked_r = set(), set()   # written / read by the earlier, still pending ops
-        for k, o in enumerate(pending[:window]):
-            movable = not (o["r"] & blocked_w) and not (o["w"] & blocked_w) and not (o["w"] & blocked_r)
-            if movable:
-                score = (2 if (o["r"] | o["w"]) & last[1] else 0) + (1 if (o["r"] | o["w"]) & last[0] else 0)
-                if bscore is None or score < bscore:
-                    best, bscore = k, score
-                    if score == 0:
-                        break
-            blocked_w |= o["w"]
-            blocked_r |= o["r"]
-        o = pending.pop(best)
-        out.append(o)
-        last = [last[1], o["w"]]
-    return out
-
-
-def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset(), lzero=frozenset(), dy3_in_w=False):
+def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset(), lzero=frozenset(), dy3_in_w=False,
+         homes=Homes()):
     """delta_in_w (asmstep.py, the all-assembly step kernel): a capturing iteration leaves delta_x = x - x_prev in
     the x part of W and delta_y in the z part of W (registers) instead of writing x_prev / delta_y to the workspace.
     qzero / lzero: x indices whose q and dynamics rows whose l (= u) are STRUCTURALLY zero for this QP (asmstep.Struct:
     q is non-zero only on the y and dp entries, l on rows 0..5, 18..26 and 32): their right-hand side is sigma x /
-    -y / rho without the AGPR read (8.6 cycles each for a lone wave) -- 35 of an iteration's 214 reads."""
+    -y / rho without the AGPR read (8.6 cycles each for a lone wave) -- 35 of an iteration's 214 reads.
+    homes: the ring slots and the extra VGPR homes of L of this stream (Homes)."""
     nx, nc, nk = s.nx, s.nc, s.nk
     neq = 2 * s.N * symbolic.NY
     xs, zs, xinv, zinv = slot_maps(s)
@@ -574,12 +492,11 @@ def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset
     v = lambda n: "v%d" % n
     sA, sO, sS, sRi, sRh = ("s%d" % r for r in (S_ALPHA, S_OMA, S_SIGMA, S_RINV, S_RHO))
     ptr = "s[%d:%d]" % (S_P2, S_P2 + 1)
-    f = Fetcher(e)
+    f = Fetcher(e, nring=homes.nring)
     ops = []
 
-    def op(src, fn, w=(), r=()):
-        """w / r: the VGPRs this op writes / reads besides its fetched operand (for despace())."""
-        ops.append(dict(src=src, emit=fn, w=frozenset(w), r=frozenset(r)))
+    def op(src, fn):
+        ops.append(dict(src=src, emit=fn))
 
     assert NVZ == neq and not (lv and first)
 
@@ -588,8 +505,8 @@ def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset
             return ("L", lpos[j])
         if lv and lpos[j] < NLDS + NVZ:   # resident in the z registers of the dynamics rows (z == l there, kept in AGPRs)
             return ("V", V_Z + lpos[j] - NLDS)
-        if NLDS + NVZ <= lpos[j] < NLDS + NVZ + XV_COUNT:
-            return ("V", XV_BASE + lpos[j] - NLDS - NVZ)
+        if NLDS + NVZ <= lpos[j] < NLDS + NVZ + homes.xv_count:
+            return ("V", homes.xv_base + lpos[j] - NLDS - NVZ)
         return ("A", A_L + lpos[j] - NLDS)
 
     if capture and not delta_in_w:  # x_prev of this iteration -> workspace
@@ -600,48 +517,44 @@ def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset
     # ---- rhs: W = [sigma x - q ; z - y / rho]  (auxil.c:164-178), two slots per instruction
     for p_ in range(0, nx - 1, 2):
         j0, j1 = xinv[p_], xinv[p_ + 1]
-        rw = dict(w=(V_W + p_, V_W + p_ + 1), r=(V_X + p_, V_X + p_ + 1))
         if j0 in qzero and j1 in qzero:
-            op(None, lambda t, p_=p_: pk(e, "v_pk_mul_f32", V_W + p_, [_sb(S_SIGMA), _vp(V_X + p_)]), **rw)
+            op(None, lambda t, p_=p_: pk(e, "v_pk_mul_f32", V_W + p_, [_sb(S_SIGMA), _vp(V_X + p_)]))
         elif j0 in qzero or j1 in qzero:
             jn, h = (j1, 1) if j0 in qzero else (j0, 0)
 
             def mixed(t, p_=p_, h=h):
                 pk(e, "v_pk_mul_f32", V_W + p_, [_sb(S_SIGMA), _vp(V_X + p_)])
                 e("v_sub_f32", v(V_W + p_ + h), v(V_W + p_ + h), v(t))
-            op(("A", A_Q + jn), mixed, **rw)
+            op(("A", A_Q + jn), mixed)
         else:
             op(("A2", A_Q + j0, A_Q + j1),
-               lambda t, p_=p_: pk(e, "v_pk_fma_f32", V_W + p_, [_sb(S_SIGMA), _vp(V_X + p_), _vp(t)], [0, 0, 1]), **rw)
+               lambda t, p_=p_: pk(e, "v_pk_fma_f32", V_W + p_, [_sb(S_SIGMA), _vp(V_X + p_), _vp(t)], [0, 0, 1]))
     if nx % 2:
         jl = xinv[nx - 1]
         if jl in qzero:
-            op(None, lambda t, jl=jl: e("v_mul_f32", v(WX(jl)), sS, X(jl)), w=(WX(jl),), r=(XR(jl),))
+            op(None, lambda t, jl=jl: e("v_mul_f32", v(WX(jl)), sS, X(jl)))
         else:
-            op(("A", A_Q + jl), lambda t, jl=jl: e("v_fma_f32", v(WX(jl)), sS, X(jl), "-" + v(t)), w=(WX(jl),), r=(XR(jl),))
+            op(("A", A_Q + jl), lambda t, jl=jl: e("v_fma_f32", v(WX(jl)), sS, X(jl), "-" + v(t)))
     assert all(zinv[p_] < neq for p_ in range(neq)) and neq % 2 == 0
     for p_ in range(0, neq, 2):
         if lv:   # z of the dynamics rows is l (== u): read it from its AGPR home
             i0, i1 = zinv[p_], zinv[p_ + 1]
-            rw = dict(w=(V_WZ + p_, V_WZ + p_ + 1), r=(V_Y + p_, V_Y + p_ + 1))
             if i0 in lzero and i1 in lzero:
-                op(None, lambda t, p_=p_: pk(e, "v_pk_mul_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_)], [1, 0]), **rw)
+                op(None, lambda t, p_=p_: pk(e, "v_pk_mul_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_)], [1, 0]))
             elif i0 in lzero or i1 in lzero:
                 inz, h = (i1, 1) if i0 in lzero else (i0, 0)
 
                 def mixed_z(t, p_=p_, h=h):
                     pk(e, "v_pk_mul_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_)], [1, 0])
                     e("v_add_f32", v(V_WZ + p_ + h), v(V_WZ + p_ + h), v(t))
-                op(("A", A_LO + inz), mixed_z, **rw)
+                op(("A", A_LO + inz), mixed_z)
             else:
                 op(("A2", A_LO + i0, A_LO + i1),
-                   lambda t, p_=p_: pk(e, "v_pk_fma_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_), _vp(t)], [1, 0, 0]), **rw)
+                   lambda t, p_=p_: pk(e, "v_pk_fma_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_), _vp(t)], [1, 0, 0]))
         else:
-            op(None, lambda t, p_=p_: pk(e, "v_pk_fma_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_), _vp(V_Z + p_)], [1, 0, 0]),
-               w=(V_WZ + p_, V_WZ + p_ + 1), r=(V_Y + p_, V_Y + p_ + 1, V_Z + p_, V_Z + p_ + 1))
+            op(None, lambda t, p_=p_: pk(e, "v_pk_fma_f32", V_WZ + p_, [_sb(S_RINV), _vp(V_Y + p_), _vp(V_Z + p_)], [1, 0, 0]))
     for i in range(neq, nc):
-        op(("A", A_M + 9 + i - neq), lambda t, i=i: e("v_fma_f32", v(WZ(i)), "-" + v(t), Y(i), Z(i)),
-           w=(WZ(i),), r=(YR(i), ZR(i)))
+        op(("A", A_M + 9 + i - neq), lambda t, i=i: e("v_fma_f32", v(WZ(i)), "-" + v(t), Y(i), Z(i)))
 
     # ---- triangular solves (qdldl.c:250-277) from the list schedule: dst -= L * src, packed where both the
     # destination and the source registers of two ready entries form aligned pairs
@@ -653,29 +566,26 @@ def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset
                 # the factor is stored NEGATED: dst += (-L) * src is the 4-byte VOP2 v_fmac_f32, which a lone wave
                 # issues every ~4.4 cycles against ~5.0 for the 8-byte VOP3 v_fma_f32 (tools/microbench.hip)
                 if src[0] == "V":
-                    op(None, lambda t, d=d, sr=sr, r=src[1]: e("v_fmac_f32", W(d), v(r), W(sr)),
-                       w=(wreg(d),), r=(wreg(d), wreg(sr)))
+                    op(None, lambda t, d=d, sr=sr, r=src[1]: e("v_fmac_f32", W(d), v(r), W(sr)))
                 else:
-                    op(src, lambda t, d=d, sr=sr: e("v_fmac_f32", W(d), v(t), W(sr)),
-                       w=(wreg(d),), r=(wreg(d), wreg(sr)))
+                    op(src, lambda t, d=d, sr=sr: e("v_fmac_f32", W(d), v(t), W(sr)))
                 continue
             (d0, s0_, j0), (d1, s1_, j1) = g          # d0 has the even destination register
             rd, r0, r1 = wreg(d0), wreg(s0_), wreg(s1_)
             assert rd % 2 == 0 and wreg(d1) == rd + 1 and r0 // 2 == r1 // 2 and lpos[j0] // 2 == lpos[j1] // 2
             srcp = ("v[%d:%d]" % (r0 - r0 % 2, r0 - r0 % 2 + 1), r0 % 2, r1 % 2)
-            rw = dict(w=(rd, rd + 1), r=(rd, rd + 1, r0, r1))
             pe = lpos[j0] - lpos[j0] % 2
             lsel = (lpos[j0] % 2, lpos[j1] % 2)
             if pe < NLDS:
                 op(("L", pe), lambda t, rd=rd, srcp=srcp, lsel=lsel:
-                   pk(e, "v_pk_fma_f32", rd, [("v[%d:%d]" % (t, t + 1), lsel[0], lsel[1]), srcp, _vp(rd)], [0, 0, 0]), **rw)
-            elif (lv and pe < NLDS + NVZ) or NLDS + NVZ <= pe < NLDS + NVZ + XV_COUNT:
-                t = V_Z + pe - NLDS if pe < NLDS + NVZ else XV_BASE + pe - NLDS - NVZ
+                   pk(e, "v_pk_fma_f32", rd, [("v[%d:%d]" % (t, t + 1), lsel[0], lsel[1]), srcp, _vp(rd)], [0, 0, 0]))
+            elif (lv and pe < NLDS + NVZ) or NLDS + NVZ <= pe < NLDS + NVZ + homes.xv_count:
+                t = V_Z + pe - NLDS if pe < NLDS + NVZ else homes.xv_base + pe - NLDS - NVZ
                 op(None, lambda _t, t=t, rd=rd, srcp=srcp, lsel=lsel:
-                   pk(e, "v_pk_fma_f32", rd, [("v[%d:%d]" % (t, t + 1), lsel[0], lsel[1]), srcp, _vp(rd)], [0, 0, 0]), **rw)
+                   pk(e, "v_pk_fma_f32", rd, [("v[%d:%d]" % (t, t + 1), lsel[0], lsel[1]), srcp, _vp(rd)], [0, 0, 0]))
             else:
                 src = ("A2", A_L + lpos[j0] - NLDS, A_L + lpos[j1] - NLDS)
-                op(src, lambda t, rd=rd, srcp=srcp: pk(e, "v_pk_fma_f32", rd, [_vp(t), srcp, _vp(rd)], [0, 0, 0]), **rw)
+                op(src, lambda t, rd=rd, srcp=srcp: pk(e, "v_pk_fma_f32", rd, [_vp(t), srcp, _vp(rd)], [0, 0, 0]))
 
     solve_ops(fwd)
     # ---- diagonal (qdldl.c:289): two unknowns per instruction, paired by register
@@ -683,13 +593,12 @@ def body(e, s, first, capture, plan, lv=False, delta_in_w=False, qzero=frozenset
     for r0 in range(V_W, V_Z, 2):
         k0, k1 = kof.get(r0), kof.get(r0 + 1)
         if k0 is not None and k1 is not None:
-            op(("A2", A_D + k0, A_D + k1), lambda t, r0=r0: pk(e, "v_pk_mul_f32", r0, [_vp(r0), _vp(t)]),
-               w=(r0, r0 + 1), r=(r0, r0 + 1))
+            op(("A2", A_D + k0, A_D + k1), lambda t, r0=r0: pk(e, "v_pk_mul_f32", r0, [_vp(r0), _vp(t)]))
         elif k0 is not None or k1 is not None:
             k, r = (k0, r0) if k0 is not None else (k1, r0 + 1)
-            op(("A", A_D + k), lambda t, r=r: e("v_mul_f32", v(r), v(t), v(r)), w=(r,), r=(r,))
+            op(("A", A_D + k), lambda t, r=r: e("v_mul_f32", v(r), v(t), v(r)))
     solve_ops(bwd)
-    f.run(despace(ops) if os.environ.get("UMPC_ASM_DESPACE", "0") == "1" else ops)
+    f.run(ops)
     # ---- x <- alpha x~ + (1 - alpha) x   (auxil.c:188-201)
     for p_ in range(0, nx - 1, 2):
         t = V_TT + 2 * ((p_ // 2) % 4)

@@ -18,10 +18,9 @@ what a 4 096-robot batch gives anyway -- 320 words of LDS. That is 576 words, an
     a168..a239    z of the dynamics rows during the FIRST iteration (afterwards z == l there)
     LDS           words 0..212 L (CSC order, written there by phase A), 213..257 x, 258..296 y;
                   word w = byte (w >> 1) * 1024 + 16 * lane + 8 * (w & 1): a ds_read_b128 returns two words
-    q, l          never stored on chip: their 81 words are global_load_dwordx2'ed (L2 hits, 8 B x 64 lanes coalesced)
-                  straight INTO the W registers they are about to be combined with -- W_x <- q right after the x update
-                  freed it, W_z <- l after the y update -- and the rhs is formed in place (W_x = sigma x - W_x).
-                  One VMEM instruction per word where an AGPR home costs two v_accvgpr_read.
+    q, l          first iteration: global_load_dwordx2'ed (L2 hits, 8 B x 64 lanes coalesced) straight INTO the W registers
+                  they are about to be combined with, the rhs formed in place (W_x = sigma x - W_x); from the second
+                  iteration on the words that can be non-zero come from AGPR homes (A_H below)
 
 Per middle iteration ~1 500 instructions (426 v_fma_f64 of the solves, 214 + 86 ds_read_b128, 168 v_accvgpr_read, 81
 global loads, 43 ds_write). Arithmetic = UMPC_GEN_ADMM_ITER of the C++ statement (csrc/umpc_gen.h) except that the
@@ -56,8 +55,7 @@ LDS_BYTES_PER_LANE = 2560
 #   a168..a253   l of the 16 dynamics rows that can be non-zero, then the 27 entries of q that can be (the z words of the
 #                first iteration are dead by then; filled at the end of the first iteration)
 A_H = 168
-HOMES = os.environ.get("UMPC_ASM64_HOMES", "1") == "1"
-FUSE = os.environ.get("UMPC_ASM64_FUSE", "1") == "1"       # the x / y updates leave the NEXT iteration's right-hand side in W
+# and the x / y updates of an iteration leave the NEXT iteration's right-hand side in W (body())
 
 
 def rhs_structure(s):
@@ -101,15 +99,18 @@ def lds_addr(word):
     return "v%d" % (1, V_B1, V_B2)[byte >> 16], byte & 0xFFFF, word & 1
 
 
+AHEAD = 14      # operations between an LDS quad read and its first consumer
+MERGE = 1       # a wait also covers this many later reads in flight
+
+
 class Fetch:
     """Issues LDS quad reads and AGPR reads ahead of the ops that consume them. An op is dict(srcs=[src...], emit=fn)
     with src = ('L', lds word) | ('A', first AGPR of the word) | ('V', first VGPR of the word); emit receives the first
     VGPR of every source word. LDS quads live in NSLOT ring slots, least recently used replaced (static analysis)."""
 
-    def __init__(self, e, ahead=None, la=2):
-        ahead = int(os.environ.get("UMPC_ASM64_AHEAD", "14")) if ahead is None else ahead
-        self.e, self.ahead, self.la = e, ahead, la
-        self.merge = int(os.environ.get("UMPC_ASM64_MERGE", "1"))     # a wait also covers this many later reads in flight
+    def __init__(self, e, la=2):
+        self.e, self.ahead, self.la = e, AHEAD, la
+        self.merge = MERGE
 
     def run(self, ops):
         e = self.e
@@ -179,80 +180,6 @@ class Fetch:
             ops[i]["emit"](regs)
 
 
-SCHED_LAT = int(os.environ.get("UMPC_ASM64_SCHED_LAT", "0"))
-SCHED_SLACK = int(os.environ.get("UMPC_ASM64_SCHED_SLACK", "2"))
-
-
-def list_schedule(ops, lat=None):
-    """Reorders the rhs / solve operations so that an operation follows the one that produced its operand by at least
-    `lat` issue slots where the dependence graph allows (one wave per SIMD: nothing else hides a dependent fp64 FMA's
-    latency). Every word keeps the order of ITS updates (read-after-write, write-after-read and write-after-write
-    edges on the W words), so each value is rounded exactly as in program order. Priority: longest latency-weighted path
-    to the end; ties in program order (= storage order of L, which keeps the two words of an LDS quad together)."""
-    lat = SCHED_LAT if lat is None else lat
-    if lat <= 0:
-        return ops
-    n = len(ops)
-    preds = [[] for _ in range(n)]      # (op, is_raw)
-    last_w, readers = {}, {}
-    for i, o in enumerate(ops):
-        for w in o["rd"]:
-            if w in last_w:
-                preds[i].append((last_w[w], True))
-            readers.setdefault(w, []).append(i)
-        w = o["wr"]
-        if w in last_w:
-            preds[i].append((last_w[w], True))      # read-modify-write of the word
-        for r in readers.get(w, ()):
-            if r != i:
-                preds[i].append((r, False))
-        last_w[w] = i
-        readers[w] = []
-    succs = [[] for _ in range(n)]
-    for i in range(n):
-        for (p_, raw) in preds[i]:
-            succs[p_].append((i, raw))
-    prio = [0] * n
-    for i in range(n - 1, -1, -1):
-        prio[i] = max([prio[j] + (lat if raw else 1) for (j, raw) in succs[i]] or [0])
-    npred = [len(set(p_ for p_, _ in preds[i])) for i in range(n)]
-    pset = [set(p_ for p_, _ in preds[i]) for i in range(n)]
-    rawset = [set(p_ for p_, raw in preds[i] if raw) for i in range(n)]
-    issued_at = {}
-    quad_of = [next((src[1] >> 1 for src in o["srcs"] if src[0] == "L"), None) for o in ops]
-    recent = []
-    ready = [i for i in range(n) if npred[i] == 0]
-    out, t = [], 0
-    remaining = [len(ps) for ps in pset]
-    users = [sorted(set(j for j, _ in succs[i])) for i in range(n)]
-    while ready:
-        def avail(i):
-            return max([issued_at[p_] + lat for p_ in rawset[i]] or [0])
-        ok = [i for i in ready if avail(i) <= t]
-        if ok:
-            # an operation whose LDS quad is still in the ring (its partner word was consumed a moment ago) first
-            best = max(prio[i] for i in ok)
-            near = [i for i in ok if quad_of[i] in recent and prio[i] >= best - SCHED_SLACK * lat]
-            pick = min(near) if near else max(ok, key=lambda i: (prio[i], -i))
-        else:
-            pick = min(ready, key=lambda i: (avail(i), -prio[i], i))
-        ready.remove(pick)
-        if quad_of[pick] is not None:
-            if quad_of[pick] in recent:
-                recent.remove(quad_of[pick])
-            recent.append(quad_of[pick])
-            del recent[:-(NSLOT - 3)]
-        issued_at[pick] = t
-        out.append(ops[pick])
-        t += 1
-        for j in users[pick]:
-            remaining[j] -= 1
-            if remaining[j] == 0:
-                ready.append(j)
-    assert len(out) == n
-    return out
-
-
 def _words(lo, hi):
     """LDS quads covering words [lo, hi): list of (quad, [words of the range in it])"""
     out = []
@@ -297,13 +224,6 @@ def preload_q(e, s):
     _row_ptr(e, S_P, S_WS, FAC_Q)
     for j in range(s.nx):
         e("global_load_dwordx2", vp(V_W + 2 * j), "v0", sp(S_P))
-        _adv(e, S_P)
-
-
-def preload_l(e, s, neq):
-    _row_ptr(e, S_P, S_WS, FAC_LOEQ)
-    for i in range(neq):
-        e("global_load_dwordx2", vp(V_W + 2 * (s.nx + i)), "v0", sp(S_P))
         _adv(e, S_P)
 
 
@@ -359,71 +279,62 @@ def body(e, s, first, capture, handoff=True):
     RHO3 = lambda k: V_C + 6 * N + 2 * k
     RINV3 = lambda k: V_C + 8 * N + 2 * k
     ptr = sp(S_P2)
-    # q (and, unless first, l of the dynamics rows) are on their way into the W registers: loads issued in the order q_0..q_44,
-    # l_0..l_35 behind the previous iteration's updates (or by the prologue), no other VMEM operation since. Each rhs
-    # operation waits for ITS word only (loads return in order), so the tail of the loads hides behind the head of the rhs.
-    npre = nx if first else nx + neq
+    # first iteration: q is on its way into the W_x registers, loads issued in the order q_0..q_44 by the prologue, no other
+    # VMEM operation since. Each rhs operation waits for ITS word only (loads return in order), so the tail of the loads
+    # hides behind the head of the rhs.
     waited = [-1]
 
     def wait_pre(pos):
         if pos > waited[0]:
-            e("s_waitcnt", "vmcnt(%d)" % min(63, npre - 1 - pos))
+            e("s_waitcnt", "vmcnt(%d)" % min(63, nx - 1 - pos))
             waited[0] = pos
     ops = []
 
-    def op(srcs, fn, wr, rd=()):
-        """wr / rd: the W word (original index) the operation updates / the other W words it reads"""
-        ops.append(dict(srcs=srcs, emit=fn, wr=wr, rd=tuple(rd)))
-    # ---- rhs: W = [sigma x - q ; z - y / rho]  (auxil.c:164-178). First iteration (and HOMES off): q / l already in W;
-    # later iterations with HOMES: q, l from their AGPR homes, structural zeros dropped. FUSE: the middle iterations have no
-    # rhs phase at all -- the x and y updates of the iteration before leave the next right-hand side in the W registers (the
-    # updated word is in a register there: no second LDS read of x and y; same operations on the same values)
-    hm = homes(s) if HOMES else None
-    fuse = HOMES and FUSE
-    fused_here = fuse and not first and not capture          # this body's updates form the next rhs
+    def op(srcs, fn):
+        ops.append(dict(srcs=srcs, emit=fn))
+    # ---- rhs: W = [sigma x - q ; z - y / rho]  (auxil.c:164-178). First iteration: q already in W; the hand-off to the
+    # second: q, l from their AGPR homes, structural zeros dropped. The later iterations have no rhs phase at all -- the x and
+    # y updates of the iteration before leave the next right-hand side in the W registers (the updated word is in a
+    # register there: no second LDS read of x and y; same operations on the same values)
+    hm = homes(s)
+    fused_here = not first and not capture          # this body's updates form the next rhs
 
     def add_rhs(first_style):
-        use_h = HOMES and not first_style
         for j in range(nx):
-            if not use_h:
-                op([("L", LW_X + j)], lambda r, j=j: (wait_pre(j), e("v_fma_f64", vp(W(j)), sS, vp(r[0]), "-" + vp(W(j)))), j)
+            if first_style:
+                op([("L", LW_X + j)], lambda r, j=j: (wait_pre(j), e("v_fma_f64", vp(W(j)), sS, vp(r[0]), "-" + vp(W(j)))))
             elif ("q", j) in hm:
-                op([("L", LW_X + j), ("A", hm[("q", j)])], lambda r, j=j: e("v_fma_f64", vp(W(j)), sS, vp(r[0]), "-" + vp(r[1])), j)
+                op([("L", LW_X + j), ("A", hm[("q", j)])], lambda r, j=j: e("v_fma_f64", vp(W(j)), sS, vp(r[0]), "-" + vp(r[1])))
             else:
-                op([("L", LW_X + j)], lambda r, j=j: e("v_mul_f64", vp(W(j)), sS, vp(r[0])), j)
+                op([("L", LW_X + j)], lambda r, j=j: e("v_mul_f64", vp(W(j)), sS, vp(r[0])))
         for i in range(neq):
             if first_style:
                 op([("L", LW_Y + i), ("A", A_Z + 2 * i)],
-                   lambda r, i=i: e("v_fma_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi, vp(r[1])), nx + i)
-            elif not use_h:
-                op([("L", LW_Y + i)], lambda r, i=i: (wait_pre(nx + i),
-                                                      e("v_fma_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi, vp(W(nx + i)))), nx + i)
+                   lambda r, i=i: e("v_fma_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi, vp(r[1])))
             elif ("l", i) in hm:
                 op([("L", LW_Y + i), ("A", hm[("l", i)])],
-                   lambda r, i=i: e("v_fma_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi, vp(r[1])), nx + i)
+                   lambda r, i=i: e("v_fma_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi, vp(r[1])))
             else:
-                op([("L", LW_Y + i)], lambda r, i=i: e("v_mul_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi), nx + i)
+                op([("L", LW_Y + i)], lambda r, i=i: e("v_mul_f64", vp(W(nx + i)), "-" + vp(r[0]), sRi))
         for k in range(N):
             i = neq + k
-            op([("L", LW_Y + i)], lambda r, i=i, k=k: e("v_fma_f64", vp(W(nx + i)), "-" + vp(RINV3(k)), vp(r[0]), vp(Z3(k))), nx + i)
-    if first or not fuse:
-        add_rhs(first)
+            op([("L", LW_Y + i)], lambda r, i=i, k=k: e("v_fma_f64", vp(W(nx + i)), "-" + vp(RINV3(k)), vp(r[0]), vp(Z3(k))))
+    if first:
+        add_rhs(True)
     # ---- forward solve (qdldl.c:250-262), columns ascending, entries ascending: W[r] -= L_j W[c]
     for c in range(nk):
         for j in range(s.L_p[c], s.L_p[c + 1]):
             r_ = s.L_i[j]
-            op([("L", j)], lambda r, r_=r_, c=c: e("v_fma_f64", vp(WK(r_)), "-" + vp(r[0]), vp(WK(c)), vp(WK(r_))),
-               s.perm[r_], [s.perm[c]])
+            op([("L", j)], lambda r, r_=r_, c=c: e("v_fma_f64", vp(WK(r_)), "-" + vp(r[0]), vp(WK(c)), vp(WK(r_))))
     # ---- diagonal (qdldl.c:289)
     for k in range(nk):
-        op([("A", A_D + 2 * k)], lambda r, k=k: e("v_mul_f64", vp(WK(k)), vp(WK(k)), vp(r[0])), s.perm[k])
+        op([("A", A_D + 2 * k)], lambda r, k=k: e("v_mul_f64", vp(WK(k)), vp(WK(k)), vp(r[0])))
     # ---- backward solve (qdldl.c:264-277), the storage walked backwards: W[c] -= L_j W[r]
     for c in range(nk - 1, -1, -1):
         for j in range(s.L_p[c + 1] - 1, s.L_p[c] - 1, -1):
             r_ = s.L_i[j]
-            op([("L", j)], lambda r, r_=r_, c=c: e("v_fma_f64", vp(WK(c)), "-" + vp(r[0]), vp(WK(r_)), vp(WK(c))),
-               s.perm[c], [s.perm[r_]])
-    Fetch(e).run(list_schedule(ops))
+            op([("L", j)], lambda r, r_=r_, c=c: e("v_fma_f64", vp(WK(c)), "-" + vp(r[0]), vp(WK(r_)), vp(WK(c))))
+    Fetch(e).run(ops)
     # ---- x <- alpha x~ + (1 - alpha) x   (auxil.c:188-201); x_prev of a capturing iteration -> workspace
     def lds_store(word, reg):
         """one word of a capture -> LDS (the capturing iteration is the last one: the L words are dead)"""
@@ -431,8 +342,6 @@ def body(e, s, first, capture, handoff=True):
         e("ds_write_b64", base, vp(reg), off + 8 * half)
         return 1
     quads = _words(LW_X, LW_X + nx)
-    if not first and not HOMES:
-        _row_ptr(e, S_P, S_WS, FAC_Q)      # the next iteration's q follows the update into each group of W_x registers
     for g in range(0, len(quads), NSLOT):
         grp = quads[g:g + NSLOT]
         where = _read_group(e, grp)
@@ -454,23 +363,16 @@ def body(e, s, first, capture, handoff=True):
                     else:
                         e("v_mul_f64", vp(W(j)), sS, vp(r))
             nw += _write_quad(e, qd, ws, {w: (V_TT + 2 * ((w - LW_X) % N_TT) if capture else where[w]) for w in ws})
-        if not first and not HOMES:
-            for qd, ws in grp:
-                for w in ws:
-                    e("global_load_dwordx2", vp(W(w - LW_X)), "v0", sp(S_P))
-                    _adv(e, S_P)
-    lrows = [i for i in range(neq) if not HOMES or ("l", i) in hm]
+    lrows = [i for i in range(neq) if ("l", i) in hm]
     if first:
         # l of the dynamics rows (the new z there) -> the W_x registers the x update has just freed, one round trip for
-        # all rows (HOMES: for the 16 that can be non-zero); q follows after the row update
+        # the 16 rows that can be non-zero; q follows after the row update
         for i in lrows:
             _row_ptr(e, S_P, S_WS, FAC_LOEQ + i)
             e("global_load_dwordx2", vp(W(i)), "v0", sp(S_P))
         e("s_waitcnt", "vmcnt(0)")
     # ---- z, y  (auxil.c:203-228, qdldl_interface.c:364-366, proj.c:4-14)
     quads = _words(LW_Y, LW_Y + nc)
-    if not first and not HOMES:
-        _row_ptr(e, S_P, S_WS, FAC_LOEQ)   # ... and l into each group of W_z registers
     for g in range(0, len(quads), NSLOT):
         grp = quads[g:g + NSLOT]
         where = _read_group(e, grp)
@@ -529,16 +431,7 @@ def body(e, s, first, capture, handoff=True):
                     e("v_fma_f64", vp(nu), "-" + rinv, vp(r), vp(zr))
                 newreg[w] = r
             nw += _write_quad(e, qd, ws, newreg)
-        if not first and not HOMES:
-            for qd, ws in grp:
-                for w in ws:
-                    if w - LW_Y < neq:
-                        e("global_load_dwordx2", vp(W(nx + w - LW_Y)), "v0", sp(S_P))
-                        _adv(e, S_P)
-    if first and not HOMES:
-        preload_q(e, s)
-        preload_l(e, s, neq)
-    elif first:
+    if first:
         # the z words of the first iteration (a168..) are dead: l (still in the W_x registers) and q take their homes there
         for i in lrows:
             e("v_accvgpr_write_b32", "a%d" % hm[("l", i)], "v%d" % W(i))
@@ -548,8 +441,8 @@ def body(e, s, first, capture, handoff=True):
                 _row_ptr(e, S_P, S_WS, FAC_Q + j)
                 e("global_load_dwordx2", "a[%d:%d]" % (a_, a_ + 1), "v0", sp(S_P))
         e("s_waitcnt", "vmcnt(0)")
-        if fuse and not capture and handoff:
-            # FUSE: the first iteration hands the second its right-hand side the classic way (x, y from LDS, q and l from the
+        if not capture and handoff:
+            # the first iteration hands the second its right-hand side the classic way (x, y from LDS, q and l from the
             # homes just filled); from then on every iteration's updates do it for the next one
             ops = []
             add_rhs(False)
@@ -562,17 +455,16 @@ def epilogue(e, s):
     nx, nc = s.nx, s.nc
     N = s.N
     neq = 2 * N * symbolic.NY
-    e("s_waitcnt", "vmcnt(0)")      # HOMES off: the last preloads, W_z of the dynamics rows holds l (= z there)
-    if HOMES:
-        hm = homes(s)
-        for i in range(neq):
-            r = V_W + 2 * (nx + i)
-            if ("l", i) in hm:
-                e("v_accvgpr_read_b32", "v%d" % r, "a%d" % hm[("l", i)])
-                e("v_accvgpr_read_b32", "v%d" % (r + 1), "a%d" % (hm[("l", i)] + 1))
-            else:
-                e("v_mov_b32", "v%d" % r, 0)
-                e("v_mov_b32", "v%d" % (r + 1), 0)
+    e("s_waitcnt", "vmcnt(0)")
+    hm = homes(s)
+    for i in range(neq):        # z of the dynamics rows is l
+        r = V_W + 2 * (nx + i)
+        if ("l", i) in hm:
+            e("v_accvgpr_read_b32", "v%d" % r, "a%d" % hm[("l", i)])
+            e("v_accvgpr_read_b32", "v%d" % (r + 1), "a%d" % (hm[("l", i)] + 1))
+        else:
+            e("v_mov_b32", "v%d" % r, 0)
+            e("v_mov_b32", "v%d" % (r + 1), 0)
     e("s_mov_b64", sp(S_P), sp(S_CTRL))
     quads = _words(LW_X, LW_X + nx + nc)
     for g in range(0, len(quads), NSLOT):
@@ -833,7 +725,6 @@ RA_ET, RA_P, RA_Q = 0, 78, 168
 S_MINS, S_MAXS = 30, 32                      # 1e-4, 1e4 (doubles in SGPR pairs)
 # Round 3: the cost scaling c is carried as a scalar through the passes (the norms see c * P_j, c * sum|P|, c * max|q|) and
 # applied to P and q once on the way out, instead of 90 AGPR read / multiply / write triples per pass (rounding only)
-CARRY_C = os.environ.get("UMPC_ASM64_RUIZ_CARRY_C", "1") == "1"
 
 
 def ruiz_program(N=3, perm=None):
@@ -951,10 +842,8 @@ def ruiz_program(N=3, perm=None):
         pj, t, dt = T(6), T(0), T(1)
         acc_read(pj, RA_P + 2 * j)
         first = True
-        pn = pj
-        if CARRY_C:      # P and q are kept WITHOUT the accumulated cost scaling c; the norms see c * P_j
-            pn = T(3)
-            e("v_mul_f64", vp(pn), vp(pj), vp(RV_C))
+        pn = T(3)        # P and q are kept WITHOUT the accumulated cost scaling c; the norms see c * P_j
+        e("v_mul_f64", vp(pn), vp(pj), vp(RV_C))
         for p_ in range(s.A_p[j], s.A_p[j + 1]):
             e("v_max_f64", vp(t), "|" + vp(pn if first else t) + "|", "|" + vp(A(p_)) + "|")
             first = False
@@ -985,9 +874,9 @@ def ruiz_program(N=3, perm=None):
     e("v_mov_b32", "v%d" % T(0), b & 0xFFFFFFFF)
     e("v_mov_b32", "v%d" % (T(0) + 1), b >> 32)
     recip(T(1), T(0), T(2))
-    if CARRY_C:          # sum |P_j| and max |q_j| were formed without c (both commute with a positive factor up to rounding)
-        e("v_mul_f64", vp(T(4)), vp(T(4)), vp(RV_C))
-        e("v_mul_f64", vp(T(5)), vp(T(5)), vp(RV_C))
+    # sum |P_j| and max |q_j| were formed without c (both commute with a positive factor up to rounding)
+    e("v_mul_f64", vp(T(4)), vp(T(4)), vp(RV_C))
+    e("v_mul_f64", vp(T(5)), vp(T(5)), vp(RV_C))
     e("v_mul_f64", vp(T(2)), vp(T(4)), vp(T(1)))
     e("v_fma_f64", vp(T(3)), "-" + vp(T(0)), vp(T(2)), vp(T(4)))
     e("v_fma_f64", vp(T(4)), vp(T(3)), vp(T(1)), vp(T(2)))              # pmean / nx
@@ -996,18 +885,6 @@ def ruiz_program(N=3, perm=None):
     limit(T(4), T(0))
     recip(T(5), T(4), T(0))                                              # ct
     e("v_mul_f64", vp(RV_C), vp(RV_C), vp(T(5)))
-    for j in range(nx if not CARRY_C else 0):
-        acc_read(T(j % 2), RA_P + 2 * j)
-        e("v_mul_f64", vp(T(j % 2)), vp(T(j % 2)), vp(T(5)))
-        acc_write(RA_P + 2 * j, T(j % 2))
-    for j in range(nx if not CARRY_C else 0):
-        kind, reg = qhome(j)
-        if kind == "a":
-            acc_read(T(2 + j % 2), reg)
-            e("v_mul_f64", vp(T(2 + j % 2)), vp(T(2 + j % 2)), vp(T(5)))
-            acc_write(reg, T(2 + j % 2))
-        else:
-            e("v_mul_f64", vp(reg), vp(reg), vp(T(5)))
     e("s_sub_i32", "s%d" % S_CNT, "s%d" % S_CNT, 1)
     e("s_cmp_gt_i32", "s%d" % S_CNT, 0)
     e("s_cbranch_scc1", "7b")
@@ -1028,8 +905,7 @@ def ruiz_program(N=3, perm=None):
                     else:
                         e("v_mov_b32", "v%d" % r, "v%d" % reg)
                         e("v_mov_b32", "v%d" % (r + 1), "v%d" % (reg + 1))
-                    if CARRY_C:      # the accumulated cost scaling, once
-                        e("v_mul_f64", vp(r), vp(r), vp(RV_C))
+                    e("v_mul_f64", vp(r), vp(r), vp(RV_C))      # the accumulated cost scaling, once
                     regs[w_] = r
                 _write_quad(e, qd, ws, regs)
     base, off, _ = lds_addr(RZ_C)

@@ -60,7 +60,6 @@ S_W, S_S, S_STRIDE, S_ITERS = 4, 6, 10, 11          # s[4:5] row workspace, s[6:
 S_P, S_CNT, S_SP = 12, 14, 16                       # row pointer, loop counter, stream pointer
 S_ALPHA, S_OMA, S_SIGMA, S_RINVEQ = 20, 21, 22, 23  # floats (inputs)
 S_RHO0, S_RINV0, S_RHOEQ = 31, 34, 35               # rho, 1/rho, rho_eq (float bits, inputs): the classes update_rho_vec assigns
-RHO_MIN_F32 = 1e-6                                  # (auxil.c:103-145; the third class, both bounds infinite, is a constant)
 V_B1, V_B2, V_LANE, V_W = 2, 3, 4, 5     # inputs: v0 = 4*robot, v1 = lane LDS address (16*lane), v4 = 4*lane
 NRING, NLAND, N_AT, N_TT = 6, 36, 4, 8
 V_END = 246
@@ -74,24 +73,14 @@ LW_FLAGS = 636                                      # LDS words 636..639: LOOSE_
 # 4-5 loads per row and iteration). Same operations on the same values: bit-identical results. The glue block decides
 # per wave (LDS word LOOSE_FLAG).
 S_RIMIN, S_RHOMIN = 36, 37                            # 1 / RHO_MIN, RHO_MIN as float bits (set by the loose program itself)
-Y0_VARIANT = os.environ.get("UMPC_QP_Y0", "1") == "1"   # the loose program carries the y == 0 variant of its loop (program())
-Y0_DLEAF = os.environ.get("UMPC_QP_Y0_DLEAF", "1") == "1"    # ... with 1/d of the leaf loose rows in an SGPR (S_DLEAF)
-Y0_FUSE = os.environ.get("UMPC_QP_Y0_FUSE", "1") == "1"      # ... and the updates forming the next iteration's right-hand side
+# the loose program carries the y == 0 variant of its loop (program()), with 1/d of the leaf loose rows in an SGPR and the
+# updates forming the next iteration's right-hand side
 S_DLEAF = 38
 
 
 def lds_addr(word):
     byte = (word >> 2) * 1024
     return "v%d" % (1, V_B1, V_B2)[byte >> 16], (byte & 0xFFFF) + 4 * (word & 3)
-
-
-# generation-time switches (experiments; the defaults are what ships): where the bounds of the leaf equality rows live
-# ('V': registers, 'A': the AGPRs behind 1/D then LDS), 1/rho of some inequality rows resident in the free LDS words,
-# rho selected instead of streamed
-PACK_PARTS = os.environ.get("UMPC_QP_PACK_PARTS", "1234")     # (diagnostics) 1: rhs of x, 2: 1/D scaling, 3: x update, 4: equality rows
-PACK_LOOSE = os.environ.get("UMPC_QP_PACK_LOOSE", "1") == "1"      # packed row updates in the loose variant (A/B switch)
-KNOB = dict(leafeq=os.environ.get("UMPC_QP_LEAFEQ", "V"), rinv_lds=os.environ.get("UMPC_QP_RINV_LDS", "1") == "1",
-            rho_select=os.environ.get("UMPC_QP_RHO_SELECT", "0") == "1")
 
 
 class Plan:
@@ -159,14 +148,10 @@ class Plan:
         for r in self.rows:
             if r["leaf"]:
                 assert r["r"] in self.wreg, "a leaf row must hang off a non-leaf unknown"
-        # (generation-time experiment UMPC_QP_RHO_SELECT=1: rho of a row selected from the three class constants by comparing
-        # its streamed 1/rho instead of streaming it -- 20 % fewer stream items, 4 more VALU per row: slower, the loop is
-        # bound by instruction issue; off by default)
-        self.V_RHO0 = V_W + len(self.nonleaf)
-        self.V_RHOEQ, self.V_RHOMIN = self.V_RHO0 + 1, self.V_RHO0 + 2
+        # the bounds of the leaf equality rows live in registers V_LEQ..
         self.leafeq = [r["i"] for r in self.rows if r["leaf"] and r["eq"]]
-        self.V_LEQ = self.V_RHO0 + (3 if KNOB["rho_select"] else 0)
-        self.V_RING = self.V_LEQ + (len(self.leafeq) if KNOB["leafeq"] == "V" else 0)
+        self.V_LEQ = V_W + len(self.nonleaf)
+        self.V_RING = self.V_LEQ + len(self.leafeq)
         self.V_LAND = self.V_RING + 4 * NRING
         self.NLAND = V_END - N_TT - N_AT - self.V_LAND        # every register left over lands stream items
         assert self.NLAND >= 16
@@ -203,24 +188,19 @@ class Plan:
         self.LW_END = self.LW_Z + len(gen)
         assert self.LW_END <= 640
         # Words that are constant over the iterations and find a home on chip are loaded ONCE (prologue) instead of streamed
-        # every iteration: the scaled bounds of the leaf equality rows -> the AGPRs behind 1/D, then LDS; 1/rho of as many
-        # inequality rows as LDS words are left (each is read twice per iteration: rhs and row update).
-        self.once = {}                                         # item -> ('A', agpr) | ('L', lds word)
-        free_a = list(range(nk, 256))
+        # every iteration: the scaled bounds of the leaf equality rows -> registers; 1/rho of as many inequality rows as LDS
+        # words are left (each is read twice per iteration: rhs and row update).
+        self.once = {}                                         # item -> ('V', vgpr) | ('L', lds word)
         free_l = list(range(self.LW_END, LW_XCH))
         for q, i in enumerate(self.leafeq):
-            if KNOB["leafeq"] == "V":
-                self.once[("l", i)] = ("V", self.V_LEQ + q)
-            else:
-                self.once[("l", i)] = ("A", free_a.pop(0)) if free_a else ("L", free_l.pop(0))
+            self.once[("l", i)] = ("V", self.V_LEQ + q)
         for i in gen:
-            if free_l and KNOB["rinv_lds"]:
+            if free_l:
                 self.once[("rinv", i)] = ("L", free_l.pop(0))
-        # stream items of one iteration, in consumption order (rho is not streamed: see V_RHO0)
+        # stream items of one iteration, in consumption order
         self.stream = [("rinv", i) for i in gen if ("rinv", i) not in self.once]
         for i in gen:
-            self.stream += [("l", i), ("u", i)] + ([("rinv", i)] if ("rinv", i) not in self.once else []) + \
-                           ([("rho", i)] if not KNOB["rho_select"] else [])
+            self.stream += [("l", i), ("u", i)] + ([("rinv", i)] if ("rinv", i) not in self.once else []) + [("rho", i)]
         self.n_land = len(self.stream)
         self.stream += [("q", j) for j in range(n)]
         self.stream += [("l", r["i"]) for r in self.rows if r["eq"] and not r["leaf"]]
@@ -245,7 +225,7 @@ class Plan:
         # ... and 1/d of a leaf loose row is ONE number (its unknown is eliminated first: d = -1/rho_min, nothing folded in),
         # which the y0 loop keeps in an SGPR; the AGPRs of those rows take the items that are still homeless
         self.y0_dleaf = [r["k"] for r in self.rows if r["leaf"] and not r["eq"]]
-        apool = list(self.y0_dleaf) if Y0_DLEAF else []
+        apool = list(self.y0_dleaf)
         for (a_, b_) in self.eqpairs:
             if ("l", a_) not in self.y0_home and len(apool) >= 2:
                 self.y0_home[("l", a_)], self.y0_home[("l", b_)] = ("A", apool.pop(0)), ("A", apool.pop(0))
@@ -266,29 +246,27 @@ class Plan:
 
 
 # distance (instructions) after which an LDS / stream access is taken to have completed when a wait is placed: the wait
-# then covers it too and the later wait for it is not emitted (0: every wait covers exactly what its op needs)
-MERGE_LDS = int(os.environ.get("UMPC_QP_MERGE_LDS", "16"))
-MERGE_VM = int(os.environ.get("UMPC_QP_MERGE_VM", "150"))
+# then covers it too and the later wait for it is not emitted
+MERGE_LDS = 16
+MERGE_VM = 150
 # generation-time experiment: the first NT_ITEMS landing items of an iteration are loaded with the non-temporal hint, so that
 # the rest of the stream (re-read every iteration) can stay in the XCD's L2 instead of the whole of it cycling through
 NT_ITEMS = int(os.environ.get("UMPC_QP_NT", "0"))
 NT_KINDS = tuple(k for k in os.environ.get("UMPC_QP_NT_KINDS", "").split(",") if k)     # "", "rows", "stream", "rows,stream"
-RING_AHEAD = int(os.environ.get("UMPC_QP_RING_AHEAD", "20"))   # ops of look-ahead for the LDS ring reads
+RING_AHEAD = 20   # ops of look-ahead for the LDS ring reads
 
 
 class Own:
     """Which variables, rows and KKT unknowns a wavefront's copy of the loop block works on (LoopSplit); ALL = one wave, all."""
 
-    def __init__(self, varw=None, roww=None, kw=None, wave=0, lhome=None, fkw=None, split=None, fvarw=None):
+    def __init__(self, varw=None, roww=None, kw=None, wave=0, lhome=None, split=None):
         self.varw, self.roww, self.kw, self.wave = varw, roww, kw, wave
         self.all = varw is None
         self.lhome = lhome or {}          # L entry (CSC index) -> VGPR that holds -L during the iterations (LoopSplit.own)
         self.chome, self.yhome = {}, {}   # LDS word of a loop constant -> VGPR: leaf entries of L (every variant); q, l (y0 bodies)
-        self.ahome, self.shome = {}, {}   # fused y0 bodies (S_HOMES): LDS word of a constant -> AGPR; of the wave's x / y / z -> VGPR
+        self.ahome, self.shome = {}, {}   # fused y0 bodies: LDS word of a constant -> AGPR; of the wave's x / y / z -> VGPR
         self.dhome = {}                   # ... and 1/D of own unknowns -> VGPR (registers that are idle in those bodies)
-        self.ghome = {}                   # bodies that are not y0 (G_HOMES): stream item -> AGPR (what they loaded every iteration)
-        self.fkw = fkw if fkw is not None else kw          # who FACTORISES unknown k (a component cut in two: the wave of half A)
-        self.fvarw = fvarw if fvarw is not None else varw
+        self.ghome = {}                   # bodies that are not y0: stream item -> AGPR (what they loaded every iteration)
         # a component cut in two (LoopSplit): the solves of every wave of the workgroup meet at two barriers
         self.xbar = split is not None
         sp = split or {}
@@ -298,9 +276,9 @@ class Own:
         self.xsend_f = sp.get("xsend_f", {})     # unknown c -> LDS word this wave leaves its forward value in
         self.xsend_b = sp.get("xsend_b", {})     # separator unknown r -> LDS word this wave leaves its solution in
         self.xrecv_b = sp.get("xrecv_b", {})     # separator unknown r (the partner's) -> LDS word
-        self.hand_out = sp.get("hand_out", {})   # unknown k this wave factorises for its partner -> LDS word 1/D_k is handed over in
-        self.hand_in = sp.get("hand_in", {})     # unknown k of this wave that the partner factorises -> that word
-        self.ftop = sp.get("ftop", set())        # separator unknowns this wave factorises AFTER its partner's subtree (FACTOR_SPLIT)
+        self.hand_out = sp.get("hand_out", {})   # unknown k this wave factorises, whose 1/D its partner needs too -> LDS word it is handed over in
+        self.hand_in = sp.get("hand_in", {})     # unknown k that the partner factorises and this wave needs 1/D of -> that word
+        self.ftop = sp.get("ftop", set())        # separator unknowns this wave factorises AFTER its partner's subtree
 
     def var(self, j):
         return self.all or self.varw[j] == self.wave
@@ -311,27 +289,13 @@ class Own:
     def k(self, k):
         return self.all or self.kw[k] == self.wave
 
-    def fk(self, k):
-        return self.all or self.fkw[k] == self.wave
-
-    def fvar(self, j):
-        return self.all or self.fvarw[j] == self.wave
-
     def item(self, item):
         what, idx = item
         return self.var(idx) if what == "q" else self.row(idx)
 
 
 ALL = Own()
-L_HOMES = os.environ.get("UMPC_QP_L_HOMES", "1") == "1"        # (A/B switch: LoopSplit.own)
-FACTOR_SPLIT = os.environ.get("UMPC_QP_FACTOR_SPLIT", "1") == "1"   # (A/B switch: a cut component's halves factorise their own subtrees)
-G_HOMES = os.environ.get("UMPC_QP_G_HOMES", "1") == "1"        # (A/B switch: LoopSplit.own, the general loop's stream items in AGPRs)
-D_HOMES = os.environ.get("UMPC_QP_D_HOMES", "1") == "1"        # (A/B switch: LoopSplit.own, 1/D of own unknowns in idle VGPRs)
-Y_NRING = 2                                                     # ring slots the fused y0 bodies of such a wave may use
-S_HOMES = os.environ.get("UMPC_QP_S_HOMES", "1") == "1"        # (A/B switch: LoopSplit.own, the iterates in VGPRs, the constants in AGPRs)
-C_HOMES = os.environ.get("UMPC_QP_C_HOMES", "1") == "1"        # (A/B switch: LoopSplit.own, the loop's other constants in VGPRs)
-TREE_SPLIT = os.environ.get("UMPC_QP_TREE_SPLIT", "1") == "1"  # (A/B switch: LoopSplit cuts large components in two)
-SCALE_LATE = os.environ.get("UMPC_QP_SCALE_LATE", "1") == "1"  # (A/B switch: where a cut component's W / D sits between the barriers)
+Y_NRING = 2                                                     # ring slots the fused y0 bodies of a wave of a cut workgroup may use
 N_XCH = 16                                                      # LDS words LW_XCH.. below the flags: the halves' exchange words
 LW_XCH = LW_FLAGS - N_XCH
 
@@ -351,14 +315,14 @@ class LoopSplit:
                   ordering puts A's columns before B's), eliminates the separator columns, scales, solves them back
         backward  A leaves the separator's solution in LDS -- barrier -- both halves walk their subtree back
     Two barriers per iteration for every wavefront of the workgroup (a wavefront without a cut component just meets them).
-    The factorisation of a cut component stays with ONE wavefront (A's; it hands 1/D of B's unknowns over through LDS once).
+    The halves of a cut component factorise their own subtrees too; 1/D of B's columns that reach into the separator goes to
+    A through the exchange words, once per tick.
     planar p5f: 118 + 112 + 12 + 9 unknowns on four wavefronts became 63 + 60 + 64 + 64."""
 
-    def __init__(self, p, nw=4, tree=None):
+    def __init__(self, p, nw=4):
         from . import qpstruct
         s = p.s
         self.p = p
-        tree = TREE_SPLIT if tree is None else tree
         vc, rc = qpstruct.qp_components(s.n, s.m, list(s.tables["A_p"]), list(s.tables["A_i"]))
         self.nw = nw
         ncomp = max(vc) + 1
@@ -372,7 +336,7 @@ class LoopSplit:
         self.cut = {}
         units = []
         for c in range(ncomp):
-            cut = (self._given(comp, c) or self._cut(comp, c)) if tree and nw >= 2 and size[c] * nw > s.nk else None
+            cut = (self._given(comp, c) or self._cut(comp, c)) if nw >= 2 and size[c] * nw > s.nk else None
             if cut is None:
                 units.append((size[c], c, None))
             else:
@@ -389,14 +353,13 @@ class LoopSplit:
             load[w] += wt
         self.active = nact
         self.load = load
-        self.kw, self.fkw = [0] * s.nk, [0] * s.nk
+        self.kw = [0] * s.nk
         for k in range(s.nk):
             c = comp[k]
             if c in self.cut:
                 self.kw[k] = uw[(c, "B")] if k in self.cut[c]["B"] else uw[(c, "A")]
-                self.fkw[k] = self.kw[k] if FACTOR_SPLIT else uw[(c, "A")]
             else:
-                self.kw[k] = self.fkw[k] = uw[(c, None)]
+                self.kw[k] = uw[(c, None)]
         self.varw = [self.kw[p.pinv[j]] for j in range(s.n)]
         self.roww = [self.kw[p.pinv[s.n + i]] for i in range(s.m)]
         for r in p.rows:
@@ -405,18 +368,8 @@ class LoopSplit:
         # exchange words and the entries that cross a cut
         self.split = [dict(top=set(), cross=[], xrecv_f={}, xsend_f={}, xsend_b={}, xrecv_b={}, hand_out={}, hand_in={})
                       for _ in range(nact)] if self.cut else None
-        self.fvarw = [self.fkw[p.pinv[j]] for j in range(s.n)]
-        # 1/D that changes hands once per tick. One wave factorises the whole of a cut component (FACTOR_SPLIT off): 1/D of half B's
-        # unknowns goes from its AGPRs to B's through LDS words that held the component's A entries. The halves factorise their own
-        # subtrees (default): only 1/D of B's columns that reach into the separator goes to A, through the exchange words.
-        A_p_ = list(s.tables["A_p"])
-        for a_ in range(nact if self.cut else 0):
-            words = [p.LW_X + q for j in range(s.n) if self.fvarw[j] == a_ for q in range(A_p_[j], A_p_[j + 1])]
-            ks = [k for k in range(s.nk) if self.fkw[k] == a_ and self.kw[k] != a_]
-            assert len(ks) <= len(words)
-            for k, word in zip(ks, words):
-                self.split[a_]["hand_out"][k] = word
-                self.split[self.kw[k]]["hand_in"][k] = word
+        # 1/D that changes hands once per tick: the halves of a cut component factorise their own subtrees, and 1/D of B's
+        # columns that reach into the separator goes to A, through the exchange words.
         quad = LW_XCH
         for c in sorted(self.cut):
             a_, b_ = uw[(c, "A")], uw[(c, "B")]
@@ -431,10 +384,9 @@ class LoopSplit:
                 self.split[a_]["xrecv_f"][c_] = self.split[b_]["xsend_f"][c_] = quad + q
             for q, r_ in enumerate(tops):
                 self.split[a_]["xsend_b"][r_] = self.split[b_]["xrecv_b"][r_] = quad + 4 + q
-            if FACTOR_SPLIT:
-                for q, c_ in enumerate(cols):       # (the forward words of the solves, idle during the factorisation)
-                    self.split[b_]["hand_out"][c_] = self.split[a_]["hand_in"][c_] = quad + q
-                self.split[a_]["ftop"] = self.split[a_].get("ftop", set()) | T
+            for q, c_ in enumerate(cols):       # (the forward words of the solves, idle during the factorisation)
+                self.split[b_]["hand_out"][c_] = self.split[a_]["hand_in"][c_] = quad + q
+            self.split[a_]["ftop"] = self.split[a_].get("ftop", set()) | T
             quad += 8
         for (r_, c_, j) in p.solve_entries:
             assert self.kw[r_] == self.kw[c_] or any((r_, c_, j) in sp_["cross"] for sp_ in self.split or [])
@@ -533,9 +485,9 @@ class LoopSplit:
         pool = sorted(p.wreg[k] for k in p.nonleaf if self.kw[k] != wave)
         cross = set(self.split[wave]["cross"]) if self.split else set()
         mine = [j for (r_, c, j) in p.solve_entries if self.kw[c] == wave or (r_, c, j) in cross]
-        lhome = dict(zip(mine, pool)) if L_HOMES else {}
-        o = Own(self.varw, self.roww, self.kw, wave, lhome, self.fkw, self.split[wave] if self.split else None, self.fvarw)
-        if G_HOMES and self.split:
+        lhome = dict(zip(mine, pool))
+        o = Own(self.varw, self.roww, self.kw, wave, lhome, self.split[wave] if self.split else None)
+        if self.split:
             # The bodies of the GENERAL loop (finite bounds) and of the loose loop with non-zero multipliers loaded their read-only
             # items -- l, u, 1/rho, rho of the wave's inequality rows, q, l of its equality rows -- from the stream EVERY iteration
             # (150 VMEM instructions per wavefront-iteration). A wave of a cut workgroup uses a quarter of the 251 AGPR indices for
@@ -543,98 +495,96 @@ class LoopSplit:
             mine = [it for it in p.stream if o.item(it) and it not in p.once]
             mine = list(dict.fromkeys(mine))
             taken = {k for k in range(p.nk) if self.kw[k] == wave} | set(self.split[wave]["hand_in"]) | \
-                {h[1] for h in p.once.values() if h[0] == "A"} | set(self.split[wave].get("top", set()))
+                set(self.split[wave].get("top", set()))
             apool_g = [k for k in range(256) if k not in taken]
             if len(mine) <= len(apool_g):
                 o.ghome = dict(zip(mine, apool_g))
-        if C_HOMES and L_HOMES:
-            # ... and what is left of them the wave's other loop constants, which the bodies read from LDS every iteration (with all
-            # four wavefronts at work the LDS pipe is the second bottleneck: 4 array cycles per float4 read, 13 per float4 write): the leaf rows'
-            # entries of L, then (y0 bodies) q and l of the equality rows. A pair of words that the packed operations read as a
-            # pair gets an aligned register pair.
-            free = [r_ for r_ in pool if r_ not in set(lhome.values())]
-            lw = [p.lpos[r["j"]] for r in p.rows if r["leaf"] and self.roww[r["i"]] == wave]
-            qw = [h for (what, j), h in sorted(p.y0_home.items(), key=lambda kv: kv[1] if isinstance(kv[1], int) else -1)
-                  if what == "q" and isinstance(h, int) and self.varw[j] == wave]
-            ew = [h for (what, i), h in sorted(p.y0_home.items(), key=lambda kv: kv[1] if isinstance(kv[1], int) else -1)
-                  if what == "l" and isinstance(h, int) and self.roww[i] == wave]
-            for words, dst in ((lw, o.chome), (qw, o.yhome), (ew, o.yhome)):
-                ws = set(words)
-                for w_ in sorted(ws):
-                    if w_ in dst:
+        # ... and what is left of them the wave's other loop constants, which the bodies read from LDS every iteration (with all
+        # four wavefronts at work the LDS pipe is the second bottleneck: 4 array cycles per float4 read, 13 per float4 write): the leaf rows'
+        # entries of L, then (y0 bodies) q and l of the equality rows. A pair of words that the packed operations read as a
+        # pair gets an aligned register pair.
+        free = [r_ for r_ in pool if r_ not in set(lhome.values())]
+        lw = [p.lpos[r["j"]] for r in p.rows if r["leaf"] and self.roww[r["i"]] == wave]
+        qw = [h for (what, j), h in sorted(p.y0_home.items(), key=lambda kv: kv[1] if isinstance(kv[1], int) else -1)
+              if what == "q" and isinstance(h, int) and self.varw[j] == wave]
+        ew = [h for (what, i), h in sorted(p.y0_home.items(), key=lambda kv: kv[1] if isinstance(kv[1], int) else -1)
+              if what == "l" and isinstance(h, int) and self.roww[i] == wave]
+        for words, dst in ((lw, o.chome), (qw, o.yhome), (ew, o.yhome)):
+            ws = set(words)
+            for w_ in sorted(ws):
+                if w_ in dst:
+                    continue
+                if w_ % 2 == 0 and w_ + 1 in ws:
+                    base = next((r_ for r_ in free if r_ % 2 == 0 and r_ + 1 in free), None)
+                    if base is None:
+                        continue              # (no aligned pair left: these two stay in LDS)
+                    free.remove(base)
+                    free.remove(base + 1)
+                    dst[w_], dst[w_ + 1] = base, base + 1
+                elif not (w_ % 2 == 1 and w_ - 1 in ws):
+                    odd = [r_ for r_ in free if not (r_ % 2 == 0 and r_ + 1 in free) and not (r_ % 2 == 1 and r_ - 1 in free)]
+                    if not (odd or free):
                         continue
-                    if w_ % 2 == 0 and w_ + 1 in ws:
-                        base = next((r_ for r_ in free if r_ % 2 == 0 and r_ + 1 in free), None)
-                        if base is None:
-                            continue              # (no aligned pair left: these two stay in LDS)
-                        free.remove(base)
-                        free.remove(base + 1)
-                        dst[w_], dst[w_ + 1] = base, base + 1
-                    elif not (w_ % 2 == 1 and w_ - 1 in ws):
-                        odd = [r_ for r_ in free if not (r_ % 2 == 0 and r_ + 1 in free) and not (r_ % 2 == 1 and r_ - 1 in free)]
-                        if not (odd or free):
-                            continue
-                        r_ = (odd or free)[0]     # (singles first into registers that cannot form an aligned pair)
-                        free.remove(r_)
-                        dst[w_] = r_
-            if S_HOMES and self.split:
-                # The fused y0 bodies (the reference's problem: every iteration but the last) go one step further: the constants
-                # move on into AGPRs that this wave's 1/D does not use (a v_accvgpr_read costs a VALU slot and no LDS cycle), and
-                # the registers they held -- filled only on this path -- keep the wave's x, z and equality-row y words: no LDS
-                # access at all for them between the first and the last iteration.
-                topall = self.split[wave]["topall"] if "topall" in self.split[wave] else self.split[wave]["top"]
-                apool = [k for k in p.nonleaf if self.kw[k] != wave and k not in topall and k not in self.split[wave]["hand_in"]]
-                consts = sorted(set(lw) | set(qw) | set(ew))
-                eqs = set(int(i) for i in p.eq_rows_set)
-                sw = sorted([p.LW_X + j for j in range(p.n) if self.varw[j] == wave] +
-                            [p.LW_Z + p.zpos[i] for i in p.zpos if self.roww[i] == wave] +
-                            [p.LW_Y + i for i in range(p.m) if i in eqs and self.roww[i] == wave])
-                free2 = [r_ for r_ in pool if r_ not in set(lhome.values())]
-                sh, ok = {}, len(consts) <= len(apool)
-                for w_ in sw:
-                    if w_ in sh:
+                    r_ = (odd or free)[0]     # (singles first into registers that cannot form an aligned pair)
+                    free.remove(r_)
+                    dst[w_] = r_
+        if self.split:
+            # The fused y0 bodies (the reference's problem: every iteration but the last) go one step further: the constants
+            # move on into AGPRs that this wave's 1/D does not use (a v_accvgpr_read costs a VALU slot and no LDS cycle), and
+            # the registers they held -- filled only on this path -- keep the wave's x, z and equality-row y words: no LDS
+            # access at all for them between the first and the last iteration.
+            topall = self.split[wave]["topall"] if "topall" in self.split[wave] else self.split[wave]["top"]
+            apool = [k for k in p.nonleaf if self.kw[k] != wave and k not in topall and k not in self.split[wave]["hand_in"]]
+            consts = sorted(set(lw) | set(qw) | set(ew))
+            eqs = set(int(i) for i in p.eq_rows_set)
+            sw = sorted([p.LW_X + j for j in range(p.n) if self.varw[j] == wave] +
+                        [p.LW_Z + p.zpos[i] for i in p.zpos if self.roww[i] == wave] +
+                        [p.LW_Y + i for i in range(p.m) if i in eqs and self.roww[i] == wave])
+            free2 = [r_ for r_ in pool if r_ not in set(lhome.values())]
+            sh, ok = {}, len(consts) <= len(apool)
+            for w_ in sw:
+                if w_ in sh:
+                    continue
+                if w_ % 2 == 0 and w_ + 1 in sw:
+                    base = next((r_ for r_ in free2 if r_ % 2 == 0 and r_ + 1 in free2), None)
+                    if base is None:
+                        ok = False
+                        break
+                    free2.remove(base)
+                    free2.remove(base + 1)
+                    sh[w_], sh[w_ + 1] = base, base + 1
+                elif not (w_ % 2 == 1 and w_ - 1 in sw):
+                    odd = [r_ for r_ in free2 if not (r_ % 2 == 0 and r_ + 1 in free2) and not (r_ % 2 == 1 and r_ - 1 in free2)]
+                    if not (odd or free2):
+                        ok = False
+                        break
+                    r_ = (odd or free2)[0]
+                    free2.remove(r_)
+                    sh[w_] = r_
+            if ok:                # (all or nothing: a body either finds every word of the wave resident or none)
+                o.shome = sh
+                o.ahome = dict(zip(consts, apool))
+                # what is idle in those bodies -- the registers left over, four of the six ring slots (the only LDS reads
+                # are the exchange words), the AGPR temporaries of the unpacked bodies -- keeps 1/D of the wave's own
+                # unknowns, pair for pair as the packed scaling reads them
+                spare = sorted(free2 + list(range(p.V_RING + 4 * Y_NRING, p.V_RING + 4 * NRING)) + list(range(p.V_AT, p.V_AT + N_AT)))
+                mine_k = sorted((p.wreg[k], k) for k in p.nonleaf if self.kw[k] == wave)
+                regk = dict(mine_k)
+                for reg, k in mine_k:
+                    if k in o.dhome:
                         continue
-                    if w_ % 2 == 0 and w_ + 1 in sw:
-                        base = next((r_ for r_ in free2 if r_ % 2 == 0 and r_ + 1 in free2), None)
-                        if base is None:
-                            ok = False
-                            break
-                        free2.remove(base)
-                        free2.remove(base + 1)
-                        sh[w_], sh[w_ + 1] = base, base + 1
-                    elif not (w_ % 2 == 1 and w_ - 1 in sw):
-                        odd = [r_ for r_ in free2 if not (r_ % 2 == 0 and r_ + 1 in free2) and not (r_ % 2 == 1 and r_ - 1 in free2)]
-                        if not (odd or free2):
-                            ok = False
-                            break
-                        r_ = (odd or free2)[0]
-                        free2.remove(r_)
-                        sh[w_] = r_
-                if ok:                # (all or nothing: a body either finds every word of the wave resident or none)
-                    o.shome = sh
-                    o.ahome = dict(zip(consts, apool))
-                    if D_HOMES:
-                        # what is idle in those bodies -- the registers left over, four of the six ring slots (the only LDS reads
-                        # are the exchange words), the AGPR temporaries of the unpacked bodies -- keeps 1/D of the wave's own
-                        # unknowns, pair for pair as the packed scaling reads them
-                        spare = sorted(free2 + list(range(p.V_RING + 4 * Y_NRING, p.V_RING + 4 * NRING)) + list(range(p.V_AT, p.V_AT + N_AT)))
-                        mine_k = sorted((p.wreg[k], k) for k in p.nonleaf if self.kw[k] == wave)
-                        regk = dict(mine_k)
-                        for reg, k in mine_k:
-                            if k in o.dhome:
-                                continue
-                            if reg % 2 == 0 and reg + 1 in regk:
-                                base = next((r_ for r_ in spare if r_ % 2 == 0 and r_ + 1 in spare), None)
-                                if base is not None:
-                                    spare.remove(base)
-                                    spare.remove(base + 1)
-                                    o.dhome[k], o.dhome[regk[reg + 1]] = base, base + 1
-                            elif not (reg % 2 == 1 and reg - 1 in regk):
-                                odd = [r_ for r_ in spare if not (r_ % 2 == 0 and r_ + 1 in spare) and not (r_ % 2 == 1 and r_ - 1 in spare)]
-                                if odd or spare:
-                                    r_ = (odd or spare)[0]
-                                    spare.remove(r_)
-                                    o.dhome[k] = r_
+                    if reg % 2 == 0 and reg + 1 in regk:
+                        base = next((r_ for r_ in spare if r_ % 2 == 0 and r_ + 1 in spare), None)
+                        if base is not None:
+                            spare.remove(base)
+                            spare.remove(base + 1)
+                            o.dhome[k], o.dhome[regk[reg + 1]] = base, base + 1
+                    elif not (reg % 2 == 1 and reg - 1 in regk):
+                        odd = [r_ for r_ in spare if not (r_ % 2 == 0 and r_ + 1 in spare) and not (r_ % 2 == 1 and r_ - 1 in spare)]
+                        if odd or spare:
+                            r_ = (odd or spare)[0]
+                            spare.remove(r_)
+                            o.dhome[k] = r_
         return o
 
 
@@ -665,7 +615,7 @@ class Sched:
         if pos <= self.vm_done:
             return
         now = len(self.e.ins)
-        while MERGE_VM and pos + 1 < self.nvm and self.vm_at.get(pos + 1, -10 ** 9) <= now - MERGE_VM:
+        while pos + 1 < self.nvm and self.vm_at.get(pos + 1, -10 ** 9) <= now - MERGE_VM:
             pos += 1
         c = min(63, self.nvm - 1 - pos)
         self.e("s_waitcnt", "vmcnt(%d)" % c)
@@ -809,7 +759,7 @@ class Sched:
                         next_inst += 1
                     if it["issued"] > waited_lds:
                         J, now = it["issued"], len(e.ins)
-                        while MERGE_LDS and J + 1 < self.nlds and self.lds_at[J + 1] <= now - MERGE_LDS:
+                        while J + 1 < self.nlds and self.lds_at[J + 1] <= now - MERGE_LDS:
                             J += 1
                         e("s_waitcnt", "lgkmcnt(%d)" % min(15, self.nlds - 1 - J))
                         waited_lds = J
@@ -847,14 +797,11 @@ def couples(words):
     return first, second
 
 
-PAIR_QUADS = os.environ.get("UMPC_QP_PAIR_QUADS", "1") == "1"
-
-
-def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=ALL, group=False):
+def body(e, p, capture=False, loose=False, y0=False, rhs=True, own=ALL, group=False):
     """capture: the LAST iteration -- x_prev and delta_y go to rows R_XP / R_DY (auxil.c:362-512 consumes them)
     loose: every inequality row is a loose row (see S_RIMIN above)
-    rhs / fuse (y0 bodies): fuse -- the row and x updates leave the NEXT iteration's right-hand side in the W registers (the new
-    x, y, z words are in registers there: no second LDS read, and a leaf row's L entry is fetched once instead of twice);
+    y0 bodies but the capturing one FUSE: the row and x updates leave the NEXT iteration's right-hand side in the W registers (the
+    new x, y, z words are in registers there: no second LDS read, and a leaf row's L entry is fetched once instead of twice);
     rhs=False -- the iteration before did that, this body starts at the solves"""
     n, m = p.n, p.m
     v = lambda r: "v%d" % r
@@ -862,6 +809,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
     W = lambda k: v(p.wreg[k])
     T = lambda q: p.V_TT + q
     assert loose or not y0
+    fuse = y0 and not capture
     gh = {} if y0 else own.ghome             # (bodies that are not y0: the stream items of the wave in AGPRs, filled once per tick)
     homes = p.y0_home if y0 else {it: ("A", a_) for it, a_ in gh.items() if it in set(p.stream[p.n_land:])}
     # Where this body finds a loop constant (C: one word, C2: an aligned pair of words) and a word of x / y / z (S, S2):
@@ -903,7 +851,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
         sc.vm_wait(pre_pos[reg])
     rhs_ops_start = len(ops)
     # ---- P1: W_x = sigma x - q (q preloaded)
-    pack = loose and not capture and PACK_LOOSE          # the loose variant's middle iterations: two entries per instruction
+    pack = loose and not capture          # the loose variant's middle iterations: two entries per instruction
     VP = lambda r_: ("v[%d:%d]" % (r_, r_ + 1), 0, 1)
     SB = lambda sreg, h: ("s[%d:%d]" % (sreg - sreg % 2, sreg - sreg % 2 + 1), h, h)
     xpair = lambda j: pack and j + 1 < n and (p.LW_X + j) % 2 == 0 and p.wreg[p.pinv[j]] % 2 == 0 and \
@@ -917,7 +865,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
         if isinstance(qh, tuple):
             op([S(p.LW_X + j), qh], lambda r, k=k: e("v_fma_f32", W(k), sS, v(r[0]), "-" + v(r[1])))
             continue
-        if qh is not None and "1" in PACK_PARTS and xpair(j) and qh % 2 == 0 and homes.get(("q", j + 1)) == qh + 1:
+        if qh is not None and xpair(j) and qh % 2 == 0 and homes.get(("q", j + 1)) == qh + 1:
             jskip.add(j + 1)
             op([S2(p.LW_X + j), C2(qh)], lambda r, j=j: _pk(e, "v_pk_fma_f32", p.wreg[p.pinv[j]],
                                                                   [SB(S_SIGMA, S_SIGMA % 2), VP(r[0]), VP(r[1])], [0, 0, 1]))
@@ -925,7 +873,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
         if qh is not None:
             op([S(p.LW_X + j), C(qh)], lambda r, k=k: e("v_fma_f32", W(k), sS, v(r[0]), "-" + v(r[1])))
             continue
-        if "1" in PACK_PARTS and xpair(j) and ("q", j + 1) not in homes:
+        if xpair(j) and ("q", j + 1) not in homes:
             jskip.add(j + 1)
 
             def f2x(r, j=j):
@@ -961,7 +909,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
                and own.row(a_) and own.row(b_)}
     eqskip = set()
     paired = {}
-    if loose and not capture and PACK_LOOSE:
+    if pack:
         for a_, b_ in p.pairs:
             if not (own.row(a_["i"]) and own.row(b_["i"])):
                 continue                  # (a pair across two waves' components: each wave takes its row alone)
@@ -992,17 +940,17 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
                 continue
             op([("L", p.LW_Y + i), ("L", p.LW_Z + p.zpos[i]), C(p.lpos[r["j"]])], f2)
             continue
-        if pack and "4" in PACK_PARTS and i in eqskip:
+        if pack and i in eqskip:
             continue
         lh = homes.get(("l", i))
         lh1 = homes.get(("l", i + 1))
         lsrc = lambda h: h if isinstance(h, tuple) else C(h)
-        if pack and "4" in PACK_PARTS and i in eqfirst and isinstance(lh, tuple) and isinstance(lh1, tuple):
+        if pack and i in eqfirst and isinstance(lh, tuple) and isinstance(lh1, tuple):
             eqskip.add(i + 1)           # both bounds in AGPR homes: read as a pair
             op([S2(p.LW_Y + i), ("A2", lh[1], lh1[1])], lambda g, k=k: _pk(e, "v_pk_fma_f32", p.wreg[k],
                                                                            [VP(g[0]), SB(S_RINVEQ, S_RINVEQ % 2), VP(g[1])], [1, 0, 0]))
             continue
-        if pack and "4" in PACK_PARTS and i in eqfirst and not isinstance(lh, tuple) and not isinstance(lh1, tuple) and \
+        if pack and i in eqfirst and not isinstance(lh, tuple) and not isinstance(lh1, tuple) and \
                 (lh is None) == (lh1 is None) and (lh is None or (lh % 2 == 0 and lh1 == lh + 1)):
             eqskip.add(i + 1)
 
@@ -1060,7 +1008,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
             k = kof[reg]
             if k in kdone or not which(k):
                 continue
-            if "2" in PACK_PARTS and pack and reg % 2 == 0 and reg + 1 in kof and which(kof[reg + 1]):
+            if pack and reg % 2 == 0 and reg + 1 in kof and which(kof[reg + 1]):
                 k1 = kof[reg + 1]
                 kdone.add(k1)
                 op([DI2(k, k1)], lambda g, reg=reg: _pk(e, "v_pk_mul_f32", reg, [VP(reg), VP(g[0])]))
@@ -1088,11 +1036,9 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
             op([], lambda g, c=c, word=word: sc.lds_write(word, p.wreg[c]))       # (the forward value: before the scaling below)
         # W / D of the subtree: a wave that only waits between the two barriers (half B, a whole small component) does it there;
         # the wave with the separator after the second barrier, while its partner's read of the separator's solution is in flight
-        late = bool(top) and SCALE_LATE
-        if not SCALE_LATE:
-            scale(lambda k: k not in top)
+        late = bool(top)
         meet()
-        if SCALE_LATE and not late:
+        if not late:
             scale(lambda k: True)
         for (r_, c, j) in own.cross:
             op([lsrc_(j), ("L", own.xrecv_f[c])], lambda g, r_=r_: e("v_fmac_f32", W(r_), v(g[0]), v(g[1])))
@@ -1130,15 +1076,10 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
     npk = [0]
     eqskip2 = set()
     zc1 = zc2 = yc1 = yc2 = xc1 = xc2 = frozenset()
-    if pack and PAIR_QUADS:
+    if pack:
         assert (p.V_LAND + 8) % 2 == 0
-        if y0:
-            zc1, zc2 = couples([p.LW_Z + p.zpos[r["i"]] for r in p.rows if paired.get(r["i"]) is not None and p.LW_Z + p.zpos[r["i"]] not in sh])
-        if "4" in PACK_PARTS:
-            yc1, yc2 = couples([p.LW_Y + i for i in sorted(eqfirst) if p.LW_Y + i not in sh])
-        if "3" in PACK_PARTS:
-            xc1, xc2 = couples([p.LW_X + j for j in range(0, n, 2) if xpair(j) and p.LW_X + j not in sh])
-    assert not fuse or (y0 and pack and not capture and PAIR_QUADS and Y0_DLEAF)
+        yc1, yc2 = couples([p.LW_Y + i for i in sorted(eqfirst) if p.LW_Y + i not in sh])
+        xc1, xc2 = couples([p.LW_X + j for j in range(0, n, 2) if xpair(j) and p.LW_X + j not in sh])
     # fuse: the updates run eq rows, then the inequality rows that are not part of a fused pair, then the box-row pairs together with
     # the x update of their two variables (a variable's W register is rewritten there: every row that reads it as x~ went before),
     # then the other x updates, then the right-hand-side pushes of the leaf rows that could not be fused
@@ -1248,7 +1189,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
             def fp0(g, r=r, zw=zw):
                 # y == 0: t3 = z, z_new = t, y_new = 0 -- five of the nine operations, no y word
                 z, L_ = VP(g[0]), VP(g[1])
-                di = SB(S_DLEAF, S_DLEAF % 2) if Y0_DLEAF else VP(g[2])
+                di = SB(S_DLEAF, S_DLEAF % 2)
                 if zw in zc1:                                        # first pair of a float4: the second one writes both
                     a_, b_ = TPK(npk[0], 4), TPK(npk[0], 0)
                 elif zw in zc2:
@@ -1271,10 +1212,10 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
                 if zw not in zc1:
                     npk[0] += 1
             if y0:
-                rop(B_OTHER, [S2(zw), C2(p.lpos[r["j"]])] + ([] if Y0_DLEAF else [("A2", k, rb["k"])]), fp0)
-                if fuse:          # the pair's pushes into the next rhs: after the x updates
-                    B_PUSH.append(dict(srcs=[S2(zw), C2(p.lpos[r["j"]])],
-                                       emit=lambda g, r=r: _pk(e, "v_pk_fma_f32", p.wreg[r["r"]], [VP(g[1]), VP(g[0]), VP(p.wreg[r["r"]])])))
+                rop(B_OTHER, [S2(zw), C2(p.lpos[r["j"]])], fp0)          # (a packed y0 body fuses)
+                # the pair's pushes into the next rhs: after the x updates
+                B_PUSH.append(dict(srcs=[S2(zw), C2(p.lpos[r["j"]])],
+                                   emit=lambda g, r=r: _pk(e, "v_pk_fma_f32", p.wreg[r["r"]], [VP(g[1]), VP(g[0]), VP(p.wreg[r["r"]])])))
             else:
                 op([("L", yw), ("L", zw), C(p.lpos[r["j"]]), ("A2", k, rb["k"])], fp)
             continue
@@ -1294,9 +1235,9 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
                     B_PUSH.append(dict(srcs=[S(yw), C(p.lpos[r["j"]]), src_of(("l", i))],
                                        emit=lambda g, r=r: (e("v_fma_f32", v(T(0)), "-" + v(g[0]), sRe, v(g[2])),
                                                             e("v_fmac_f32", W(r["r"]), v(g[1]), v(T(0))))))
-            elif pack and "4" in PACK_PARTS and i in eqskip2:
+            elif pack and i in eqskip2:
                 pass
-            elif pack and "4" in PACK_PARTS and i in eqfirst:
+            elif pack and i in eqfirst:
                 eqskip2.add(i + 1)
 
                 def f2u(g, k=k, yw=yw):
@@ -1344,7 +1285,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
                 z = v(g[0])
                 t3, nu, t2, tt = (v(T(q)) for q in range(4))
                 if r["leaf"]:
-                    e("v_mul_f32", nu, z, "s%d" % S_DLEAF if Y0_DLEAF else v(g[2]))
+                    e("v_mul_f32", nu, z, "s%d" % S_DLEAF)
                     e("v_fmac_f32", nu, v(g[1]), W(r["r"]))
                 else:
                     nu = W(k)
@@ -1360,7 +1301,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
                     sc.lds_write(zw, T(3))
                 if fuse and not r["leaf"]:
                     e("v_mov_b32", W(k), tt)                                  # next rhs of the row: z_new (y == 0)
-            rop(B_OTHER, [S(zw)] + ([C(p.lpos[r["j"]])] + ([] if Y0_DLEAF else [("A", k)]) if r["leaf"] else []), f0)
+            rop(B_OTHER, [S(zw)] + ([C(p.lpos[r["j"]])] if r["leaf"] else []), f0)
             if fuse and r["leaf"]:
                 B_PUSH.append(dict(srcs=[S(zw), C(p.lpos[r["j"]])],
                                    emit=lambda g, r=r: e("v_fmac_f32", W(r["r"]), v(g[1]), v(g[0]))))
@@ -1368,11 +1309,8 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
         if loose:
             srcs, nfix = [("L", yw), ("L", zw)], 2
         else:
-            srcs = [("L", yw), ("L", zw), src_of(("l", i)), src_of(("u", i)), src_of(("rinv", i))]
-            nfix = 5
-            if not KNOB["rho_select"]:
-                srcs.append(src_of(("rho", i)))
-                nfix = 6
+            srcs = [("L", yw), ("L", zw), src_of(("l", i)), src_of(("u", i)), src_of(("rinv", i)), src_of(("rho", i))]
+            nfix = 6
         if r["leaf"]:
             srcs += [C(p.lpos[r["j"]]), ("A", k)]
 
@@ -1386,13 +1324,6 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
             t3, nu, t2, tt, t4, d = (v(T(q)) for q in range(6))
             if loose:
                 rho = "s%d" % S_RHOMIN
-            elif KNOB["rho_select"]:
-                rho = v(T(6))
-                # rho of the row: the class constant whose 1/rho this is (auxil.c:103-145 assigns one of three)
-                e("v_cmp_eq_f32", "vcc", "s%d" % S_RINV0, rinv)
-                e("v_cndmask_b32", rho, v(p.V_RHOMIN), v(p.V_RHO0), "vcc")
-                e("v_cmp_eq_f32", "vcc", sRe, rinv)
-                e("v_cndmask_b32", rho, rho, v(p.V_RHOEQ), "vcc")
             else:
                 rho = v(g[5])
             e("v_fma_f32", t3, "-" + rinv, y, z)                          # z - y/rho (the rhs again)
@@ -1424,7 +1355,6 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
         ops.extend(B_EQ + B_OTHER + B_PAIR)
     if capture and group:
         # x_prev goes over the leaf block of L, which ANY wave's row updates above still read: meet once more
-        assert not fuse
         op([], lambda g: (e("s_waitcnt", "lgkmcnt(0)"), e("s_barrier")))
         ops.append(dict(flush=True))
     jskip = set(fused_x)
@@ -1432,7 +1362,7 @@ def body(e, p, capture=False, loose=False, y0=False, rhs=True, fuse=False, own=A
         k = p.pinv[j]
         if j in jskip or not own.var(j):
             continue
-        if "3" in PACK_PARTS and xpair(j) and j + 1 not in fused_x:
+        if xpair(j) and j + 1 not in fused_x:
             jskip.add(j + 1)
 
             def fx2(g, j=j):
@@ -1579,7 +1509,7 @@ def prologue_tail(e, p, loose=False, homes=(), own=ALL):
             e("s_add_u32", "s%d" % S_SP, "s%d" % S_S, blk * BLOCK * 256)
             e("s_addc_u32", "s%d" % (S_SP + 1), "s%d" % (S_S + 1), 0)
         kind, where = p.once[item]
-        dst = "a%d" % where if kind == "A" else "v%d" % where if kind == "V" else "v%d" % (V_W + q)   # (W: landing zone)
+        dst = "v%d" % where if kind == "V" else "v%d" % (V_W + q)   # (W: landing zone)
         e("global_load_dword", dst, "v%d" % V_LANE, "s[%d:%d]" % (S_SP, S_SP + 1), ((idx + q) % BLOCK) * 256)
     e("s_waitcnt", "vmcnt(0)")
     for q, item in enumerate(p.extra):
@@ -1588,10 +1518,6 @@ def prologue_tail(e, p, loose=False, homes=(), own=ALL):
             base, off = lds_addr(where)
             e("ds_write_b32", base, "v%d" % (V_W + q), off)
     e("s_waitcnt", "lgkmcnt(0)")
-    if KNOB["rho_select"]:
-        e("v_mov_b32", "v%d" % p.V_RHO0, "s%d" % S_RHO0)
-        e("v_mov_b32", "v%d" % p.V_RHOEQ, "s%d" % S_RHOEQ)
-        e("v_mov_b32", "v%d" % p.V_RHOMIN, f32bits(float(np.float32(RHO_MIN_F32))))
     if not homes and own.ghome:
         homes = {it: ("A", a_) for it, a_ in own.ghome.items()}
     preloads(e, p, homes, own)
@@ -1652,7 +1578,7 @@ def prologue_fast(e, p, res, loose=False, y0check=False, own=ALL, group=False):
     assert p.LW_X + s.nnzA <= 640
     G = V_END - V_W - (1 if y0check else 0)      # landing registers V_W ..; y0check keeps the last one as its accumulator
     A_p_ = list(s.tables["A_p"])
-    own_a = [k for j in range(s.n) if own.fvar(j) for k in range(A_p_[j], A_p_[j + 1])]      # (what this wave FACTORISES)
+    own_a = [k for j in range(s.n) if own.var(j) for k in range(A_p_[j], A_p_[j + 1])]      # (what this wave FACTORISES)
     for g in range(0, len(own_a), G):
         ks = own_a[g:g + G]
         for q, k in enumerate(ks):
@@ -1669,7 +1595,7 @@ def prologue_fast(e, p, res, loose=False, y0check=False, own=ALL, group=False):
     pool0 = v_rinv + len(gen)
     assert pool0 + 30 <= p.V_RING
     for j in sorted(res.it_p):
-        if own.fvar(j):
+        if own.var(j):
             sload(v_p + res.pidx[j], res.it_p[j])
     items = p.stream + p.extra
     for q, i in enumerate(gen):
@@ -1686,11 +1612,6 @@ def prologue_fast(e, p, res, loose=False, y0check=False, own=ALL, group=False):
     factor_emit(e, s, p, p.LW_X, v_p, v_rinv, dict(p.zpos), S_SIGMA, S_RINVEQ, list(range(pool0, p.V_RING - 12)),
                 list(range(p.V_LAND, p.V_LAND + p.NLAND)) + list(range(p.V_RING - 12, p.V_RING)), v_fmin, own)
     _lstamp(e, own, 2)
-    for q, (k, word) in enumerate(sorted(own.hand_out.items()) if not FACTOR_SPLIT else []):   # a cut component: 1/D of the partner's half -> LDS
-        t = p.V_TT + q % 4                 # (V_TT + N_TT - 1 is the pivot accumulator)
-        e("v_accvgpr_read_b32", "v%d" % t, "a%d" % k)
-        base, off = lds_addr(word)
-        e("ds_write_b32", base, "v%d" % t, off)
     base, off = lds_addr(FAC_MIN)
     if group:
         # several waves: the A words above are the other waves' x, y words -- nobody loads its warm start before everybody
@@ -1701,17 +1622,6 @@ def prologue_fast(e, p, res, loose=False, y0check=False, own=ALL, group=False):
         e("s_waitcnt", "lgkmcnt(0)")
         e("s_barrier")
         e("ds_min_f32", base, "v%d" % v_fmin, off)
-        if own.xbar and not FACTOR_SPLIT:
-            # ... and the other half takes its 1/D from there into its own AGPRs; nobody's warm start overwrites the words before
-            hin = sorted(own.hand_in.items())
-            assert len(hin) <= G
-            for q, (k, word) in enumerate(hin):
-                base_, off_ = lds_addr(word)
-                e("ds_read_b32", "v%d" % (V_W + q), base_, off_)
-            e("s_waitcnt", "lgkmcnt(0)")
-            for q, (k, word) in enumerate(hin):
-                e("v_accvgpr_write_b32", "a%d" % k, "v%d" % (V_W + q))
-            e("s_barrier")
     else:
         e("ds_write_b32", base, "v%d" % v_fmin, off)
     e("s_waitcnt", "lgkmcnt(0)")
@@ -1809,90 +1719,85 @@ def program(s, eq_rows, res=None, loose=False, own=ALL, group=False):
     e = Emit()
     assert res is not None or (own.all and not group)
 
-    def loop(**kw):
+    def loop():
         e("s_mov_b32", "s%d" % S_CNT, "s%d" % S_ITERS)
         e("s_cmp_lt_i32", "s%d" % S_CNT, 1)
         e("s_cbranch_scc1", "8f")
         e("label", "7")
-        body(e, p, loose=loose, own=own, **kw)
+        body(e, p, loose=loose, own=own)
         e("s_sub_i32", "s%d" % S_CNT, "s%d" % S_CNT, 1)
         e("s_cmp_gt_i32", "s%d" % S_CNT, 0)
         e("s_cbranch_scc1", "7b")
         e("label", "8")
-        body(e, p, capture=True, loose=loose, own=own, group=group, **kw)
+        body(e, p, capture=True, loose=loose, own=own, group=group)
     if loose:
         # the loose variant exists for the all-assembly route only: always the fast start (the caller passes s30 != 0)
         assert res is not None
         e("s_mov_b32", "s%d" % S_RIMIN, f32bits(float(np.float32(1.0 / QP_RHO_MIN))))
         e("s_mov_b32", "s%d" % S_RHOMIN, f32bits(float(np.float32(QP_RHO_MIN))))
-        if not Y0_VARIANT:
-            prologue_fast(e, p, res, loose=True, own=own, group=group)
-        else:
-            # y0: a loose row's multiplier moves by rho (t - z_new) with z_new = t + y / rho unclipped, so a multiplier that
-            # starts at exactly 0 stays exactly 0 (z_new = t, delta_y = rho * 0) -- in the reference as here. When the warm start
-            # has y == 0 on every inequality row of the wave (a cold start, or any earlier result of this loop), the iterations
-            # below drop those 87 words and their operations (same values: bit-identical), and q / l move into the freed LDS
-            # words instead of being loaded from the stream every iteration. Any other warm start takes the loop after label 20.
-            v_or = prologue_fast(e, p, res, loose=True, y0check=True, own=own, group=group)
-            e("v_and_b32", "v%d" % v_or, 0x7FFFFFFF, "v%d" % v_or)
-            e("v_cmp_ne_u32", "vcc", 0, "v%d" % v_or)
-            e("s_cbranch_vccnz", "20f")
-            dleaf = [k for k in p.y0_dleaf if own.k(k)]
-            if Y0_DLEAF and dleaf:
-                e("v_accvgpr_read_b32", "v%d" % v_or, "a%d" % dleaf[0])
-                e("s_nop", 0)
-                e("v_readfirstlane_b32", "s%d" % S_DLEAF, "v%d" % v_or)
-            y0_fill(e, p, own)
-            prologue_tail(e, p, True, p.y0_home, own)
-            l_homes_fill(e, p, own, y0=True)
-            _lstamp(e, own, 5)
-            if not Y0_FUSE:
-                loop(y0=True)
-            else:
-                # four bodies: the first iteration forms its right-hand side the classic way and, like every middle one, leaves
-                # the NEXT one's in the W registers; the capturing iteration starts at the solves; a single iteration is plain
-                e("s_mov_b32", "s%d" % S_CNT, "s%d" % S_ITERS)
-                e("s_cmp_lt_i32", "s%d" % S_CNT, 1)
-                e("s_cbranch_scc1", "30f")
-                body(e, p, loose=True, y0=True, rhs=True, fuse=True, own=own)
-                e("s_sub_i32", "s%d" % S_CNT, "s%d" % S_CNT, 1)
-                e("s_cmp_lt_i32", "s%d" % S_CNT, 1)
-                e("s_cbranch_scc1", "8f")
-                e("label", "7")
-                body(e, p, loose=True, y0=True, rhs=False, fuse=True, own=own)
-                e("s_sub_i32", "s%d" % S_CNT, "s%d" % S_CNT, 1)
-                e("s_cmp_gt_i32", "s%d" % S_CNT, 0)
-                e("s_cbranch_scc1", "7b")
-                e("label", "8")
-                state_writeback(e, p, own)
-                body(e, p, capture=True, loose=True, y0=True, rhs=False, own=own, group=group)
-                e("s_branch", "31f")
-                e("label", "30")
-                body(e, p, capture=True, loose=True, y0=True, own=own, group=group)
-                e("label", "31")
-            y0_restore(e, p, own)
-            e("s_branch", "29f")
-            e("label", "20")
-            g_homes_fill(e, p, own)
-            prologue_tail(e, p, True, own=own)
-            l_homes_fill(e, p, own)
-            _lstamp(e, own, 5)
-            loop()
-            e("label", "29")
-            epilogue(e, p)
-            if LOOP_STAMPS and (own.all or own.wave == 0):
-                _lstamp(e, own, 6)
-                # intervals: A -> LDS, factorisation, barrier, warm start, y0 fill + preloads, the iterations -> stream items
-                e("s_add_u32", "s%d" % S_SP, "s%d" % S_S, (STAMP_ITEM0 // BLOCK) * BLOCK * 256)
-                e("s_addc_u32", "s%d" % (S_SP + 1), "s%d" % (S_S + 1), 0)
-                for k in range(6):
-                    e("s_sub_u32", "s%d" % (60 + 2 * k), "s%d" % (62 + 2 * k), "s%d" % (60 + 2 * k))
-                    e("v_cvt_f32_u32", "v%d" % (p.V_TT + k), "s%d" % (60 + 2 * k))
-                    e("global_store_dword", "v%d" % V_LANE, "v%d" % (p.V_TT + k), "s[%d:%d]" % (S_SP, S_SP + 1), ((STAMP_ITEM0 + k) % BLOCK) * 256)
-                e("s_waitcnt", "vmcnt(0)")
-            if group:
-                e("s_barrier")        # every wave's x, y, z, x_prev, delta_y words are in LDS for whoever reads them next
-            return e.ins, p
+        # y0: a loose row's multiplier moves by rho (t - z_new) with z_new = t + y / rho unclipped, so a multiplier that
+        # starts at exactly 0 stays exactly 0 (z_new = t, delta_y = rho * 0) -- in the reference as here. When the warm start
+        # has y == 0 on every inequality row of the wave (a cold start, or any earlier result of this loop), the iterations
+        # below drop those 87 words and their operations (same values: bit-identical), and q / l move into the freed LDS
+        # words instead of being loaded from the stream every iteration. Any other warm start takes the loop after label 20.
+        v_or = prologue_fast(e, p, res, loose=True, y0check=True, own=own, group=group)
+        e("v_and_b32", "v%d" % v_or, 0x7FFFFFFF, "v%d" % v_or)
+        e("v_cmp_ne_u32", "vcc", 0, "v%d" % v_or)
+        e("s_cbranch_vccnz", "20f")
+        dleaf = [k for k in p.y0_dleaf if own.k(k)]
+        if dleaf:
+            e("v_accvgpr_read_b32", "v%d" % v_or, "a%d" % dleaf[0])
+            e("s_nop", 0)
+            e("v_readfirstlane_b32", "s%d" % S_DLEAF, "v%d" % v_or)
+        y0_fill(e, p, own)
+        prologue_tail(e, p, True, p.y0_home, own)
+        l_homes_fill(e, p, own, y0=True)
+        _lstamp(e, own, 5)
+        if True:
+            # four bodies: the first iteration forms its right-hand side the classic way and, like every middle one, leaves
+            # the NEXT one's in the W registers; the capturing iteration starts at the solves; a single iteration is plain
+            e("s_mov_b32", "s%d" % S_CNT, "s%d" % S_ITERS)
+            e("s_cmp_lt_i32", "s%d" % S_CNT, 1)
+            e("s_cbranch_scc1", "30f")
+            body(e, p, loose=True, y0=True, own=own)
+            e("s_sub_i32", "s%d" % S_CNT, "s%d" % S_CNT, 1)
+            e("s_cmp_lt_i32", "s%d" % S_CNT, 1)
+            e("s_cbranch_scc1", "8f")
+            e("label", "7")
+            body(e, p, loose=True, y0=True, rhs=False, own=own)
+            e("s_sub_i32", "s%d" % S_CNT, "s%d" % S_CNT, 1)
+            e("s_cmp_gt_i32", "s%d" % S_CNT, 0)
+            e("s_cbranch_scc1", "7b")
+            e("label", "8")
+            state_writeback(e, p, own)
+            body(e, p, capture=True, loose=True, y0=True, rhs=False, own=own, group=group)
+            e("s_branch", "31f")
+            e("label", "30")
+            body(e, p, capture=True, loose=True, y0=True, own=own, group=group)
+            e("label", "31")
+        y0_restore(e, p, own)
+        e("s_branch", "29f")
+        e("label", "20")
+        g_homes_fill(e, p, own)
+        prologue_tail(e, p, True, own=own)
+        l_homes_fill(e, p, own)
+        _lstamp(e, own, 5)
+        loop()
+        e("label", "29")
+        epilogue(e, p)
+        if LOOP_STAMPS and (own.all or own.wave == 0):
+            _lstamp(e, own, 6)
+            # intervals: A -> LDS, factorisation, barrier, warm start, y0 fill + preloads, the iterations -> stream items
+            e("s_add_u32", "s%d" % S_SP, "s%d" % S_S, (STAMP_ITEM0 // BLOCK) * BLOCK * 256)
+            e("s_addc_u32", "s%d" % (S_SP + 1), "s%d" % (S_S + 1), 0)
+            for k in range(6):
+                e("s_sub_u32", "s%d" % (60 + 2 * k), "s%d" % (62 + 2 * k), "s%d" % (60 + 2 * k))
+                e("v_cvt_f32_u32", "v%d" % (p.V_TT + k), "s%d" % (60 + 2 * k))
+                e("global_store_dword", "v%d" % V_LANE, "v%d" % (p.V_TT + k), "s[%d:%d]" % (S_SP, S_SP + 1), ((STAMP_ITEM0 + k) % BLOCK) * 256)
+            e("s_waitcnt", "vmcnt(0)")
+        if group:
+            e("s_barrier")        # every wave's x, y, z, x_prev, delta_y words are in LDS for whoever reads them next
+        return e.ins, p
     elif group:
         prologue_fast(e, p, res, own=own, group=True)          # (a shared block always factorises itself: the fast start)
         g_homes_fill(e, p, own)
@@ -2087,7 +1992,6 @@ def reference_iterations(p, d, iters, alpha, sigma):
 # Arithmetic = the pass of codegen_qp.emit_structure statement by statement, except that 1/sqrt is v_rsq_f32 + one Newton
 # step and the two divisions v_rcp_f32 + Newton (+ a correction step for csum / n): each within an ulp of the IEEE results.
 RZ_MIN, RZ_MAX = 1e-4, 1e4
-RUIZ_WQ = os.environ.get("UMPC_QP_RUIZ_WQ", "1") == "1"
 
 
 class QuadWriter:
@@ -2136,7 +2040,7 @@ class RuizPlan:
         # three register quads that collect consecutive words of A, D and E for one ds_write_b128 each (round 3: the pass
         # wrote its 505 words back one ds_write_b32 at a time)
         self.V_WQ = (max(self.V_TT + self.NT, 211) + 1) // 2 * 2        # (v210 = V_RLANE is an input of the block)
-        self.WQ = RUIZ_WQ and self.V_WQ + 12 <= V_END
+        self.WQ = self.V_WQ + 12 <= V_END
         self.n_land = 0
         self.A_DT, self.A_P = 0, self.n
         self.A_Q = self.A_P + self.nnzP
@@ -2232,14 +2136,14 @@ class RuizSplit:
         assert w0 <= p.LW_END, (w0, p.LW_END)
 
 
+# landing registers the residual block keeps in flight: all of them. With 12 the block is not slower (78 against 82 us for the
+# interval around it, profiles/r04_p5f_res_nland.txt): it is not bound by the latency of its landing stream.
+RES_NLAND = NLAND
 S_RWAVE = 26                       # ruiz_group_program: s26 = the wave's index in its workgroup
 S_AV, S_PV, S_QV = 4, 6, 8          # s[4:5] Av rows, s[6:7] Pv rows, s[8:9] q rows (the block's inputs, [k][B] floats)
 S_RSB, V_RLANE = 24, 210           # Ruiz block with a residual stream: s[24:25] = the wave's stream block, v210 = 4*lane
 S_RMIN, S_RMAX = 20, 21            # 1e-4, 1e4 (float bits, set by the block)
 RUIZ_STAMPS = os.environ.get("UMPC_QP_RUIZ_STAMPS") == "1"     # (diagnostics: see ruiz_program)
-RUIZ_HOMES = os.environ.get("UMPC_QP_RUIZ_HOMES", "1") == "1"   # (A/B switch: ruiz_program, shared blocks)
-RUIZ_FAST_LIMIT = os.environ.get("UMPC_QP_RUIZ_FAST_LIMIT", "1") == "1"   # (A/B switch: one wave-wide limit_scaling test per pass)
-RUIZ_LEAN = os.environ.get("UMPC_QP_RUIZ_LEAN", "1") == "1"     # (A/B switch: in-place operations on the register homes, v_max3_f32)
 LOOP_STAMPS = os.environ.get("UMPC_QP_LOOP_STAMPS") == "1"     # (diagnostics: see program(); the residual block copies the items)
 STAMP_ITEM0 = 2040                 # spare items at the end of a wave's stream block (codegen_qp.ASM_STREAM_ITEMS = 2048)
 
@@ -2262,7 +2166,7 @@ def ruiz_program(s, res=None, split=None, wave=0):
     # A wavefront of a shared block touches a quarter of the rows: the Et registers of the others hold ITS entries of A and of
     # D across the passes (RA, RD) -- no LDS round trip per pass for them (an LDS instruction costs a lone wave ~6 ns), and
     # none at all: nothing downstream of a shared block reads A or D from LDS (the factorisation and the residual block take
-    # them from the residual stream). RUIZ_HOMES=0: the LDS form (A/B switch).
+    # them from the residual stream).
     RA, RD, HV = {}, {}, {}
 
     def asrc(a_):
@@ -2277,7 +2181,7 @@ def ruiz_program(s, res=None, split=None, wave=0):
 
     def adst(a_):
         return v(HV[a_]) if a_ in HV else "a%d" % a_
-    if sp is not None and res is not None and RUIZ_HOMES:
+    if sp is not None and res is not None:
         idle = [p.V_ET + i for i in range(m) if wave not in sp.touch[i]]
         assert len(idle) >= len(aq) + len(cols), (len(idle), len(aq), len(cols))
         RA = dict(zip(aq, idle))
@@ -2395,13 +2299,13 @@ def ruiz_program(s, res=None, split=None, wave=0):
     fast_cols = []                       # register homes that hold column NORMS until the wave-wide limit test below
     for j in cols:
         ents = list(range(p.A_p[j], p.A_p[j + 1]))
-        if RUIZ_LEAN and all(q in RA for q in ents) and (p.pidx[j] < 0 or p.A_P + p.pidx[j] in HV):
+        if all(q in RA for q in ents) and (p.pidx[j] < 0 or p.A_P + p.pidx[j] in HV):
             # every operand of the column's norm in a register (shared blocks): up to three per v_max3_f32 (max is exact and
             # order-free: the same bits as the chain of v_max_f32 below), the row norms as before
             def fcol(g, j=j, ents=ents, firsts=tuple(p.A_i[q] not in touched for q in ents)):
                 opnds = ([HV[p.A_P + p.pidx[j]]] if p.pidx[j] >= 0 else []) + [RA[q] for q in ents]
                 head, rest = opnds[:3], opnds[3:]
-                nrm = HV[p.A_DT + j] if (RUIZ_FAST_LIMIT and p.A_DT + j in HV) else T(0)      # (limited wave-wide below)
+                nrm = HV[p.A_DT + j] if p.A_DT + j in HV else T(0)      # (limited wave-wide below)
                 if not opnds:
                     e("v_mov_b32", v(nrm), 0)
                 if len(head) == 3:
@@ -2420,7 +2324,7 @@ def ruiz_program(s, res=None, split=None, wave=0):
                     e("v_max_f32", ET(i), ab(v(RA[q])) if first else ET(i), ab(v(RA[q])))
             op([], fcol)
             touched.update(p.A_i[q] for q in ents)
-            if RUIZ_FAST_LIMIT and p.A_DT + j in HV:
+            if p.A_DT + j in HV:
                 fast_cols.append(HV[p.A_DT + j])
                 continue
         else:
@@ -2439,7 +2343,7 @@ def ruiz_program(s, res=None, split=None, wave=0):
 
         def fin(g, j=j):
             limit(T(0), T(1))
-            if RUIZ_LEAN and p.A_DT + j in HV:
+            if p.A_DT + j in HV:
                 # straight into the column scaling's register home: no copy, and no wait state either (the next VALU
                 # instruction starts the next column and does not read it)
                 e("v_rsq_f32", v(HV[p.A_DT + j]), v(T(0)))
@@ -2496,7 +2400,7 @@ def ruiz_program(s, res=None, split=None, wave=0):
     op([], lambda g: stamp(3))
     op([], lambda g: (e("v_mov_b32", v(T(4)), 0), e("v_mov_b32", v(T(5)), 0)))
     for j in cols:
-        lean = RUIZ_LEAN and p.A_DT + j in HV
+        lean = p.A_DT + j in HV
         DTJ = HV[p.A_DT + j] if lean else T(7)       # dt of the column: its register home itself (shared blocks), else a copy
         if not lean:
             op([asrc(p.A_DT + j)], lambda g: e("v_mov_b32", v(T(7)), v(g[0])))
@@ -2832,10 +2736,7 @@ def res_program(s, eq_rows, ap, res, own=ALL, nw=1):
     pl = P_()
     pl.V_RING, pl.V_LAND, pl.V_AT, pl.n_land = R.V_RING, R.V_LAND, R.V_AT, R.n_land
     pl.land_map = None if own.all else [it - res.it_rows for it in land]
-    # (diagnostics: fewer landing registers in use -> fewer stream loads in flight; if the block's time follows 1 / this,
-    # it is bound by the latency of its landing stream)
-    pl.NLAND = int(os.environ.get("UMPC_QP_RES_NLAND", str(NLAND)))
-    assert 8 <= pl.NLAND <= NLAND
+    pl.NLAND = RES_NLAND
     sc = Sched(e, pl, 0)
     # the landing stream starts at item it_rows: pointer and block bookkeeping relative to it
     e("s_add_u32", "s%d" % S_SP, "s%d" % S_S, res.it_rows * 256)
@@ -2865,8 +2766,6 @@ def res_program(s, eq_rows, ap, res, own=ALL, nw=1):
         # Stores count in vmcnt like loads, in issue order: the scheduler must know about them, or its `vmcnt(N)` before a
         # landing item (N = the LOADS issued since) also drains every store issued since -- an exposed HBM write latency per
         # row (round 2: 82 us for this 7.7 k-instruction block). Registered as VMEM operations nobody waits for.
-        if os.environ.get("UMPC_QP_RES_NOSTORE") == "1":          # (timing experiment: wrong results)
-            return
         sc.vm_at[sc.nvm] = len(e.ins)
         sc.nvm += 1
         e("global_store_dword", "v0", v(reg), "s[%d:%d]" % (b, b + 1), 0)
@@ -3061,7 +2960,7 @@ def factor_emit(e, s, p, lw_a, v_p, v_rinv, gen_pos, s_sigma, s_rinveq, v_pool, 
     t = s.tables
     pidx = list(t["pidx"])
     v = lambda r: "v%d" % r
-    fops = [op_ for op_ in s.factor_ops if own.fk(op_["k"])]     # (components factorise independently: LoopSplit)
+    fops = [op_ for op_ in s.factor_ops if own.k(op_["k"])]     # (components factorise independently: LoopSplit)
     reused = sorted({j for op_ in fops for (_, upd, _) in op_["elim"] for (j, _) in upd})
     assert len(reused) <= len(v_pin), (len(reused), len(v_pin))
     pin = {j: v_pin[q] for q, j in enumerate(reused)}
@@ -3077,7 +2976,7 @@ def factor_emit(e, s, p, lw_a, v_p, v_rinv, gen_pos, s_sigma, s_rinveq, v_pool, 
 
     def op(srcs, fn):
         ops.append(dict(srcs=srcs, emit=fn))
-    split = own.xbar and FACTOR_SPLIT
+    split = own.xbar
     met = [not split]
 
     def meet():
@@ -3182,8 +3081,6 @@ def _f32_strict_bounds():
 
 
 S_GWAVE = 28                       # glue_group_program: s28 = the wave's index in its workgroup
-GLUE_TWO_PASS = os.environ.get("UMPC_QP_GLUE_TWO_PASS", "1") == "1"   # (A/B switch: glue_program, shared blocks)
-GLUE_BALANCE = os.environ.get("UMPC_QP_GLUE_BALANCE", "1") == "1"     # (A/B switch: equality and other rows dealt out separately)
 
 
 def glue_program(s, eq_rows, p, res, rp, split=None):
@@ -3194,7 +3091,7 @@ def glue_program(s, eq_rows, p, res, rp, split=None):
     n, m = s.n, s.m
     wave, nw = split if split is not None else (0, 1)
     my_rows = [i for i in range(m) if i * nw // m == wave]
-    if split is not None and GLUE_TWO_PASS and GLUE_BALANCE:
+    if split is not None:
         # a quarter of the equality rows AND a quarter of the other rows each: when the robots take the loose loop nothing of the
         # other rows is stored, and the equality rows -- all of the work that is left -- must not sit on two of the four waves
         eqr, ineqr = [i for i in range(m) if i in set(int(i_) for i_ in eq_rows)], [i for i in range(m) if i not in set(int(i_) for i_ in eq_rows)]
@@ -3265,9 +3162,9 @@ def glue_program(s, eq_rows, p, res, rp, split=None):
     put_items = []
     # A shared block decides FIRST whether the 64 robots take the loose loop (every inequality row of every robot a loose row:
     # the reference's problem) and then leaves the per-row items of those rows -- 1/rho, l, u, rho: what only the general loop
-    # and the C++ routes read -- unwritten: 5 of the 7 stores of such a row, 1.7 kB per robot-tick (GLUE_TWO_PASS; the C++
+    # and the C++ routes read -- unwritten: 5 of the 7 stores of such a row, 1.7 kB per robot-tick (the C++
     # residual phase forms l E, u E of those rows itself: codegen_qp.emit_fast_route_reload). One chunk of rows per wave.
-    two_pass = split is not None and GLUE_TWO_PASS and len(my_rows) <= R
+    two_pass = split is not None and len(my_rows) <= R
     for c00 in range(0, len(my_rows), R):
         rows = my_rows[c00:c00 + R]
         c0 = rows[0]

@@ -104,38 +104,29 @@ IMP_BYTES = 16            # pointer, stride, one word of padding (the block is r
 S_IMP = 32                # s[32:33] the slice address, s34 the stride / low offset word, s35 the high offset word (dead lane masks)
 
 VFIRST, VEND = 2, 256
-XV_N, XV_B = 10, 246      # L entries kept in VGPRs beyond the loop's fixed layout (asmgen.XV_COUNT / XV_BASE)
-# generator switches for A/B timing of variants on one box (tools/build_variant.py); defaults = the shipped kernel
-# v246..v255 hold either ten L words (UMPC_ASM_RING=4) or two more slots of the LDS read ring plus two L words (6, the
-# default: with six slots the reads run 20 operations ahead and waits merge in pairs, 1.2 % faster, profiles/README.md)
-OPT_RING = int(os.environ.get("UMPC_ASM_RING", "6"))
-assert OPT_RING in (4, 6)
-OPT_XV = os.environ.get("UMPC_ASM_XV", "1") == "1"
-if OPT_RING == 6:
-    XV_N, XV_B = 2, 254
-# LIMIT_FAST: wave-wide min / max test that skips the exact limit_scaling sequence (-1 500 instructions per step).
-# Measured SLOWER on the MI355X (same box, K = 500: 0.1261 vs 0.1239 ms per step): five VALU -> SGPR -> s_cbranch_vccz
-# round trips per Ruiz pass cost more than the 150 instructions they skip. Off.
-OPT_LIMIT_FAST = os.environ.get("UMPC_ASM_LIMIT_FAST", "0") == "1"
-# ZSKIP: the right-hand side of entries whose q / l is structurally zero is formed without the AGPR read (asmgen.body)
-OPT_ZSKIP = os.environ.get("UMPC_ASM_ZSKIP", "1") == "1"
-# NT: the once-per-step STREAMING rows (state, ctrl, ref, out, stats: read in phase A, rewritten in phase C) carry the
-# non-temporal hint, so that the 85 workspace rows D, E, c a wave parks across its 50 iterations (21.7 KB per wave, 2.8 MB per
-# XCD against a 4-MB L2) are not evicted by them and need not round-trip through HBM. "1" (default, lane form): loads and
-# stores, "ld" / "st": one side, "0": off. Measured (tools/ab_nt.sh, profiles/r05_nt_ab.txt, one box, K = 500): read bytes per
-# robot-step 969 -> 616 (algorithmic 604), written 977 -> 980, 1.61x -> 1.32x algorithmic; 0.1208 -> 0.1216 ms per step. Either
-# side alone does nothing ("ld": 1071 read; "st": 964).
-OPT_NT = os.environ.get("UMPC_ASM_NT", "1")
+# v246..v255 through the ADMM loop: two more slots of the LDS read ring (six in all, asmgen.ring_base) and two L words in
+# v254 / v255 (lane form; the quad form keeps y there). With six slots the reads run 20 operations ahead and waits merge in
+# pairs, 1.2 % faster than four slots and ten L words (profiles/README.md).
+NRING = 6
+XV_N, XV_B = 2, 254       # L entries kept in VGPRs beyond the loop's fixed layout (asmgen.Homes.xv_count / xv_base)
+# The lane and the quad form differ in four places, each a plain function of `quad`, stated once here:
+#   * L words in VGPRs: XV_N in the lane form, none in the quad form (v254 / v255 hold y there): StepGen.homes.
+#   * streaming hint: the once-per-step STREAMING rows (state, ctrl, ref, out, stats: read in phase A, rewritten in phase C)
+#     carry the non-temporal hint on loads and stores in the lane form only, so that the 85 workspace rows D, E, c a wave
+#     parks across its 50 iterations (21.7 KB per wave, 2.8 MB per XCD against a 4-MB L2) are not evicted by them and need
+#     not round-trip through HBM. Measured (profiles/r05_nt_ab.txt, one box, K = 500): read bytes per robot-step 969 -> 616
+#     (algorithmic 604), written 977 -> 980, 1.61x -> 1.32x algorithmic; 0.1208 -> 0.1216 ms per step. Either side alone
+#     does nothing (loads only: 1071 read; stores only: 964). The quad form serves batches whose whole working set lives in
+#     the eight L2s (0.14-0.44x algorithmic HBM traffic): there the state / ctrl rows are exactly what should stay cached.
+#   * workspace policy: the stores / loads of the parked D, E, c rows carry "nt" in the lane form only. Measured
+#     (profiles/r05_nt_ab.txt, one box, on top of the streaming hint): plain 565 B read + 936 B written per robot-step =
+#     1.24x algorithmic; "nt" on both sides 502 + 779 = 1.06x, same ms per step (0.1206 / 0.1208); sc0 no change; sc1 /
+#     sc0 sc1 (write-through scopes) 805 read = 1.44x.
+#   * the spare AGPRs below (lane form only).
 NT_PTRS = ("state", "ctrl", "ref", "out", "stats")
 # The ten AGPRs nobody owns (the loop: a0..a229, the weights: a230..a245) take c and the first nine D words across the loop
 # instead of workspace rows (lane form only: the quad entry composes words in AGPRs): 10 stores + 10 loads fewer per step
 A_SPARE, N_SPARE_D = 246, 9
-# Cache-policy bits on the workspace stores / loads of the parked D, E, c rows (lane form). Measured (tools/ab_ws.sh,
-# profiles/r05_nt_ab.txt, one box, on top of the streaming hint): plain 565 B read + 936 B written per robot-step = 1.24x
-# algorithmic; "nt" on both sides 502 + 779 = 1.06x, same ms per step (0.1206 / 0.1208); sc0 no change; sc1 / sc0 sc1
-# (write-through scopes) 805 read = 1.44x. Shipped: nt / nt.
-OPT_WS_ST = os.environ.get("UMPC_ASM_WS_ST", "nt")
-OPT_WS_LD = os.environ.get("UMPC_ASM_WS_LD", "nt")
 
 
 class Pool:
@@ -348,9 +339,8 @@ class StepGen:
         self.pool = Pool(self.e)
         self.lab = 20
         self.quad = quad
-        # the quad form serves batches whose whole working set lives in the eight L2s (0.14-0.44x algorithmic HBM traffic):
-        # there the state / ctrl rows are exactly what should stay cached, so the hint is a lane-form matter
-        self.nt = "0" if quad else OPT_NT
+        self.nt = () if quad else ("nt",)      # cache policy of the streaming rows and of the parked workspace rows
+        self.homes = asmgen.Homes(NRING, 0 if quad else XV_N, XV_B)     # the loop's ring and extra homes of L
 
     # ---- small emit helpers -----------------------------------------------------------------------------
     def label(self):
@@ -440,7 +430,7 @@ class StepGen:
         self.rows_ptr(voff, first_row)
         for k, r in enumerate(regs):
             self.e("global_load_dword", r if isinstance(r, str) else v(r), v(voff), sp(S_PTR[ptr]),
-                   *(("nt",) if self.nt in ("1", "ld") and ptr in NT_PTRS else (OPT_WS_LD,) if ptr == "ws" and OPT_WS_LD and not self.quad else ()))
+                   *(self.nt if ptr in NT_PTRS or ptr == "ws" else ()))
             if k + 1 < len(regs):
                 self.adv(voff)
         if own:
@@ -453,7 +443,7 @@ class StepGen:
         self.rows_ptr(voff, first_row)
         for k, r in enumerate(regs):
             self.e("global_store_dword", v(voff), v(r), sp(S_PTR[ptr]),
-                   *(("nt",) if self.nt in ("1", "st") and ptr in NT_PTRS else ()))
+                   *(self.nt if ptr in NT_PTRS else ()))
             if k + 1 < len(regs):
                 self.adv(voff)
         if own:
@@ -734,59 +724,22 @@ class StepGen:
             e("v_max_f32", v(dst), v(dst), "|%s|" % v(regs[0]))
 
     def limit(self, regs, rsq):
-        """limit_scaling (scaling.c:7-14: v < 1e-4 -> 1, v > 1e4 -> 1e4) on every register, then 1/sqrt if rsq.
-        For a list, one running min / max (v_min3 / v_max3, two registers per instruction) decides wave-wide whether
-        ANY value of ANY robot needs limiting -- it never does once the data is equilibrated -- and the exact
-        compare / select / min sequence (software-pipelined: the vcc compare -> select pair never feeds the next
-        instruction) runs only then."""
+        """limit_scaling (scaling.c:7-14: v < 1e-4 -> 1, v > 1e4 -> 1e4) on every register, then 1/sqrt if rsq: the exact
+        compare / select / min sequence, software-pipelined (the vcc compare -> select pair never feeds the next
+        instruction). (A wave-wide min / max test that skips it was measured SLOWER on the MI355X, same box, K = 500: 0.1261
+        vs 0.1239 ms per step -- five VALU -> SGPR -> s_cbranch_vccz round trips per Ruiz pass cost more than the 150
+        instructions they skip.)"""
         e = self.e
         regs = list(regs)
-
-        def exact():
-            prev = None
-            for r in regs + [None]:
-                if r is not None:
-                    e("v_cmp_lt_f32", "vcc", sg(S_C["minscal"]), v(r))
-                if prev is not None:
-                    e("v_min_f32", v(prev), sg(S_C["maxscal"]), v(prev))
-                if r is not None:
-                    e("v_cndmask_b32", v(r), 1.0, v(r), "vcc")
-                prev = r
-        if len(regs) < 6 or not OPT_LIMIT_FAST:
-            exact()
-        else:
-            # two independent min chains and two max chains, interleaved: no instruction reads its predecessor's result
-            mn, mx, mn2, mx2 = [self.pool.get() for _ in range(4)]
-            halves = [regs[0::2], regs[1::2]]
-            chains = [(mn, mx), (mn2, mx2)]
-            pos = [0, 0]
-            while any(pos[h] < len(halves[h]) for h in (0, 1)):
-                for h in (0, 1):
-                    vals, p_ = halves[h], pos[h]
-                    if p_ >= len(vals):
-                        continue
-                    rmin, rmax = chains[h]
-                    if p_ == 0:
-                        take = (vals + [vals[0], vals[0]])[:3]
-                        e("v_min3_f32", v(rmin), v(take[0]), v(take[1]), v(take[2]))
-                        e("v_max3_f32", v(rmax), v(take[0]), v(take[1]), v(take[2]))
-                        pos[h] = 3
-                    else:
-                        take = (vals[p_:p_ + 2] + [vals[p_]])[:2]
-                        e("v_min3_f32", v(rmin), v(rmin), v(take[0]), v(take[1]))
-                        e("v_max3_f32", v(rmax), v(rmax), v(take[0]), v(take[1]))
-                        pos[h] = p_ + 2
-            e("v_min_f32", v(mn), v(mn), v(mn2))
-            e("v_max_f32", v(mx), v(mx), v(mx2))
-            self.pool.free(mn2, mx2)
-            lab = self.label()
-            e("v_cmp_gt_f32_e64", sp(S_M0), sg(S_C["minscal"]), v(mn))
-            e("v_cmp_lt_f32", "vcc", sg(S_C["maxscal"]), v(mx))
-            e("s_or_b64", "vcc", "vcc", sp(S_M0))
-            e("s_cbranch_vccz", lab + "f")
-            exact()
-            e("label", lab)
-            self.pool.free(mn, mx)
+        prev = None
+        for r in regs + [None]:
+            if r is not None:
+                e("v_cmp_lt_f32", "vcc", sg(S_C["minscal"]), v(r))
+            if prev is not None:
+                e("v_min_f32", v(prev), sg(S_C["maxscal"]), v(prev))
+            if r is not None:
+                e("v_cndmask_b32", v(r), 1.0, v(r), "vcc")
+            prev = r
         if rsq:
             for r in regs:
                 e("v_rsq_f32", v(r), v(r))
@@ -816,7 +769,7 @@ class StepGen:
         colpairs = [(st.xinv[2 * k], st.xinv[2 * k + 1]) for k in range(nx // 2)]
         if nx % 2:
             colpairs.append((st.xinv[nx - 1], None))
-        CH = 6 if OPT_LIMIT_FAST else 3
+        CH = 3
         for c0 in range(0, len(colpairs), CH):
             chunk = colpairs[c0:c0 + CH]
             T = [pool.get2() for _ in chunk]
@@ -1061,7 +1014,6 @@ class StepGen:
         self.rcp_nr(cinv, cs, t)
         voff = pool.get()
         npark = 0 if self.quad else N_SPARE_D
-        WS_ST = (OPT_WS_ST,) if OPT_WS_ST and not self.quad else ()
         self.rows_ptr(voff, npark)     # the kernel's `ws` pointer is the workspace row WS_DS (host side): rows D 0.., E 45.., c 84
         rows_of_col = {}
         for i in range(nc):
@@ -1078,7 +1030,7 @@ class StepGen:
             if j < npark:
                 e("v_accvgpr_write_b32", "a%d" % (A_SPARE + j), v(d))
             else:
-                e("global_store_dword", v(voff), v(d), sp(S_PTR["ws"]), *WS_ST)
+                e("global_store_dword", v(voff), v(d), sp(S_PTR["ws"]), *self.nt)
                 self.adv(voff)
             if j in rows_of_col:
                 e("v_rcp_f32", v(r), v(d))
@@ -1087,7 +1039,7 @@ class StepGen:
                     e("v_mul_f32", v(RE(i)), "|%s|" % v(RA(st.unit[i][0])), v(r))       # E_i = |A_ip| / D_p
         assert asmgen.WS_ES == asmgen.WS_DS + nx and asmgen.WS_C == asmgen.WS_ES + nc
         for i in range(nc):
-            e("global_store_dword", v(voff), v(RE(i)), sp(S_PTR["ws"]), *WS_ST)
+            e("global_store_dword", v(voff), v(RE(i)), sp(S_PTR["ws"]), *self.nt)
             self.adv(voff)
         if npark:
             e("v_accvgpr_write_b32", "a%d" % (A_SPARE + N_SPARE_D), v(cs))
@@ -1144,9 +1096,8 @@ class StepGen:
         for c, r in last_row.items():
             done_at.setdefault(r, []).append(c)
         nL, Dinv = {}, {}
-        # XV_N more L entries live in v246..v255 through the loop (2 AGPR reads per iteration each otherwise)
-        asmgen.XV_COUNT, asmgen.XV_BASE = (XV_N if OPT_XV and not self.quad else 0), XV_B   # (quad: v254 / v255 hold y)
-        pool.reserve(246, 10)         # L words and/or ring slots (OPT_RING)
+        # homes.xv_count more L entries live in v254 / v255 through the loop (2 AGPR reads per iteration each otherwise)
+        pool.reserve(246, 10)         # ring slots and L words (NRING, XV_N)
         t = pool.get()
 
         def retire_dinv(k):
@@ -1158,7 +1109,7 @@ class StepGen:
                 pos = lpos[j]
                 if pos < NLDS:
                     e("ds_write_b32", "v1", v(nL[j]), (pos // 4) * 1024 + (pos % 4) * 4)
-                elif NLDS + NVZ <= pos < NLDS + NVZ + asmgen.XV_COUNT:
+                elif NLDS + NVZ <= pos < NLDS + NVZ + self.homes.xv_count:
                     e("v_mov_b32", v(XV_B + pos - NLDS - NVZ), v(nL[j]))
                 else:
                     e("v_accvgpr_write_b32", "a%d" % (A_L + pos - NLDS), v(nL[j]))
@@ -1250,7 +1201,8 @@ class StepGen:
             e("v_mov_b32", v(pad), 0)
         e("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
         plan = st.plan
-        zk = dict(qzero=st.qzero, lzero=st.lzero) if OPT_ZSKIP else {}
+        # the right-hand side of entries whose q / l is structurally zero is formed without the AGPR read (asmgen.body)
+        zk = dict(qzero=st.qzero, lzero=st.lzero, homes=self.homes)
         asmgen.body(e, s, first=True, capture=True, plan=plan, delta_in_w=True, **zk)
         if self.quad:
             # iterations 2..maxIter on the lane quad: entry transposition, the quad bodies, the broadcast back into the
@@ -1349,21 +1301,20 @@ class StepGen:
         e("v_mov_b32", v(DS(nx)), 0)
         # 2. the controller record goes back now (a cold start, if any, rewrites it below): x, y, z
         zt = [g_() for _ in range(4)]
-        NT_ST = ("nt",) if self.nt in ("1", "st") else ()
         self.rows_ptr(voff, 0)
         for r in range(nx):
-            e("global_store_dword", v(voff), v(XR(r)), sp(S_PTR["ctrl"]), *NT_ST)
+            e("global_store_dword", v(voff), v(XR(r)), sp(S_PTR["ctrl"]), *self.nt)
             self.adv(voff)
         for r in range(nc):
-            e("global_store_dword", v(voff), v(YR(r)), sp(S_PTR["ctrl"]), *NT_ST)
+            e("global_store_dword", v(voff), v(YR(r)), sp(S_PTR["ctrl"]), *self.nt)
             self.adv(voff)
         for r in range(nc):
             if r < neq:
                 t_ = zt[r % 4]
                 e("v_accvgpr_read_b32", v(t_), "a%d" % (A_LO + r))
-                e("global_store_dword", v(voff), v(t_), sp(S_PTR["ctrl"]), *NT_ST)
+                e("global_store_dword", v(voff), v(t_), sp(S_PTR["ctrl"]), *self.nt)
             else:
-                e("global_store_dword", v(voff), v(ZR(r)), sp(S_PTR["ctrl"]), *NT_ST)
+                e("global_store_dword", v(voff), v(ZR(r)), sp(S_PTR["ctrl"]), *self.nt)
             self.adv(voff)
         pool.free(*zt)
         e("s_waitcnt", "vmcnt(0)")
@@ -2205,13 +2156,8 @@ class StepGen:
         self.prologue()
         top = self.label()
         e("label", top)
-        try:
-            asmgen.NRING = OPT_RING
-            self.phase_a()      # factor() switches asmgen's extra-VGPR L homes on (module state) ...
-            self.admm()
-        finally:
-            asmgen.XV_COUNT = 0  # ... for this stream only: asmgen.program() of the C++ kernel must not see them
-            asmgen.NRING = 4
+        self.phase_a()
+        self.admm()
         self.phase_c()
         # reference trajectory: `ref` moves on by `refstep` bytes for the next step (both ref loads of this step, phase A
         # and phase C, are behind us). No SGPR is free for the whole kernel in the quad form, so the word is read from the

@@ -143,11 +143,7 @@ def p5f_analysis(N=10):
     st = p5f_structure(N, grouped=True)
     # elimination order: the two horizon chains cut in the middle (qpstruct.bisect_ordering: an elimination tree of two halves
     # under a two-vertex separator instead of one spine; +14 entries of L at N = 10) -- asmqp.LoopSplit gives the halves to two
-    # wavefronts. UMPC_QP_ORDERING=minfill: the plain min-fill order of rounds 2-4.
-    if os.environ.get("UMPC_QP_ORDERING") == "minfill":
-        from . import symbolic
-        perm = symbolic.min_fill_ordering(qpstruct.kkt_adjacency(st["n"], st["m"], st["A_p"], st["A_i"]), hold=st["hold"])
-        return st, qpstruct.analyse_qp(st["n"], st["m"], st["A_p"], st["A_i"], st["P_cols"], perm=perm)
+    # wavefronts.
     perm = qpstruct.bisect_ordering(st["n"], st["m"], st["A_p"], st["A_i"], parts=st["parts"], hold=st["hold"])
     return st, qpstruct.analyse_qp(st["n"], st["m"], st["A_p"], st["A_i"], st["P_cols"], perm=perm, parts=st["parts"])
 

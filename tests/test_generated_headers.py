@@ -38,15 +38,15 @@ def test_build_refuses_generator_switches(monkeypatch):
     """_lib.build() rewrites tracked headers and the shipped library, so it must refuse to run under a stray
     A/B switch (variants go through tools/build_variant.py into robobee3d_amd/variants/)."""
     from robobee3d_amd import _lib, asmgen
-    monkeypatch.setenv("UMPC_ASM_LIMIT_FAST", "1")
-    assert asmgen.generator_switches() == {"UMPC_ASM_LIMIT_FAST": "1"}
-    assert "UMPC_ASM_LIMIT_FAST=1" in asmgen.switch_banner()
+    monkeypatch.setenv("UMPC_ASM64_TIMING", "1")
+    assert asmgen.generator_switches() == {"UMPC_ASM64_TIMING": "1"}
+    assert "UMPC_ASM64_TIMING=1" in asmgen.switch_banner()
     before = {f: os.path.getmtime(os.path.join(CSRC, f)) for f in ("umpc_step_asm.h", "umpc_admm_asm.h")}
     with pytest.raises(RuntimeError, match="generator switches"):
         _lib.build()
     assert before == {f: os.path.getmtime(os.path.join(CSRC, f)) for f in before}
     monkeypatch.setenv("UMPC_QP_KERNEL", "tables")       # a run-time diagnostic, not a generator switch
-    monkeypatch.delenv("UMPC_ASM_LIMIT_FAST")
+    monkeypatch.delenv("UMPC_ASM64_TIMING")
     assert asmgen.generator_switches() == {}
 
 
@@ -66,3 +66,21 @@ def test_run_time_variables_of_the_host_code_are_not_generator_switches(monkeypa
             assert n in asmgen.NOT_SWITCHES, "%s is read at run time by csrc/ but counts as a generator switch" % n
         monkeypatch.setenv(n, "1")
     assert asmgen.generator_switches() == {}
+
+
+def test_generator_switches_are_listed_and_read():
+    """asmgen.SWITCHES is the list of the generation-time switches: every os.environ read of a name with a switch prefix in the
+    package's Python sources is in it (or is a run-time variable, NOT_SWITCHES), and every listed switch is read somewhere."""
+    import glob
+    import re
+    from robobee3d_amd import asmgen
+    read = set()
+    for path in glob.glob(os.path.join(os.path.dirname(CSRC), "*.py")):
+        read |= set(re.findall(r'os\.environ(?:\.get\(|\[)\s*"(UMPC_[A-Z0-9_]+)"', open(path).read()))
+    read = {n for n in read if n.startswith(asmgen.SWITCH_PREFIXES)}
+    assert {"UMPC_QP_NT_KINDS", "UMPC_ASM64_TIMING", "UMPC_QP_KERNEL"} <= read       # (the pattern finds the reads)
+    assert not set(asmgen.SWITCHES) & set(asmgen.NOT_SWITCHES)
+    for n in sorted(read):
+        assert n in asmgen.SWITCHES or n in asmgen.NOT_SWITCHES, "%s is read from the environment but listed nowhere" % n
+    for n in asmgen.SWITCHES:
+        assert n in read, "%s is listed as a generator switch but nothing reads it" % n

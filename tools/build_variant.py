@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Builds robobee3d_amd/variants/libumpc_<name>.so from the current sources with generator switches taken from the
-environment (UMPC_ASM_*), for A/B timing of step-kernel variants inside ONE gpurun call (select with UMPC_LIB).
-usage: UMPC_ASM_XV=0 tools/build_variant.py noxv
+environment (asmgen.SWITCHES), for timing step-kernel variants next to the shipped library in one session (select with UMPC_LIB).
+usage: UMPC_ASM64_TIMING=1 tools/build_variant.py timing64
        UMPC_VARIANT_DEFS="-DUMPC_SCALING_ITERS=1" tools/build_variant.py ruiz1     (extra compiler flags, timing diagnostics)"""
 import os
 import subprocess
