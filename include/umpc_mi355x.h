@@ -215,7 +215,8 @@ int umpcBatchSetWeights(umpc_batch_t *h, const void *weights);
  * A table and a handle task != 0 exclude each other: whichever of umpcBatchSetRefTrajectory / umpcBatchSetTask comes
  * second is refused (-1). umpcBatchReactive and umpcBatchTaskReference are refused (-1) while a table is set: they
  * evaluate the reference per plant substep / at a free time, and a table has one slice per MPC step (substep-granular
- * references are not built). The WL coupling, per-robot weights, Ib, gain, actualT0, both plant modes and
+ * references are not built); umpcBatchReactiveRollout is the reactive baseline that reads a table, one slice held over
+ * the substeps of each step. The WL coupling, per-robot weights, Ib, gain, actualT0, both plant modes and
  * umpcBatchSetStepKernel 0..3 all combine with a table. Memory: 9 x B x steps scalars (fp32, B = 65 536, 500 steps:
  * 1.2 GB) -- long runs are chunked: fill the next table while one runs, then set it with cursor0 = 0. */
 int umpcBatchSetRefTrajectory(umpc_batch_t *h, const void *tab, long long steps, long long cursor0);
@@ -251,7 +252,8 @@ int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int3
  * advances by K per rollout, so consecutive rollouts continue one table; a rollout that would pass `steps` is refused
  * (-1, umpcLastError) BEFORE anything is launched or copied. Refused (-1): a handle with nsub = 0 (its rollouts never
  * write the state), steps < 1, cursor0 outside [0, steps]. umpcBatchUpdate, umpcBatchPlant, umpcBatchReactive and the
- * B = 1 drop-in neither record nor move the cursor.
+ * B = 1 drop-in neither record nor move the cursor; umpcBatchReactiveRollout, the reactive baseline in closed-loop steps,
+ * records into the same tables (see there).
  * Combines with a reference trajectory, the tasks, per-robot weights, Ib, gain, actualT0, the WL coupling, both plant
  * modes, both dtypes and umpcBatchSetStepKernel 0..3. Memory: (18 (steps + 1) + 9 steps + steps + 2 steps) x B scalars
  * when all four are on -- fp32, B = 65 536, 500 steps: state 2.4 GB, out 1.2 GB -- long runs are chunked: read a full table
@@ -280,6 +282,7 @@ long long umpcBatchHistoryCursor(const umpc_batch_t *h);
  * umpcBatchPlant and the B = 1 drop-in neither apply a slice nor move the cursor. umpcBatchReactive honours the table (the
  * reference's MPC-vs-reactive comparison under one push): it adds slice cursor + j after substep (j + 1) * nsub - 1 and
  * advances the cursor by nsteps / nsub; with a table set it is refused when nsteps % nsub != 0 or the table would be overrun.
+ * umpcBatchReactiveRollout adds slice cursor + k after step k like umpcBatchRollout.
  * The fp32 assembly kernels (lane and quad) and the C++ kernels fp32, fp64 lane and fp64 C++ add the slice in the kernel:
  * one launch, six loads and six adds per robot-step; without a table a step costs a few scalar instructions more. One form
  * is an exception, as for the history: the fp64 kernel with one robot per lane quad (the automatic choice for fp64 at
@@ -395,6 +398,39 @@ const char *umpcBatchKernelName(const umpc_batch_t *h);
  * defaults); out [3][B] last command or NULL; stats as in umpcBatchRollout. */
 int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const void *ref, const void *gains,
                       const void *Ib, const void *thrust_gain, void *out, void *stats, void *stream);
+/* The reactive baseline on the tables of the MPC rollout: the other half of the reference's comparisons (hoverTask, sTask:
+ * controlTest(useMPC=True) against controlTest(useMPC=False) on one task under one push, template/uprightmpc2.py:214-246;
+ * gainTuningSims(useMPC=False), :272-303) as ONE launch that reads and writes what umpcBatchRollout reads and writes.
+ * K closed-loop steps of nsub substeps of dtsim each -- the granularity of umpcBatchRollout, so every table keeps its shape
+ * and meaning. The controller fires at the substeps j of a step with j % every == 0; `every` must divide nsub (a run cut
+ * into several launches then fires at the same substeps). Moments are clipped at +-taulim; gains, Ib, thrust_gain, out
+ * [3][B] or NULL and stats (accumulated per substep) are those of umpcBatchReactive.
+ * The reference of substep j of step k is one of three, chosen once per call:
+ *   handle task      task == NULL and no reference trajectory set: the handle's task at t = t0 + T(k nsub + j) dtsim, the
+ *                    expression of umpcBatchReactive. With nothing else set the call equals umpcBatchReactive(h, K nsub,
+ *                    every, ...) bit for bit in state, out, stats and umpcBatchTime.
+ *   per-robot task   task [B] int32 of UMPC_TASK_* ids, task_params [4][B] in the handle's dtype or NULL (= the handle's),
+ *                    layout as in umpcBatchTaskTable; rows 0..2 of ref are initialPos, task 0 follows its ref column.
+ *                    Evaluated per substep at the same t. Refused while a reference trajectory is set. Robots of different
+ *                    tasks in one wavefront (64 consecutive robots) run their generators one after the other: a sweep
+ *                    keeps the robots of one task adjacent.
+ *   reference table  umpcBatchSetRefTrajectory set: pdes = rows 0..2 of slice ref_cursor + k, held over the substeps of
+ *                    step k; ref may be NULL; the cursor advances by K. No time expression enters.
+ * Impulses (umpcBatchSetImpulses): slice imp_cursor + k is added to dq after the last substep of step k and before anything
+ * of that step is stored -- the placement and the single IEEE add of umpcBatchRollout.
+ * Step history (umpcBatchSetHistory; any record may be off): state slice c = `state` as passed (the kernel stores the words
+ * it loaded: no copy), slice c + k + 1 = the state after step k, kick included; out slice c + k = (thrust, clipped moments)
+ * of the last fire of the step in rows 0..2 and 0 in rows 3..8 (a reactive controller has no accdes); status = 1; info = 0.
+ * The tables stay fully defined -- umpcBatchScore takes them as they are, its row 8 counts nothing -- and `state` / `out`
+ * hold after the call what they hold without a history.
+ * Every range check (trajectory, history, impulses) is made BEFORE the launch; the clock and the three cursors move after
+ * the launch has been accepted and nowhere else. Refused (-1, umpcLastError): h NULL, K < 1, every < 1, nsub % every != 0,
+ * a handle with nsub = 0, state NULL, ref NULL without a table, task_params without task, task with a table set, K * nsub
+ * > 2^31 - 1. Slice offsets are 64-bit: a table may pass 4 GB (the state history does after 455 steps at B = 65 536 in
+ * fp32). Both dtypes, both plant modes. Asynchronous on `stream`. */
+int umpcBatchReactiveRollout(umpc_batch_t *h, int K, int every, void *state, const void *ref, const void *gains,
+                             const int32_t *task, const void *task_params, const void *Ib, const void *thrust_gain, void *out,
+                             void *stats, void *stream);
 /* out [9][B] = (pdes, dpdes, sdes) of the handle's task (template/flight_tasks.py:6-49) at time t_ms, what the
  * step kernel evaluates at an MPC fire; ref as in umpcBatchRollout (rows 0..2 = initialPos for a task). */
 int umpcBatchTaskReference(umpc_batch_t *h, double t_ms, const void *ref, void *out, void *stream);

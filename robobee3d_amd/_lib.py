@@ -25,7 +25,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchDefaultParams", "umpcBatchCreate", "umpcBatchDestroy", "umpcBatchInitCtrl",
            "umpcBatchRollout", "umpcBatchUpdate", "umpcBatchPlant", "umpcBatchAssemble",
            "umpcBatchSize", "umpcBatchDtype", "umpcAxIdx", "umpcKKTPerm", "umpcNnzL",
-           "umpcBatchSetTask", "umpcBatchTime", "umpcBatchSetWeights", "umpcBatchSetStepKernel", "umpcBatchSetGlobalBatch", "umpcBatchGlobalBatch", "umpcBatchReactive", "umpcBatchTaskReference",
+           "umpcBatchSetTask", "umpcBatchTime", "umpcBatchSetWeights", "umpcBatchSetStepKernel", "umpcBatchSetGlobalBatch", "umpcBatchGlobalBatch", "umpcBatchReactive", "umpcBatchReactiveRollout", "umpcBatchTaskReference",
            "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable", "umpcBatchSetHistory", "umpcBatchHistoryCursor",
            "umpcBatchSetImpulses", "umpcBatchImpulseCursor", "umpcBatchScoreInit", "umpcBatchScore", "umpcBatchScoreGroups",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
@@ -250,6 +250,7 @@ def lib():
         L.umpcBatchRollout.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
         L.umpcBatchUpdate.argtypes = [C.c_void_p] + [C.c_void_p] * 9
         L.umpcBatchReactive.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+        L.umpcBatchReactiveRollout.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10
         L.umpcBatchTaskReference.argtypes = [C.c_void_p, C.c_double] + [C.c_void_p] * 3
         L.umpcBatchPlant.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.umpcBatchAssemble.argtypes = [C.c_void_p] + [C.c_void_p] * 10

@@ -146,6 +146,42 @@ def impulse_table(steps, B, events, dtype=torch.float32, device="cpu"):
     return tab
 
 
+# the generators of template/flight_tasks.py: name -> (UMPC_TASK_* id, the keywords that fill the parameter slots in order)
+TASKS = {"ref": (0, ()), "helix": (1, ("trajAmp", "trajFreq", "dz", "useY")),
+         "straightAcc": (2, ("tduration", "vdes")), "flip": (3, ("tstart", "tend")),
+         "perch": (4, ("tend", "trotstart", "trotend", "vdes"))}
+TASK_DEFAULTS = {"trajAmp": 80, "trajFreq": 1, "dz": 0.15, "useY": True, "tduration": 500, "vdes": None,
+                 "tstart": 100, "tend": None, "trotstart": 100, "trotend": 450}
+
+
+def task_arrays(B, tasks, params, default_task):
+    """Per-robot task ids [B] int32 and parameters [4, B] float64 (the layout of umpcBatchTaskTable / umpcBatchReactiveRollout)
+    from names and keywords. tasks: a name of TASKS, a length-B sequence of names, or None (= `default_task` for every
+    robot); params: {keyword of TASK_DEFAULTS: a scalar or a [B] array}, defaults as set_task for each robot's task (vdes and
+    tend depend on it). Pure numpy, no device. Raises TypeError on an unknown keyword."""
+    B = int(B)
+    bad = sorted(set(params) - set(TASK_DEFAULTS))
+    if bad:
+        raise TypeError("unknown task parameter(s) %r" % bad)
+    names = [default_task] * B if tasks is None else [tasks] * B if isinstance(tasks, str) else list(tasks)
+    if len(names) != B:
+        raise ValueError("tasks must be one name or %d names" % B)
+    names = np.asarray(names)
+    ids = np.zeros(B, np.int32)
+    P = np.zeros((4, B), np.float64)
+    for name in sorted(set(names.tolist())):
+        t_id, slots = TASKS[name]
+        sel = names == name
+        ids[sel] = t_id
+        dflt = dict(TASK_DEFAULTS)
+        dflt["vdes"] = {"straightAcc": 2, "perch": 0.2}.get(name, 0)
+        dflt["tend"] = {"flip": 200, "perch": 500}.get(name, 0)
+        for i, n in enumerate(slots):
+            val = np.broadcast_to(np.asarray(params.get(n, dflt[n]), np.float64), (B,))
+            P[i, sel] = val[sel]
+    return ids, P
+
+
 class BatchUprightMPC:
     """B independent uprightmpc2 controllers (+ plants), one GPU lane each."""
 
@@ -205,11 +241,7 @@ class BatchUprightMPC:
         if ref is not None:
             self.ref.copy_(torch.as_tensor(ref, dtype=self.dtype))
 
-    TASKS = {"ref": (0, ()), "helix": (1, ("trajAmp", "trajFreq", "dz", "useY")),
-             "straightAcc": (2, ("tduration", "vdes")), "flip": (3, ("tstart", "tend")),
-             "perch": (4, ("tend", "trotstart", "trotend", "vdes"))}
-    TASK_DEFAULTS = {"trajAmp": 80, "trajFreq": 1, "dz": 0.15, "useY": True, "tduration": 500, "vdes": None,
-                     "tstart": 100, "tend": None, "trotstart": 100, "trotend": 450}
+    TASKS, TASK_DEFAULTS = TASKS, TASK_DEFAULTS
 
     def set_task(self, name, t_ms=0.0, **kw):
         """On-device reference generator (template/flight_tasks.py, same keyword names and defaults).
@@ -230,7 +262,8 @@ class BatchUprightMPC:
         (pdes, dpdes, sdes) of every step; step k of a rollout reads slice ref_cursor + k and `self.ref` is not read. The
         cursor starts at `cursor` and advances with every rollout(); a rollout that would run past the table raises before
         anything is launched. None switches back to `self.ref`. Excludes set_task (either call raises after the other) and
-        reactive_rollout / task_reference; combines with everything else. Memory: 36 B x B x steps in fp32 -- chunk long runs."""
+        reactive_rollout / task_reference (reactive_steps reads the table, one slice held over each step); combines with
+        everything else. Memory: 36 B x B x steps in fp32 -- chunk long runs."""
         if tab is None:
             self._check(self.L.umpcBatchSetRefTrajectory(self.h, None, 0, 0))
             self._reftab = None
@@ -254,8 +287,9 @@ class BatchUprightMPC:
         quad form alone -- fp64 at B <= 4 096, or set_step_kernel("quad") -- runs K single-step launches with a state copy each);
         self.state / out / status / info end every rollout holding what they hold without a history. Consecutive rollouts
         continue the tables; one that would pass `steps` raises before anything is launched. update(), plant() and
-        reactive_rollout() record nothing. record_history(None) switches history off. Memory: 72 B x B x steps for the
-        state and 36 B x B x steps for out in fp32 -- chunk long runs with rewind_history()."""
+        reactive_rollout() record nothing; reactive_steps() records like rollout() (status 1, info 0, out rows 3..8 = 0).
+        record_history(None) switches history off. Memory: 72 B x B x steps for the state and 36 B x B x steps for out in
+        fp32 -- chunk long runs with rewind_history()."""
         if steps is None:
             self._check(self.L.umpcBatchSetHistory(self.h, None, None, None, None, 0, 0))
             self._hist = None
@@ -345,7 +379,8 @@ class BatchUprightMPC:
         template/uprightmpc2.py:130-133). One IEEE add per component: rollout(K) equals K times rollout(1) with
         `state[12:18] += tab[c]` in between, bit for bit. The cursor starts at `cursor0` and advances with every rollout();
         a rollout that would run past the table raises before anything is launched. reactive_rollout() honours the table
-        too (one slice per nsub substeps; nsteps must then be a multiple of nsub); update() and plant() do not. None
+        too (one slice per nsub substeps; nsteps must then be a multiple of nsub), reactive_steps() like rollout(); update() and
+        plant() do not. None
         switches impulses off. impulse_table() builds a table from sparse events. Memory: 24 B x B x steps in fp32 -- chunk
         long runs."""
         if tab is None:
@@ -375,7 +410,7 @@ class BatchUprightMPC:
         """impulse_table() for this handle: [steps, 6, B] in its dtype, on its device."""
         return impulse_table(steps, self.B, events, self.dtype, self.device)
 
-    def score(self, first=0, count=None, tol=10.0, after=False, score=None, step0=None):
+    def score(self, first=0, count=None, tol=10.0, after=False, score=None, step0=None, ref_table=None, ref_first=0):
         """The recorded steps first .. first + count - 1 of the step history as a per-robot score [12, B] (umpcBatchScore; rows:
         robobee3d_amd/score.py -- steps, sum / max / last of e_p = |p - pdes|^2, sum / max of e_s = |s - sdes|^2, sum of
         the clipped moments squared, sum |p|^2, steps not solved, first / last step with e_p > tol^2, steps skipped as not
@@ -386,7 +421,10 @@ class BatchUprightMPC:
         on, after=True the state it produced (the convention of the reference's log). step0 (default `first`) is the step
         number rows 9 and 10 report for step `first`. Passing a score back in accumulates: a chunked run is scored chunk by
         chunk (rewind_history() in between, step0 = the steps already run). The out and status records enter when they are
-        on; without them rows 6 / 8 stay as they are."""
+        on; without them rows 6 / 8 stay as they are. ref_table [steps, 9, B], when given, is read IN PLACE of the set
+        trajectory / `self.ref` / the task: recorded step c is scored against its slice ref_first + c -- a run that followed
+        per-robot tasks or the handle's task (reactive_steps, rollout) is scored against task_table(...) without switching
+        the controller to step-held references."""
         hist = getattr(self, "_hist", None)
         if hist is None or hist["state"] is None:
             raise RuntimeError("score needs a step history with the state record (record_history)")
@@ -395,15 +433,22 @@ class BatchUprightMPC:
         count = cur - first if count is None else int(count)
         if first < 0 or count < 0 or first + count > cur:
             raise ValueError("score: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
-        reftab = getattr(self, "_reftab", None)
-        ref_first = 0
-        if reftab is not None:
-            ref_first = self._hist_ref0 + first
-            if ref_first < 0 or ref_first + count > int(reftab.shape[0]):
+        reftab, rfirst = getattr(self, "_reftab", None), 0
+        if ref_table is not None:
+            reftab, rfirst = ref_table, int(ref_first) + first
+            if (reftab.dim() != 3 or tuple(reftab.shape[1:]) != (_lib.REF_ROWS, self.B) or reftab.dtype != self.dtype
+                    or reftab.device != self.state.device or not reftab.is_contiguous()):
+                raise ValueError("ref_table must be a contiguous [steps, 9, %d] tensor of the handle's dtype on its device" % self.B)
+            if rfirst < 0 or rfirst + count > int(reftab.shape[0]):
+                raise ValueError("score: ref_table does not cover the steps asked for")
+        elif reftab is not None:
+            rfirst = self._hist_ref0 + first
+            if rfirst < 0 or rfirst + count > int(reftab.shape[0]):
                 raise ValueError("score: the reference trajectory does not cover the steps asked for")
         elif self._task_id() != 0:
             raise RuntimeError("score: the handle follows a task generator, there is no reference table to read; build the "
-                               "table with task_table() and set it with set_reference_trajectory() before the run")
+                               "table with task_table() and pass it as ref_table (or set it with set_reference_trajectory() "
+                               "before the run)")
         with torch.cuda.device(self.device):
             if score is None:
                 score = torch.empty((_lib.SCORE_ROWS, self.B), dtype=self.dtype, device=self.device)
@@ -413,7 +458,7 @@ class BatchUprightMPC:
                 raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
             self._check(self.L.umpcBatchScore(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
                                               _ptr(reftab), None if reftab is not None else _ptr(self.ref), first, count,
-                                              ref_first, first if step0 is None else int(step0), float(tol), int(bool(after)),
+                                              rfirst, first if step0 is None else int(step0), float(tol), int(bool(after)),
                                               _ptr(score), self._stream()))
         return score
 
@@ -441,35 +486,21 @@ class BatchUprightMPC:
         useY, tduration, vdes, tstart, tend, trotstart, trotend) a scalar or a [B] array, defaults as set_task for the
         robot's task. Rows 0..2 of `self.ref` are the robots' initialPos ("ref" robots copy their whole column)."""
         steps = int(steps)
-        bad = sorted(set(params) - set(self.TASK_DEFAULTS))
-        if bad:
-            raise TypeError("unknown task parameter(s) %r" % bad)
+        tid, prm = self._task_tensors(tasks, params)
         tab = torch.empty((steps, _lib.REF_ROWS, self.B), dtype=self.dtype, device=self.device)
-        tid = prm = None
-        if tasks is not None or params:
-            by_id = {v[0]: k for k, v in self.TASKS.items()}
-            names = [by_id[self._task_id()]] * self.B if tasks is None else [tasks] * self.B if isinstance(tasks, str) else list(tasks)
-            if len(names) != self.B:
-                raise ValueError("tasks must be one name or %d names" % self.B)
-            names = np.asarray(names)
-            ids = np.zeros(self.B, np.int32)
-            P = np.zeros((4, self.B), np.float64)
-            for name in sorted(set(names.tolist())):
-                t_id, slots = self.TASKS[name]
-                sel = names == name
-                ids[sel] = t_id
-                dflt = dict(self.TASK_DEFAULTS)
-                dflt["vdes"] = {"straightAcc": 2, "perch": 0.2}.get(name, 0)
-                dflt["tend"] = {"flip": 200, "perch": 500}.get(name, 0)
-                for i, n in enumerate(slots):
-                    val = np.broadcast_to(np.asarray(params.get(n, dflt[n]), np.float64), (self.B,))
-                    P[i, sel] = val[sel]
-            tid = torch.as_tensor(ids).to(self.device)
-            prm = torch.as_tensor(P).to(self.dtype).to(self.device).contiguous()
         with torch.cuda.device(self.device):
             self._check(self.L.umpcBatchTaskTable(self.h, steps, self.time_ms if t_ms is None else float(t_ms), _ptr(tid),
                                                   _ptr(prm), _ptr(self.ref), _ptr(tab), self._stream()))
         return tab
+
+    def _task_tensors(self, tasks, params):
+        """task_arrays on the device, in the handle's dtype: (ids [B] int32, params [4, B]), or (None, None) when neither names
+        nor keywords are given (= the handle's task)."""
+        if tasks is None and not params:
+            return None, None
+        by_id = {v[0]: k for k, v in TASKS.items()}
+        ids, P = task_arrays(self.B, tasks, params, by_id[self._task_id()])
+        return torch.as_tensor(ids).to(self.device), torch.as_tensor(P).to(self.dtype).to(self.device).contiguous()
 
     def set_weights(self, weights):
         """Per-robot objective weights [8, B] = (ws, wds, wpr, wpf, wvr, wvf, wthrust, wmom), or None."""
@@ -535,6 +566,30 @@ class BatchUprightMPC:
             self._check(self.L.umpcBatchReactive(self.h, int(nsteps), int(every), _ptr(self.state), _ptr(self.ref),
                                                  _ptr(gains), _ptr(self.Ib), _ptr(self.gain), _ptr(self.out),
                                                  _ptr(self.stats), self._stream()))
+
+    def reactive_steps(self, K, gains=None, every=1, tasks=None, **params):
+        """The reactive baseline on the tables of rollout() (umpcBatchReactiveRollout): K closed-loop steps of nsub plant
+        substeps in one launch, reactiveController fired at the substeps j of a step with j % every == 0 (`every` divides
+        nsub). It reads what rollout() reads and records what rollout() records, so an MPC-versus-reactive sweep over tasks x
+        gains x pushes is two launches scored the same way:
+        the reference is the table of set_reference_trajectory when one is set (pdes of slice ref_cursor + k, held over the
+        step), else per-robot tasks when `tasks` / task keywords are given (as in task_table: a name, B names, keywords as
+        scalars or [B] arrays; rows 0..2 of self.ref are initialPos, "ref" robots follow their column), else the handle's
+        task -- then the call equals reactive_rollout(K * nsub, gains, every) bit for bit; the table of set_impulses kicks
+        after the last substep of every step; record_history tables take the state before / after every step, the last
+        command of the step in rows 0..2 of `out` (rows 3..8 = 0: there is no accdes), status 1 and info 0, so score() and
+        score_groups() apply as they are (score a per-robot task run with ref_table=task_table(...)). Robots of different
+        tasks inside one wavefront (64 consecutive robots) take turns in the generators: keep the robots of one task adjacent.
+        gains: [6, B] (kpos0, kpos1, kz0, kz1, ks0, ks1) or None. Raises before anything is launched when a table would be
+        overrun; the clock and the cursors then stay where they were."""
+        if gains is not None:
+            gains = torch.as_tensor(gains, dtype=self.dtype, device=self.device).contiguous()
+            assert gains.shape == (6, self.B)
+        tid, prm = self._task_tensors(tasks, params)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchReactiveRollout(self.h, int(K), int(every), _ptr(self.state), _ptr(self.ref), _ptr(gains),
+                                                        _ptr(tid), _ptr(prm), _ptr(self.Ib), _ptr(self.gain), _ptr(self.out),
+                                                        _ptr(self.stats), self._stream()))
 
     def task_reference(self, t_ms):
         """(pdes, dpdes, sdes) [9, B] of the current task at time t_ms (template/flight_tasks.py:6-49)."""

@@ -342,6 +342,160 @@ __global__ __launch_bounds__(kBlock) void umpc_reactive_kernel(DevParams<T> prm,
   if (stats) { stats[b] = s_err; stats[B + b] = s_eff; }
 }
 
+// The reactive baseline on the tables of the MPC rollout (umpcBatchReactiveRollout): K closed-loop steps of nsub substeps,
+// with a reference per robot, the impulse table and the step history. Where pdes comes from is decided on the host, once
+// per call, and is a template parameter: the substep loop holds no test of a table pointer and no load.
+//   kRefHandle  the handle's task at t = t0 + T(k nsub + j) dtsim -- the expression of umpc_reactive_kernel, so with no
+//               table set the two kernels run the same arithmetic on the same values
+//   kRefRobot   the same expression with the robot's own task id and parameters (lanes of different tasks diverge inside
+//               task_reference: a sweep keeps the robots of one task adjacent)
+//   kRefTable   rows 0..2 of one slice of the reference trajectory per step, held over its substeps: no time expression
+// One lane per robot, robot index fastest: every access below is one coalesced row segment, nothing crosses robots. The
+// table pointers move on one slice per step as 64-bit pointers, so a table may pass 4 GB.
+enum { kRefHandle = 0, kRefRobot = 1, kRefTable = 2 };
+
+template <typename T>
+struct ReactiveSteps {
+  DevParams<T> prm;
+  int B, K, nsub, every;
+  T t0;
+  T *state;
+  const T *ref, *gains, *Ib, *gain;
+  T *out, *stats;
+  const int32_t *task;     // kRefRobot: [B] ids
+  const T *task_params;    // kRefRobot: [4][B] or null (= the handle's)
+  const T *reftab;         // kRefTable: the slice of step 0
+  const T *imp;            // the impulse slice of step 0, or null
+  T *h_state;              // the history slices of step 0 (state: the slice BEFORE it), each may be null
+  T *h_out;
+  int32_t *h_status;
+  T *h_info;
+};
+
+template <typename T, int SRC>
+__global__ __launch_bounds__(kBlock) void umpc_reactive_steps_kernel(ReactiveSteps<T> a) {
+  const int b = blockIdx.x * kBlock + threadIdx.x;
+  if (b >= a.B) return;
+  const size_t B = (size_t)a.B;
+  const DevParams<T> &prm = a.prm;
+  T p[3], R[9], dq[6], Ib[3], ip[3] = {T(0), T(0), T(0)}, tp[4];
+  T k[6] = {T(5e-3), T(5e-1), T(1e-1), T(1e0), T(10e0), T(1e2)}, u[3] = {T(0), T(0), T(0)};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) p[i] = a.state[(size_t)i * B + b];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = a.state[(size_t)(3 + i) * B + b];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) dq[i] = a.state[(size_t)(12 + i) * B + b];
+  // state slice c of the history: the registers just loaded
+  T *hs = a.h_state;
+  if (hs) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) hs[(size_t)i * B + b] = p[i];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) hs[(size_t)(3 + i) * B + b] = R[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) hs[(size_t)(12 + i) * B + b] = dq[i];
+    hs += 18 * B;
+  }
+  int tk = prm.task;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tp[i] = prm.task_p[i];
+  if constexpr (SRC != kRefTable) {
+    // (the reactive controller reads pdes only, and every generator takes rows 0..2 = initialPos and nothing else)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ip[i] = a.ref[(size_t)i * B + b];
+  }
+  if constexpr (SRC == kRefRobot) {
+    tk = a.task[b];
+    if (a.task_params) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) tp[i] = a.task_params[(size_t)i * B + b];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Ib[i] = a.Ib ? a.Ib[(size_t)i * B + b] : prm.Ib[i];
+  if (a.gains) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) k[i] = a.gains[(size_t)i * B + b];
+  }
+  const T gain = a.gain ? a.gain[b] : T(1);
+  const T Ibinv[3] = {T(1) / Ib[0], T(1) / Ib[1], T(1) / Ib[2]};
+  T s_err = a.stats ? a.stats[b] : T(0), s_eff = a.stats ? a.stats[B + b] : T(0);
+  const T *imp = a.imp, *rt = a.reftab;
+  T *ho = a.h_out, *hi = a.h_info;
+  int32_t *hst = a.h_status;
+  int ti = 0;
+#pragma nounroll
+  for (int ks = 0; ks < a.K; ++ks) {
+    // the words of this step that come from tables, ahead of its substeps (which hide the miss); used after the last one
+    T kick[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, pdes[3] = {ip[0], ip[1], ip[2]};
+    if (imp) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) kick[i] = imp[(size_t)i * B + b];
+      imp += 6 * B;
+    }
+    if constexpr (SRC == kRefTable) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) pdes[i] = rt[(size_t)i * B + b];
+      rt += 9 * B;
+    }
+    int hold = 0;      // substeps until the controller fires again: j % every == 0, counted down
+#pragma nounroll
+    for (int j = 0; j < a.nsub; ++j, ++ti) {
+      if (hold == 0) {
+        hold = a.every;
+        if constexpr (SRC != kRefTable) {
+          T rf[9] = {ip[0], ip[1], ip[2], T(0), T(0), T(0), T(0), T(0), T(0)};
+          umpc::task_reference(tk, tp, a.t0 + T(ti) * prm.dtsim, rf);
+          pdes[0] = rf[0]; pdes[1] = rf[1]; pdes[2] = rf[2];
+        }
+        reactive_controller(p, R, dq, pdes, k, u);
+        u[1] = umpc::umpc_min(umpc::umpc_max(u[1], -prm.taulim), prm.taulim);
+        u[2] = umpc::umpc_min(umpc::umpc_max(u[2], -prm.taulim), prm.taulim);
+      }
+      --hold;
+      umpc::plant_step(p, R, dq, u, prm.dtsim, Ib, Ibinv, gain, prm.plant_mode);
+      s_err += p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+      s_eff += u[1] * u[1] + u[2] * u[2];
+    }
+    // velocity impulse of the step (umpcBatchSetImpulses): after its last substep, ahead of everything it stores
+    if (imp) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) dq[i] += kick[i];
+    }
+    // the records of the step (wave-uniform tests, once per step; the stores are issued and not waited for)
+    if (hs) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) hs[(size_t)i * B + b] = p[i];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) hs[(size_t)(3 + i) * B + b] = R[i];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) hs[(size_t)(12 + i) * B + b] = dq[i];
+      hs += 18 * B;
+    }
+    if (ho) {      // (thrust, clipped moments, accdes = 0: a reactive controller has none)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) ho[(size_t)i * B + b] = u[i];
+#pragma unroll
+      for (int i = 3; i < 9; ++i) ho[(size_t)i * B + b] = T(0);
+      ho += 9 * B;
+    }
+    if (hst) { hst[b] = 1; hst += B; }      // OSQP_SOLVED: the step counts as solved in a score
+    if (hi) { hi[b] = T(0); hi[B + b] = T(0); hi += 2 * B; }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) a.state[(size_t)i * B + b] = p[i];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) a.state[(size_t)(3 + i) * B + b] = R[i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) a.state[(size_t)(12 + i) * B + b] = dq[i];
+  if (a.out) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a.out[(size_t)i * B + b] = u[i];
+  }
+  if (a.stats) { a.stats[b] = s_err; a.stats[B + b] = s_eff; }
+}
+
 // (pdes, dpdes, sdes) of the handle's task at time t for every robot (what the step kernel evaluates at a fire)
 template <typename T>
 __global__ void umpc_taskref_kernel(DevParams<T> prm, int B_, T t, const T *ref, T *out) {
@@ -736,6 +890,38 @@ static int launch_reactive(umpc_batch_t *h, int nsteps, int every, void *state, 
   return 0;
 }
 
+// umpcBatchReactiveRollout has made every check; the slices of the three tables are taken from the cursors here, the form of
+// the kernel is chosen from where the reference comes from, and the clock and the cursors move last
+template <typename T>
+static int launch_reactive_steps(umpc_batch_t *h, int K, int every, void *state, const void *ref, const void *gains,
+                                 const int32_t *task, const void *task_params, const void *Ib, const void *gain, void *out,
+                                 void *stats, void *stream) {
+  const int nsub = h->prm.nsub;
+  const bool hist = h->hist_on(K, nsub), imp = h->imp_on(K, nsub);
+  const size_t B = (size_t)h->B, c = (size_t)h->hist_c.cursor;
+  ReactiveSteps<T> a;
+  a.prm = make_dev_task<T>(h);
+  a.B = h->B; a.K = K; a.nsub = nsub; a.every = every; a.t0 = (T)h->t_ms;
+  a.state = (T *)state; a.ref = (const T *)ref; a.gains = (const T *)gains; a.Ib = (const T *)Ib; a.gain = (const T *)gain;
+  a.out = (T *)out; a.stats = (T *)stats;
+  a.task = task; a.task_params = (const T *)task_params;
+  a.reftab = h->reftab ? (const T *)h->reftab + (size_t)h->ref_c.cursor * 9 * B : nullptr;
+  a.imp = imp ? (const T *)h->imptab + (size_t)h->imp_c.cursor * 6 * B : nullptr;
+  a.h_state = hist && h->hist_state ? (T *)h->hist_state + c * 18 * B : nullptr;
+  a.h_out = hist && h->hist_out ? (T *)h->hist_out + c * 9 * B : nullptr;
+  a.h_status = hist && h->hist_status ? h->hist_status + c * B : nullptr;
+  a.h_info = hist && h->hist_info ? (T *)h->hist_info + c * 2 * B : nullptr;
+  const dim3 grid((unsigned)((h->B + kBlock - 1) / kBlock)), block(kBlock);
+  const hipStream_t s = (hipStream_t)stream;
+  if (h->reftab) hipLaunchKernelGGL((umpc_reactive_steps_kernel<T, kRefTable>), grid, block, 0, s, a);
+  else if (task) hipLaunchKernelGGL((umpc_reactive_steps_kernel<T, kRefRobot>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((umpc_reactive_steps_kernel<T, kRefHandle>), grid, block, 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(e, "umpcBatchReactiveRollout");      // (the clock and the cursors stay where they were)
+  h->advance((double)((long long)K * nsub) * h->prm.dtsim, h->reftab ? K : 0, hist ? K : 0, imp ? K : 0);
+  return 0;
+}
+
 template <typename T>
 static int launch_task_table(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
                              const void *ref, void *tab, void *stream) {
@@ -1031,6 +1217,34 @@ int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const
   }
   return h->dtype == UMPC_F32 ? launch_reactive<float>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream)
                               : launch_reactive<double>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream);
+}
+
+int umpcBatchReactiveRollout(umpc_batch_t *h, int K, int every, void *state, const void *ref, const void *gains,
+                             const int32_t *task, const void *task_params, const void *Ib, const void *thrust_gain, void *out,
+                             void *stats, void *stream) {
+  const char *const me = "umpcBatchReactiveRollout";
+  if (!h) { g_err = std::string(me) + ": bad argument (no handle)"; return -1; }
+  const int nsub = h->prm.nsub;
+  if (K < 1 || every < 1 || !state) { g_err = std::string(me) + ": bad argument (K >= 1, every >= 1, state must be given)"; return -1; }
+  if (nsub == 0) { g_err = std::string(me) + ": the handle has no plant (nsub = 0): there is no closed-loop step to run"; return -1; }
+  if (nsub % every != 0) {
+    g_err = std::string(me) + ": every = " + std::to_string(every) + " does not divide nsub = " + std::to_string(nsub) +
+            " (a run cut into several launches must fire at the same substeps)";
+    return -1;
+  }
+  if ((long long)K * nsub > 0x7fffffffLL) { g_err = std::string(me) + ": K * nsub passes 2^31 - 1 substeps"; return -1; }
+  if (!ref && !h->reftab) { g_err = std::string(me) + ": bad argument (ref must be given when no reference trajectory is set)"; return -1; }
+  if (task_params && !task) { g_err = std::string(me) + ": task_params without task"; return -1; }
+  if (task && h->reftab) {
+    g_err = std::string(me) + ": per-robot tasks and a reference trajectory (umpcBatchSetRefTrajectory) exclude each other";
+    return -1;
+  }
+  if (h->reftab && !h->ref_c.fits(me, "reference trajectory", "K ", K)) return -1;
+  if (h->hist_on(K, nsub) && !h->hist_c.fits(me, "step history", "K ", K)) return -1;
+  if (h->imp_on(K, nsub) && !h->imp_c.fits(me, "impulse table", "K ", K)) return -1;
+  return h->dtype == UMPC_F32
+             ? launch_reactive_steps<float>(h, K, every, state, ref, gains, task, task_params, Ib, thrust_gain, out, stats, stream)
+             : launch_reactive_steps<double>(h, K, every, state, ref, gains, task, task_params, Ib, thrust_gain, out, stats, stream);
 }
 
 int umpcBatchUpdate(umpc_batch_t *h, const void *state, void *ctrl, const void *ref, const void *actualT0,
