@@ -355,6 +355,52 @@ int umpcBatchScore(umpc_batch_t *h, const void *state_hist, const void *out_hist
                    long long step0, double tol_p, int after, void *score, void *stream);
 int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *group, int G, double *gstat, void *stream);
 
+/* Ensemble curves: the statistics of each group of robots at every step -- a quantity over time, the view every figure of
+ * the reference's harness draws (y(t) against pdes(t), template/uprightmpc2.py:177-269), for a cell of a sweep: reduced over
+ * the cell's draws and NOT over time. It is the transpose of the score's reduction over the same words (60 B per robot-step in
+ * fp32), which a score cannot give any more (it has summed over the steps) and array expressions cannot give without
+ * [steps][B] temporaries. Both calls are pure functions of their arguments, as umpcBatchScore is: they read no cursor of
+ * the handle, take only B, the dtype and taulim from it, are asynchronous on `stream` and allocate nothing.
+ * umpcBatchGroupIndex sorts the robots by group, once per sweep: group [B] is the array umpcBatchScoreGroups takes;
+ * offset [G + 1] with offset[0] = 0; order [B] is a full permutation of 0 .. B - 1: positions offset[g] .. offset[g + 1] - 1
+ * hold the robots of group g in ascending robot index, positions offset[G] .. B - 1 the robots whose id is outside [0, G),
+ * ascending too (a stable sort by group with the ignored ids last). Integers only, exact. One wavefront per group scans
+ * `group` twice: 2 (G + 1) x B id reads. Refused (-1, umpcLastError): h, group, order or offset NULL, G < 1.
+ * umpcBatchEnsemble takes the tables, first, count, ref_first, tol_p and after exactly as umpcBatchScore does (layouts, the
+ * meaning of `after`, exactly one of ref_tab / ref). order and offset are trusted as umpcBatchGroupIndex left them: the
+ * library does not validate device data. ens [count][G][UMPC_ENS_ROWS] is DOUBLE whatever the dtype and is OVERWRITTEN; row
+ * i belongs to step first + i, and every (step, group) row is independent of every other: a chunked run writes its chunks
+ * into disjoint slices of one `ens` by moving the pointer. A member is scored at a step when all the up to 14 values it
+ * reads there are finite. The per-member terms e_p, e_s, the clipped moments and d = p - pdes are formed in the handle's
+ * dtype by the expressions of umpcBatchScore, then widened; everything that crosses robots is fp64. Per (step, group):
+ *   0  members scored               1  members skipped (not finite); they enter no other row
+ *   2  sum e_p                      3  sum e_p^2 (the square formed in double)
+ *   4  max e_p                      5  min e_p, +inf when row 0 is 0
+ *   6  sum e_s                      7  max e_s
+ *   8  sum (tau1^2 + tau2^2), clipped at +-taulim              9  max of that term
+ *  10  members with e_p > tol_p^2 (outside the tube at this step)      11  members with status != 1
+ *  12..14  sum d_x, d_y, d_z (signed: the cell's bias)
+ *  15  robot index of the member with the largest e_p (ties: the lowest index), -1 when row 0 is 0
+ * (2 / 0 is the cell's mean tracking error at the step, 3 / 0 - (2 / 0)^2 its variance, 10 / 0 the share of draws outside the
+ * tube: a survival curve after a push.) out_hist NULL: rows 8 and 9 are 0 and `out` does not enter the finiteness test;
+ * status_hist NULL: row 11 is 0. An empty group has rows 0 and 1 = 0, row 5 = +inf, row 15 = -1 and 0 elsewhere.
+ * Order of summation: lane l of a wavefront folds members l, l + 64, .. of the group's list in order, then a fixed butterfly
+ * over the 64 lanes. The order of a (step, group) row is a function of that group's member list alone: it does not depend
+ * on G, on the other groups, on how the step range is cut into calls, or on the run -- the same bits every time, no
+ * floating-point atomics. The rows hold raw sums, maxima and minima, so the blocks of a sharded job combine (score.py,
+ * combine_ensembles).
+ * Lay the sweep out with CONTIGUOUS cells (cell = b / 64): the 64 lanes then read one 256-B segment per word. Scattered ids
+ * are correct but gather one word per row segment and lane, an order of magnitude slower per load; there is no second path.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; state_hist, order, offset or ens NULL; both or neither of ref_tab
+ * and ref; count, first or ref_first < 0; count > 2^31 - 1; tol_p < 0 or not finite; G < 1. count == 0 is a successful
+ * no-op. */
+#define UMPC_ENS_ROWS 16
+int umpcBatchGroupIndex(umpc_batch_t *h, const int32_t *group, int G, int32_t *order, int32_t *offset, void *stream);
+int umpcBatchEnsemble(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                      const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                      double tol_p, int after, const int32_t *order, const int32_t *offset, int G,
+                      double *ens, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

@@ -18,6 +18,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-s
 UMPC_F32, UMPC_F64 = 0, 1
 STATE_ROWS, CTRL_ROWS, REF_ROWS, OUT_ROWS, STAT_ROWS = 18, 127, 9, 9, 2
 SCORE_ROWS, GSCORE_ROWS = 12, 8
+ENS_ROWS = 16
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -28,6 +29,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchSetTask", "umpcBatchTime", "umpcBatchSetWeights", "umpcBatchSetStepKernel", "umpcBatchSetGlobalBatch", "umpcBatchGlobalBatch", "umpcBatchReactive", "umpcBatchReactiveRollout", "umpcBatchTaskReference",
            "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable", "umpcBatchSetHistory", "umpcBatchHistoryCursor",
            "umpcBatchSetImpulses", "umpcBatchImpulseCursor", "umpcBatchScoreInit", "umpcBatchScore", "umpcBatchScoreGroups",
+           "umpcBatchGroupIndex", "umpcBatchEnsemble",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -77,6 +79,13 @@ class UprightMPC_t(C.Structure):
 
 
 RESOURCE_LIMITS = os.path.join(HERE, "csrc", "resource_limits.json")
+# Limits of the kernels added since tests/test_reactive_steps.py (sha256 of the file) and tests/test_step_history.py (its exact
+# set of entries) hold csrc/resource_limits.json as it is: same format, checked by the same _validate_resources. Streaming
+# kernels: nothing may spill. A later change that may touch those two tests moves these entries into the file.
+RESOURCE_LIMITS_MORE = {
+    "umpc_ensemble_kernel": {"ScratchSize": 0},       # umpcBatchEnsemble: 8 forms by which tables there are x 2 dtypes
+    "umpc_group_index_kernel": {"ScratchSize": 0},    # umpcBatchGroupIndex
+}
 
 
 def _check_resources(remarks):
@@ -110,7 +119,7 @@ def _validate_resources(res):
     import json
     if not os.path.exists(RESOURCE_LIMITS):
         return res
-    limits = json.load(open(RESOURCE_LIMITS))
+    limits = dict(json.load(open(RESOURCE_LIMITS)), **RESOURCE_LIMITS_MORE)
     for pat, lim in limits.items():
         hits = [k for k in res if pat in k]
         if not hits:
@@ -149,7 +158,7 @@ def build(force=False, verbose=False):
     greg, gqp_units = codegen_qp.write()
     hdr = os.path.join(ROOT, "include", "umpc_mi355x.h")
     csrc = os.path.join(HERE, "csrc")
-    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_err.h")]),
+    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_ensemble.h", "umpc_err.h")]),
              (SRC_BQP, [hdr, greg, os.path.join(csrc, "umpc_bqp_common.h"), os.path.join(csrc, "umpc_err.h")])]
     gen_hdrs = [os.path.join(csrc, "gen", f) for f in os.listdir(os.path.join(csrc, "gen")) if f.endswith(".h")]
     units += [(u, [os.path.join(csrc, "umpc_bqp_common.h")] + gen_hdrs) for u in gqp_units]
@@ -274,6 +283,9 @@ def lib():
         L.umpcBatchScoreInit.argtypes = [C.c_void_p] * 3
         L.umpcBatchScore.argtypes = [C.c_void_p] * 6 + [C.c_longlong] * 4 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchScoreGroups.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchGroupIndex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.umpcBatchEnsemble.argtypes = [C.c_void_p] * 6 + [C.c_longlong] * 3 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

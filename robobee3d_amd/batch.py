@@ -410,6 +410,28 @@ class BatchUprightMPC:
         """impulse_table() for this handle: [steps, 6, B] in its dtype, on its device."""
         return impulse_table(steps, self.B, events, self.dtype, self.device)
 
+    def _scoring_reference(self, what, first, count, ref_table, ref_first):
+        """What the recorded steps first .. first + count - 1 are scored against (score, ensemble): (table, its first slice) --
+        `ref_table` when given, else the table of set_reference_trajectory -- or (None, 0) for the constant `self.ref`; a
+        handle that follows a task generator has no table to read and raises."""
+        reftab, rfirst = getattr(self, "_reftab", None), 0
+        if ref_table is not None:
+            reftab, rfirst = ref_table, int(ref_first) + first
+            if (reftab.dim() != 3 or tuple(reftab.shape[1:]) != (_lib.REF_ROWS, self.B) or reftab.dtype != self.dtype
+                    or reftab.device != self.state.device or not reftab.is_contiguous()):
+                raise ValueError("ref_table must be a contiguous [steps, 9, %d] tensor of the handle's dtype on its device" % self.B)
+            if rfirst < 0 or rfirst + count > int(reftab.shape[0]):
+                raise ValueError("%s: ref_table does not cover the steps asked for" % what)
+        elif reftab is not None:
+            rfirst = self._hist_ref0 + first
+            if rfirst < 0 or rfirst + count > int(reftab.shape[0]):
+                raise ValueError("%s: the reference trajectory does not cover the steps asked for" % what)
+        elif self._task_id() != 0:
+            raise RuntimeError("%s: the handle follows a task generator, there is no reference table to read; build the "
+                               "table with task_table() and pass it as ref_table (or set it with set_reference_trajectory() "
+                               "before the run)" % what)
+        return reftab, rfirst
+
     def score(self, first=0, count=None, tol=10.0, after=False, score=None, step0=None, ref_table=None, ref_first=0):
         """The recorded steps first .. first + count - 1 of the step history as a per-robot score [12, B] (umpcBatchScore; rows:
         robobee3d_amd/score.py -- steps, sum / max / last of e_p = |p - pdes|^2, sum / max of e_s = |s - sdes|^2, sum of
@@ -433,22 +455,7 @@ class BatchUprightMPC:
         count = cur - first if count is None else int(count)
         if first < 0 or count < 0 or first + count > cur:
             raise ValueError("score: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
-        reftab, rfirst = getattr(self, "_reftab", None), 0
-        if ref_table is not None:
-            reftab, rfirst = ref_table, int(ref_first) + first
-            if (reftab.dim() != 3 or tuple(reftab.shape[1:]) != (_lib.REF_ROWS, self.B) or reftab.dtype != self.dtype
-                    or reftab.device != self.state.device or not reftab.is_contiguous()):
-                raise ValueError("ref_table must be a contiguous [steps, 9, %d] tensor of the handle's dtype on its device" % self.B)
-            if rfirst < 0 or rfirst + count > int(reftab.shape[0]):
-                raise ValueError("score: ref_table does not cover the steps asked for")
-        elif reftab is not None:
-            rfirst = self._hist_ref0 + first
-            if rfirst < 0 or rfirst + count > int(reftab.shape[0]):
-                raise ValueError("score: the reference trajectory does not cover the steps asked for")
-        elif self._task_id() != 0:
-            raise RuntimeError("score: the handle follows a task generator, there is no reference table to read; build the "
-                               "table with task_table() and pass it as ref_table (or set it with set_reference_trajectory() "
-                               "before the run)")
+        reftab, rfirst = self._scoring_reference("score", first, count, ref_table, ref_first)
         with torch.cuda.device(self.device):
             if score is None:
                 score = torch.empty((_lib.SCORE_ROWS, self.B), dtype=self.dtype, device=self.device)
@@ -478,6 +485,55 @@ class BatchUprightMPC:
         with torch.cuda.device(self.device):
             self._check(self.L.umpcBatchScoreGroups(self.h, _ptr(score), _ptr(group), int(G), _ptr(gstat), self._stream()))
         return gstat
+
+    def group_index(self, group, G):
+        """(order [B], offset [G + 1]) int32 on the device (umpcBatchGroupIndex): the robots sorted by group, once per sweep,
+        for ensemble(). group [B] int32 is the array score_groups takes; order[offset[g]:offset[g + 1]] are the robots of
+        group g in ascending index, order[offset[G]:] the robots whose id is outside [0, G)."""
+        group = torch.as_tensor(group).to(torch.int32).to(self.device).contiguous()
+        if tuple(group.shape) != (self.B,):
+            raise ValueError("group must be [%d]" % self.B)
+        order = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        offset = torch.empty(int(G) + 1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchGroupIndex(self.h, _ptr(group), int(G), _ptr(order), _ptr(offset), self._stream()))
+        return order, offset
+
+    def ensemble(self, index, first=0, count=None, tol=10.0, after=False, ref_table=None, ref_first=0, out=None):
+        """The recorded steps first .. first + count - 1 of the step history as per-step, per-group statistics [count, G, 16]
+        float64 on the device (umpcBatchEnsemble; rows: robobee3d_amd/score.py -- members scored / skipped, sum, sum of
+        squares, max and min of e_p, sum and max of e_s and of the clipped moments squared, members outside the tube
+        e_p > tol^2, members not solved, the signed sums of p - pdes, the robot with the largest e_p): the curve of a grid cell
+        over time, reduced over its draws and not over the steps, in ONE pass over the tables. index = group_index(group, G).
+        first, count, tol, after, ref_table and ref_first are those of score(), and the reference is resolved as there. Every
+        (step, group) row is independent and bit-reproducible; `out` [count, G, 16], when given, is overwritten and returned
+        (a slice of a larger tensor serves a chunked run). Keep the cells contiguous in the batch (cell = b // 64): scattered
+        ids are correct and an order of magnitude slower per load."""
+        hist = getattr(self, "_hist", None)
+        if hist is None or hist["state"] is None:
+            raise RuntimeError("ensemble needs a step history with the state record (record_history)")
+        order, offset = index
+        G = int(offset.numel()) - 1
+        for t, n, name in ((order, self.B, "order"), (offset, G + 1, "offset")):
+            if tuple(t.shape) != (n,) or t.dtype != torch.int32 or t.device != self.state.device or not t.is_contiguous():
+                raise ValueError("ensemble: index must be the (order, offset) pair of group_index() of this handle (%s)" % name)
+        cur = self.history_cursor
+        first = int(first)
+        count = cur - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > cur:
+            raise ValueError("ensemble: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
+        reftab, rfirst = self._scoring_reference("ensemble", first, count, ref_table, ref_first)
+        if out is None:
+            out = torch.empty((count, G, _lib.ENS_ROWS), dtype=torch.float64, device=self.device)
+        elif (tuple(out.shape) != (count, G, _lib.ENS_ROWS) or out.dtype != torch.float64 or out.device != self.state.device
+              or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous [%d, %d, 16] float64 tensor on the handle's device" % (count, G))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchEnsemble(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
+                                                 _ptr(reftab), None if reftab is not None else _ptr(self.ref), first, count,
+                                                 rfirst, float(tol), int(bool(after)), _ptr(order), _ptr(offset), G, _ptr(out),
+                                                 self._stream()))
+        return out
 
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device

@@ -20,6 +20,7 @@
 #include "umpc_step_asm_quad.h"   // the same stream with one robot per lane QUAD (asmquad.py): the latency-bound shapes
 #include "umpc_models.h"
 #include "umpc_score.h"    // scoring of recorded rollouts (umpcBatchScore / umpcBatchScoreGroups): stand-alone kernels
+#include "umpc_ensemble.h" // per-step, per-group statistics of recorded rollouts (umpcBatchEnsemble): stand-alone kernels
 #include "umpc_err.h"
 #include "umpc_n3_general.h"   // the N = 3 QP as data for the general-structure solver (compat bounds-reject path only)
 
@@ -973,6 +974,45 @@ static int launch_score(umpc_batch_t *h, const void *state_hist, const void *out
   return launch_status("umpcBatchScore");
 }
 
+// umpcBatchEnsemble has checked the arguments; the table pointers are moved to the first slice of the call here
+template <typename T>
+static int launch_ensemble(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                           const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                           double tol_p, int after, const int32_t *order, const int32_t *offset, int G, double *ens,
+                           void *stream) {
+  const size_t B = (size_t)h->B;
+  umpc::EnsArgs<T> e;
+  umpc::ScoreArgs<T> &a = e.t;
+  a.state = (const T *)state_hist + (size_t)(first + (after ? 1 : 0)) * 18 * B;
+  a.out = out_hist ? (const T *)out_hist + (size_t)first * 9 * B : nullptr;
+  a.status = status_hist ? status_hist + (size_t)first * B : nullptr;
+  a.reftab = ref_tab ? (const T *)ref_tab + (size_t)ref_first * 9 * B : nullptr;
+  a.ref = (const T *)ref;
+  a.score = nullptr;
+  a.B = h->B; a.count = (int)count; a.step0 = 0;
+  a.tol2 = (T)(tol_p * tol_p); a.taulim = (T)h->prm.taulim;
+  e.order = order; e.offset = offset; e.ens = ens; e.G = G;
+  // slices of the step range: enough blocks to fill the device when G is small, never fewer than two steps per wavefront
+  // while there are that many (which wavefront takes a step does not enter its row)
+  long long gy = (4096 + G - 1) / G;
+  const long long most = (count + 2 * umpc::kEnsWaves - 1) / (2 * umpc::kEnsWaves);
+  if (gy > most) gy = most;
+  if (gy > 65535) gy = 65535;
+  const dim3 grid((unsigned)G, (unsigned)gy), block(64, umpc::kEnsWaves);
+  const int form = (a.reftab ? 4 : 0) | (a.out ? 2 : 0) | (a.status ? 1 : 0);
+#define UMPC_ENS_FORM(f)                                                                                                \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_ensemble_kernel<T, ((f) & 4) != 0, ((f) & 2) != 0, ((f) & 1) != 0>), grid, block, 0,   \
+                       (hipStream_t)stream, e);                                                                         \
+    break;
+  switch (form) {
+    UMPC_ENS_FORM(0) UMPC_ENS_FORM(1) UMPC_ENS_FORM(2) UMPC_ENS_FORM(3) UMPC_ENS_FORM(4) UMPC_ENS_FORM(5)
+    UMPC_ENS_FORM(6) UMPC_ENS_FORM(7)
+  }
+#undef UMPC_ENS_FORM
+  return launch_status("umpcBatchEnsemble");
+}
+
 extern "C" {
 
 const char *umpcLastError(void) { return g_err.c_str(); }
@@ -1133,6 +1173,30 @@ int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *grou
   else
     hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<double>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const double *)score, group, h->B, gstat);
   return launch_status("umpcBatchScoreGroups");
+}
+int umpcBatchGroupIndex(umpc_batch_t *h, const int32_t *group, int G, int32_t *order, int32_t *offset, void *stream) {
+  if (!h || !group || !order || !offset || G < 1) { g_err = "umpcBatchGroupIndex: bad argument (group, order, offset and G >= 1 must be given)"; return -1; }
+  hipLaunchKernelGGL(umpc::umpc_group_index_kernel, dim3((unsigned)G + 1u), dim3(64), 0, (hipStream_t)stream, group, h->B, G, order, offset);
+  return launch_status("umpcBatchGroupIndex");
+}
+int umpcBatchEnsemble(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                      const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                      double tol_p, int after, const int32_t *order, const int32_t *offset, int G,
+                      double *ens, void *stream) {
+  if (!h) { g_err = "umpcBatchEnsemble: bad argument (no handle)"; return -1; }
+  if (!state_hist || !order || !offset || !ens) { g_err = "umpcBatchEnsemble: bad argument (state_hist, order, offset and ens must be given)"; return -1; }
+  if ((ref_tab != nullptr) == (ref != nullptr)) {
+    g_err = "umpcBatchEnsemble: exactly one of ref_tab (a reference per step) and ref (a constant reference) must be given";
+    return -1;
+  }
+  if (count < 0 || first < 0 || ref_first < 0) { g_err = "umpcBatchEnsemble: bad argument (count, first, ref_first >= 0)"; return -1; }
+  if (count > 0x7fffffffLL) { g_err = "umpcBatchEnsemble: count too large for one call (2^31 - 1 steps at the most)"; return -1; }
+  if (!(tol_p >= 0) || !(tol_p <= 1.79769313486231570815e308)) { g_err = "umpcBatchEnsemble: bad argument (tol_p must be finite and >= 0)"; return -1; }
+  if (G < 1) { g_err = "umpcBatchEnsemble: bad argument (G >= 1)"; return -1; }
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32
+             ? launch_ensemble<float>(h, state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, tol_p, after, order, offset, G, ens, stream)
+             : launch_ensemble<double>(h, state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, tol_p, after, order, offset, G, ens, stream);
 }
 
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,

@@ -104,23 +104,42 @@ __device__ __forceinline__ void score_load(const ScoreArgs<T> &a, size_t B, size
   v.st = STAT ? score_ld<NT>(a.status + ((size_t)i * B + col) + lane) : 1;
 }
 
+// what one robot-step contributes, in the dtype: the one place these expressions are written (the scoring kernel folds them
+// over the steps of a robot, the ensemble kernel of umpc_ensemble.h over the robots of a step)
+template <typename T>
+struct ScoreTerms {
+  bool ok;              // every word the step read is finite
+  T d[3], ep, es, p2, tt;
+};
+
 // Branch-free on purpose: `&` instead of `&&` and selects instead of an `if (ok)` body. With short-circuit tests the
 // compiler sinks the loads of the later words into the branches of the earlier tests, and a step's loads are then issued
 // and waited for a few at a time.
 template <typename T>
-__device__ __forceinline__ void score_step(const ScoreArgs<T> &a, int i, const ScoreStep<T> &v, ScorePart<T> &q) {
+__device__ __forceinline__ ScoreTerms<T> score_terms(T taulim, const ScoreStep<T> &v) {
+  ScoreTerms<T> t;
   bool ok = __builtin_isfinite(v.tau[0]) & __builtin_isfinite(v.tau[1]);   // (zeros without an out table)
 #pragma unroll
   for (int j = 0; j < 3; ++j)
     ok = ok & __builtin_isfinite(v.p[j]) & __builtin_isfinite(v.s[j]) & __builtin_isfinite(v.rp[j]) & __builtin_isfinite(v.rs[j]);
+  t.ok = ok;
   const T d0 = v.p[0] - v.rp[0], d1 = v.p[1] - v.rp[1], d2 = v.p[2] - v.rp[2];
-  const T ep = (d0 * d0 + d1 * d1) + d2 * d2;
+  t.d[0] = d0; t.d[1] = d1; t.d[2] = d2;
+  t.ep = (d0 * d0 + d1 * d1) + d2 * d2;
   const T c0 = v.s[0] - v.rs[0], c1 = v.s[1] - v.rs[1], c2 = v.s[2] - v.rs[2];
-  const T es = (c0 * c0 + c1 * c1) + c2 * c2;
-  const T p2 = (v.p[0] * v.p[0] + v.p[1] * v.p[1]) + v.p[2] * v.p[2];
+  t.es = (c0 * c0 + c1 * c1) + c2 * c2;
+  t.p2 = (v.p[0] * v.p[0] + v.p[1] * v.p[1]) + v.p[2] * v.p[2];
   // the moments as the plant saw them (closed_loop_step clips them at +-taulim before the substeps)
-  const T t1 = umpc_min(umpc_max(v.tau[0], -a.taulim), a.taulim), t2 = umpc_min(umpc_max(v.tau[1], -a.taulim), a.taulim);
-  const T tt = t1 * t1 + t2 * t2;
+  const T t1 = umpc_min(umpc_max(v.tau[0], -taulim), taulim), t2 = umpc_min(umpc_max(v.tau[1], -taulim), taulim);
+  t.tt = t1 * t1 + t2 * t2;
+  return t;
+}
+
+template <typename T>
+__device__ __forceinline__ void score_step(const ScoreArgs<T> &a, int i, const ScoreStep<T> &v, ScorePart<T> &q) {
+  const ScoreTerms<T> t = score_terms(a.taulim, v);
+  const bool ok = t.ok;
+  const T ep = t.ep, es = t.es, p2 = t.p2, tt = t.tt;
   const bool over = ok & (ep > a.tol2);
   // a skipped step adds +0 to sums of non-negative terms and takes no part in a max of non-negative terms: no rounding
   q.n += ok; q.nskip += !ok;

@@ -1,10 +1,15 @@
 """Scores of recorded rollouts: the row names of umpcBatchScore / umpcBatchScoreGroups (include/umpc_mi355x.h) and their
 numpy fp64 mirrors. The device path is BatchUprightMPC.score / score_groups (batch.py); nothing here touches a device, and
-the mirrors are the definition the kernels are tested against, not a fallback.
+the mirrors are the definition the kernels are tested against, not a fallback. The same holds for the ensemble rows of
+umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble) further down.
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
-(costs[i,j], efforts[i,j] = logMetric(log), template/uprightmpc2.py:272-303)."""
+(costs[i,j], efforts[i,j] = logMetric(log), template/uprightmpc2.py:272-303). An ensemble [count, G, 16] keeps the steps
+apart instead and reduces over the robots of each group: the cell's y(t) against pdes(t) figure (uprightmpc2.py:177-269) as
+mean, spread, envelope and the share of draws outside the tube, per step."""
+import math
+
 import numpy as np
 
 SCORE_ROWS, GSCORE_ROWS = 12, 8
@@ -16,6 +21,14 @@ SCORE_ROW_NAMES = ("steps", "sum_ep", "max_ep", "last_ep", "sum_es", "max_es", "
 (G_ROBOTS, G_SCORED, G_SUM_MEAN_EP, G_MAX_EP, G_SUM_MEAN_TAU2, G_SUM_MEAN_P2, G_LEFT, G_NOT_SOLVED) = range(8)
 GSCORE_ROW_NAMES = ("robots", "scored", "sum_mean_ep", "max_ep", "sum_mean_tau2", "sum_mean_p2", "left", "not_solved")
 OSQP_SOLVED = 1
+# ensemble rows, per (step, group)
+ENS_ROWS = 16
+(E_N, E_SKIPPED, E_SUM_EP, E_SUM_EP2, E_MAX_EP, E_MIN_EP, E_SUM_ES, E_MAX_ES, E_SUM_TAU2, E_MAX_TAU2, E_OVER, E_NOT_SOLVED,
+ E_SUM_DX, E_SUM_DY, E_SUM_DZ, E_ARGMAX_EP) = range(16)
+ENS_ROW_NAMES = ("n", "skipped", "sum_ep", "sum_ep2", "max_ep", "min_ep", "sum_es", "max_es", "sum_tau2", "max_tau2", "over",
+                 "not_solved", "sum_dx", "sum_dy", "sum_dz", "argmax_ep")
+ENS_ADD_ROWS = (E_N, E_SKIPPED, E_SUM_EP, E_SUM_EP2, E_SUM_ES, E_SUM_TAU2, E_OVER, E_NOT_SOLVED, E_SUM_DX, E_SUM_DY, E_SUM_DZ)
+ENS_MAX_ROWS = (E_MAX_EP, E_MAX_ES, E_MAX_TAU2)
 
 
 def score_identity(B, dtype=np.float64):
@@ -108,4 +121,102 @@ def combine_groups(parts):
             total[:, G_MAX_EP].maximum(p[:, G_MAX_EP])
         total += p
         total[:, G_MAX_EP] = mx
+    return total
+
+
+def group_index_reference(group, G):
+    """umpcBatchGroupIndex in numpy: (order [B], offset [G + 1]) int32. order is a stable sort of the robots by group with
+    every id outside [0, G) last: positions offset[g] .. offset[g + 1] - 1 hold group g in ascending robot index, positions
+    offset[G] .. B - 1 the ignored robots."""
+    group, G = np.asarray(group), int(G)
+    if G < 1 or group.ndim != 1:
+        raise ValueError("group_index_reference: bad argument")
+    key = np.where((group >= 0) & (group < G), group, G)
+    order = np.argsort(key, kind="stable").astype(np.int32)
+    offset = np.zeros(G + 1, np.int32)
+    for g in range(1, G + 1):
+        offset[g] = offset[g - 1] + int((key == g - 1).sum())
+    return order, offset
+
+
+def ensemble_reference(state_hist, out_hist, status_hist, ref, first, count, ref_first, tol_p, after, taulim, order, offset):
+    """umpcBatchEnsemble in numpy fp64, step by step and group by group: [count, G, 16] with G = len(offset) - 1. The tables,
+    first, count, ref_first, tol_p and after are those of score_reference; order / offset are a group index
+    (group_index_reference). The members of group g are order[offset[g]:offset[g + 1]]; a member is scored at a step when
+    every value it reads there is finite. The sums are the correctly rounded sums of their terms (math.fsum): the mirror has no
+    order of summation of its own."""
+    st = np.asarray(state_hist, np.float64)
+    out = None if out_hist is None else np.asarray(out_hist, np.float64)
+    stat = None if status_hist is None else np.asarray(status_hist)
+    ref = np.asarray(ref, np.float64)
+    order, offset = np.asarray(order), np.asarray(offset)
+    first, count, ref_first, after = int(first), int(count), int(ref_first), int(bool(after))
+    G = len(offset) - 1
+    if count < 0 or first < 0 or ref_first < 0 or not (tol_p >= 0 and np.isfinite(tol_p)) or G < 1:
+        raise ValueError("ensemble_reference: bad argument")
+    tol2, tl = float(tol_p) ** 2, float(taulim)
+    ens = np.zeros((count, G, ENS_ROWS))
+    for i in range(count):
+        c = first + i
+        y = st[c + after]
+        r = ref[ref_first + i] if ref.ndim == 3 else ref
+        p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
+        ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
+        if out is not None:
+            ok &= np.isfinite(out[c, 1:3]).all(0)
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = p - pdes
+            ep = (d ** 2).sum(0)
+            es = ((s - sdes) ** 2).sum(0)
+            tau2 = (np.clip(out[c, 1:3], -tl, tl) ** 2).sum(0) if out is not None else np.zeros_like(ep)
+        for g in range(G):
+            mem = order[offset[g]:offset[g + 1]]
+            sel = mem[ok[mem]]                                  # the scored members, in list order
+            e = ens[i, g]
+            e[E_N], e[E_SKIPPED] = len(sel), len(mem) - len(sel)
+            e[E_MIN_EP], e[E_ARGMAX_EP] = np.inf, -1
+            if len(sel) == 0:
+                continue
+            x = ep[sel]
+            e[E_SUM_EP], e[E_SUM_EP2] = math.fsum(x), math.fsum(x * x)
+            e[E_MAX_EP], e[E_MIN_EP] = x.max(), x.min()
+            e[E_SUM_ES], e[E_MAX_ES] = math.fsum(es[sel]), es[sel].max()
+            if out is not None:
+                e[E_SUM_TAU2], e[E_MAX_TAU2] = math.fsum(tau2[sel]), tau2[sel].max()
+            e[E_OVER] = (x > tol2).sum()
+            if stat is not None:
+                e[E_NOT_SOLVED] = (stat[c][sel] != OSQP_SOLVED).sum()
+            for j in range(3):
+                e[E_SUM_DX + j] = math.fsum(d[j][sel])
+            e[E_ARGMAX_EP] = sel[x == x.max()].min()              # ties: the lowest robot index
+    return ens
+
+
+def combine_ensembles(parts, los=None):
+    """The ensemble of a whole job from the ensembles [count, G, 16] of its blocks of robots (each block: its own columns
+    and ids, BatchUprightMPC.group_index + ensemble): rows 0-3, 6, 8, 10-14 add, rows 4, 7, 9 take the max, row 5 the min,
+    and row 15 comes from the part with the larger row 4 (the first such part on a tie), shifted by that block's first robot
+    los[k] (None: no shift) -- the blocks in ascending robot order give the lowest index on a tie, as the undivided call
+    does. numpy arrays or torch tensors; the result is of the first part's kind and the parts are not modified."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_ensembles: no parts")
+    los = [0] * len(parts) if los is None else [int(v) for v in los]
+    if len(los) != len(parts):
+        raise ValueError("combine_ensembles: one lo per part")
+    if hasattr(parts[0], "clone"):
+        import torch as xp
+        total = parts[0].clone()
+    else:
+        xp = np
+        total = np.array(parts[0], np.float64)
+    arg = total[..., E_ARGMAX_EP]
+    total[..., E_ARGMAX_EP] = xp.where(arg >= 0, arg + los[0], arg)
+    add, mx = list(ENS_ADD_ROWS), list(ENS_MAX_ROWS)
+    for p, lo in zip(parts[1:], los[1:]):
+        take = (p[..., E_ARGMAX_EP] >= 0) & ((total[..., E_ARGMAX_EP] < 0) | (p[..., E_MAX_EP] > total[..., E_MAX_EP]))
+        total[..., E_ARGMAX_EP] = xp.where(take, p[..., E_ARGMAX_EP] + lo, total[..., E_ARGMAX_EP])
+        total[..., add] = total[..., add] + p[..., add]
+        total[..., mx] = xp.maximum(total[..., mx], p[..., mx])
+        total[..., E_MIN_EP] = xp.minimum(total[..., E_MIN_EP], p[..., E_MIN_EP])
     return total

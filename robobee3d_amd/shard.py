@@ -90,7 +90,8 @@ def score_block(score, lo, hi):
     """The block [lo, hi) of the robots of a score [12, B] (BatchUprightMPC.score), contiguous -- a column slice like
     table_block: the score of a block of a job equals these columns of the undivided job's score bit for bit. Scores gather
     over ranks like the statistics (gather_stats); the group tables of blocks (BatchUprightMPC.score_groups on each block's
-    own group ids) combine with score.combine_groups."""
+    own group ids) combine with score.combine_groups. Ensemble curves need no slice: a block computes its ensemble on its own
+    columns and ids (group_index + ensemble on the block's handle), and blocks combine with score.combine_ensembles."""
     return table_block(score, lo, hi)
 
 
