@@ -68,6 +68,8 @@ S_INT = {"stride": 10, "K": 13, "maxIter": S_ITERS, "nsub": 5, "plant": 39}     
 S_F = {n: 64 + k for k, n in enumerate(FLOATS)}                      # s64..s95
 assert max(S_F.values()) <= 95
 S_STEP, S_SUB, S_RUIZ = 12, 15, 15          # loop counters: closed-loop step; plant substep / Ruiz pass (never nested)
+S_EXACT = 14                                # lane form, step start .. end of Ruiz (the ADMM counter is dead there): 1 = every
+                                            # Ruiz pass of this step runs the exact limit_scaling body (StepGen.ruiz)
 S_MBAD, S_MP0 = 62, 14                      # phase C masks: s[62:63]; s[14:15] (ADMM / Ruiz counters are dead there)
 S_M0, S_M1, S_M2, S_M3 = 30, 32, 34, 36     # lane masks (pairs)
 S_C = {"minscal": 16, "maxscal": 17, "c45": 18, "eps10": 19, "eps": 38, "rho": 6, "rinv": 7, "rmin": 8,
@@ -329,16 +331,21 @@ class Struct:
 # The generator
 # ----------------------------------------------------------------------------------------------------------
 class StepGen:
-    def __init__(self, N=3, perm=None, quad=False):
+    def __init__(self, N=3, perm=None, quad=False, exact_ruiz=False):
         """quad: one robot per lane QUAD (asmquad.py) -- every phase runs redundantly in the four lanes of a quad and the
         ADMM iterations from the second on split the unknowns over lanes 0..2; the stream of the latency-bound shapes
-        (B = 1 drop-in, batches that cannot give every SIMD a wave)."""
+        (B = 1 drop-in, batches that cannot give every SIMD a wave).
+        exact_ruiz: the lane form with all ten Ruiz passes through the exact limit_scaling body and no speculation -- the
+        stream the shipped one must equal bit for bit (tests/test_ruiz_fast_path.py); never written to a header."""
         self.st = Struct(N, perm)
         self.s = self.st.s
         self.e = Emit()
         self.pool = Pool(self.e)
         self.lab = 20
+        self.lab_spec = 500            # labels of the Ruiz speculation: a range of their own, every other label keeps its number
         self.quad = quad
+        self.speculate = not quad and not exact_ruiz      # Ruiz passes 2..10 without limit tests, one test per step (ruiz)
+        self.ruiz_span = self.restart_at = None           # instruction indices, for the interpreter's counts (simulate)
         self.nt = () if quad else ("nt",)      # cache policy of the streaming rows and of the parked workspace rows
         self.homes = asmgen.Homes(NRING, 0 if quad else XV_N, XV_B)     # the loop's ring and extra homes of L
 
@@ -346,6 +353,10 @@ class StepGen:
     def label(self):
         self.lab += 1
         return str(self.lab)
+
+    def label_spec(self):
+        self.lab_spec += 1
+        return str(self.lab_spec)
 
     def rcp_nr(self, dst, src, t):
         """dst = 1 / src: v_rcp_f32 (1 ulp) + one Newton step (the C++ statement divides)."""
@@ -746,25 +757,130 @@ class StepGen:
             e("s_nop", 0)
 
     # ---- Ruiz equilibration, scaling.c:44-156 ---------------------------------------------------------------
+    def scalings(self, regs, track):
+        """norms -> scalings, in place. track None: limit_scaling + 1/sqrt (limit). track = (lo, hi): 1/sqrt alone, and
+        every norm is folded into the lane's running minimum / maximum of the speculative passes (ruiz): two norms per
+        instruction instead of limit's three instructions per norm."""
+        if track is None:
+            return self.limit(regs, rsq=True)
+        e = self.e
+        regs = list(regs)
+        lo, hi = track
+        for k in range(0, len(regs) - 1, 2):
+            e("v_min3_f32", v(lo), v(lo), v(regs[k]), v(regs[k + 1]))
+            e("v_max3_f32", v(hi), v(hi), v(regs[k]), v(regs[k + 1]))
+        if len(regs) % 2:
+            e("v_min_f32", v(lo), v(lo), v(regs[-1]))
+            e("v_max_f32", v(hi), v(hi), v(regs[-1]))
+        for r in regs:
+            e("v_rsq_f32", v(r), v(r))
+        e("s_nop", 0)
+
     def ruiz(self):
+        """Ten passes. Pass 1 always runs the exact body: raw weights may lie far outside limit_scaling's range. Passes
+        2..10 SPECULATE that every row and column norm lies in (1e-4, 1e4], where limit_scaling changes no bit: their body
+        has no compare / select / min (258 of an exact pass's 734 instructions) and folds the norms into a running minimum
+        and maximum per lane instead (86). One wave-wide test after pass 10 -- a single VALU -> SGPR -> branch round trip per
+        step, against five per pass for the per-chunk test that was measured slower (limit) -- confirms it. If any lane
+        fails, S_EXACT is set and the wavefront starts the step again (program: everything ahead of this point only reads
+        memory or rewrites what it wrote) with all ten passes through the exact body, the identity on the lanes that were
+        clean: every lane ends bit-identical to the exact-only stream (StepGen(exact_ruiz=True)).
+        The minimum / maximum instructions drop NaN operands, and a NaN norm needs a NaN entry, which -- from finite data --
+        only a pass with an infinite or zero norm (tracked, out of range) can create. Non-finite RAW data is therefore
+        caught ahead of pass 1 (finite_guard) and takes the exact body without a restart."""
         e, pool, st, s = self.e, self.pool, self.st, self.s
-        nx, nc = s.nx, s.nc
-        RP, RA, RQ = self.RP, self.RA, self.RQ
+        nc = s.nc
         VE = pool.getn(nc + 1)
         self.VE = VE
-        RE = lambda i: VE + st.zs[i]
-        self.RE = RE
+        self.RE = lambda i: VE + st.zs[i]
         cs = pool.get()
         self.cs = cs
         e("v_mov_b32", v(cs), 1.0)
         e("v_mov_b32", v(VE + nc), 0)
         e("s_mov_b32", sg(S_RUIZ), 10)
-        top = self.label()
-        e("label", top)
+        first = len(e.ins)
+        if not self.speculate:
+            top = self.label()
+            e("label", top)
+            self.ruiz_pass(None)
+            e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
+            e("s_cmp_gt_i32", sg(S_RUIZ), 0)
+            e("s_cbranch_scc1", top + "b")
+            self.ruiz_span = (first, len(e.ins))
+            return
+        self.finite_guard()
+        lab_x = self.label()              # the exact body keeps the label the one loop had
+        lab_f, lab_more, lab_done = (self.label_spec() for _ in range(3))
+        e("label", lab_x)
+        self.ruiz_pass(None)
+        e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
+        e("s_cmp_lg_u32", sg(S_EXACT), 0)
+        e("s_cbranch_scc1", lab_more + "f")
+        track = (pool.get(), pool.get())
+        for r in track:
+            e("v_mov_b32", v(r), 1.0)
+        e("label", lab_f)
+        self.ruiz_pass(track)
+        e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
+        e("s_cmp_gt_i32", sg(S_RUIZ), 0)
+        e("s_cbranch_scc1", lab_f + "b")
+        # clean: limit's v_cmp_lt minscal, v holds for the smallest norm (a norm equal to minscal is not clean) and its
+        # v_min maxscal, v is the identity on the largest (the upper end is inclusive)
+        e("v_cmp_lt_f32_e64", sp(S_M0), sg(S_C["minscal"]), v(track[0]))
+        e("v_cmp_ge_f32_e64", sp(S_M1), sg(S_C["maxscal"]), v(track[1]))
+        e("s_and_b64", sp(S_M0), sp(S_M0), sp(S_M1))
+        e("s_andn2_b64", sp(S_M0), "exec", sp(S_M0))            # SCC = some active lane is not clean
+        e("s_cbranch_scc0", lab_done + "f")
+        # cold: the step again, exact (the wait retires this attempt's T0 store ahead of the reload)
+        e("s_mov_b32", sg(S_EXACT), 1)
+        e("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
+        self.restart_at = len(e.ins)
+        e("s_branch", self.lab_restart + "b")
+        e("label", lab_more)                                     # exact step: passes 2..10 through the body above
+        e("s_cmp_gt_i32", sg(S_RUIZ), 0)
+        e("s_cbranch_scc1", lab_x + "b")
+        e("label", lab_done)
+        pool.free(*track)
+        self.ruiz_span = (first, len(e.ins))
+
+    def finite_guard(self):
+        """S_EXACT = 1 if any lane's raw P, A or q holds a NaN or an infinity: 0 * entry accumulates to NaN exactly then.
+        Every entry of A is a finite constant or a copy of one of eleven words (dt, dt T0, dt s0[3], dt B[6]: phase_a) and
+        every P_jj one of the eight weights, so one representative of each is read; q is read whole."""
+        e, pool, st, s = self.e, self.pool, self.st, self.s
+        zero = PB(self.VE + s.nc)
+        acc = pool.get2()
+        nq2 = st.nq + st.nq % 2
+        pk(e, "v_pk_mul_f32", acc, [zero, P2(self.VQ)])
+        for k in range(2, nq2, 2):
+            pk(e, "v_pk_fma_f32", acc, [zero, P2(self.VQ + k), P2(acc)])
+        reps = {}
+        for p_, tag in enumerate(s.A_tag):
+            if tag[0] != 'c':
+                reps.setdefault(tag[0] if tag[0] in ("dt", "T0dt") else tuple(tag[:2]), self.RA(p_))
+        for j in range(s.nx):
+            reps.setdefault(st.weight_of(j), self.RP(j))
+        assert len(reps) == 11 + len(WNAMES)
+        for r in reps.values():
+            e("v_fma_f32", v(acc), 0, v(r), v(acc))
+        lab = self.label_spec()
+        e("v_cmp_u_f32", "vcc", v(acc), v(acc + 1))
+        e("s_cmp_eq_u64", "vcc", 0)
+        e("s_cbranch_scc1", lab + "f")
+        e("s_mov_b32", sg(S_EXACT), 1)
+        e("label", lab)
+        pool.free(acc, acc + 1)
+
+    def ruiz_pass(self, track):
+        """One pass: the exact body (track None) or the speculative one (scalings); same norms, same v_rsq_f32, same
+        scaling multiplies in the same order."""
+        e, pool, st, s = self.e, self.pool, self.st, self.s
+        nx, nc = s.nx, s.nc
+        RP, RA, RQ, RE, cs = self.RP, self.RA, self.RQ, self.RE, self.cs
         # (a) row norms -> Et
         for i in range(nc):
             self.maxabs(RE(i), [RA(p) for p in st.rows[i]])
-        self.limit([RE(i) for i in range(nc)], rsq=True)
+        self.scalings([RE(i) for i in range(nc)], track)
         # (b) columns, three slot pairs at a time: norms -> Dt (transient) -> apply
         colpairs = [(st.xinv[2 * k], st.xinv[2 * k + 1]) for k in range(nx // 2)]
         if nx % 2:
@@ -779,7 +895,7 @@ class StepGen:
                         e("v_mov_b32", v(t2 + 1), 1.0)
                         continue
                     self.maxabs(t2 + h, [RP(j)] + [RA(p) for p in range(s.A_p[j], s.A_p[j + 1])])
-            self.limit([t2 + h for (j0, j1), t2 in zip(chunk, T) for h, j in enumerate((j0, j1)) if j is not None], rsq=True)
+            self.scalings([t2 + h for (j0, j1), t2 in zip(chunk, T) for h, j in enumerate((j0, j1)) if j is not None], track)
             for (j0, j1), t2 in zip(chunk, T):
                 cols = [j for j in (j0, j1) if j is not None]
                 tcol = {j0: t2}
@@ -837,10 +953,6 @@ class StepGen:
             pk(e, "v_pk_mul_f32", VQ + k, [P2(VQ + k), PB(ct)])
         e("v_mul_f32", v(cs), v(cs), v(ct))
         pool.free(acc, acc + 1, qn, ct, t)
-        e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
-        e("s_cmp_gt_i32", sg(S_RUIZ), 0)
-        e("s_cbranch_scc1", top + "b")
-
 
     # ---- Ruiz equilibration on the lane QUAD (the quad form of the stream, asmquad.py) ---------------------------------
     def ruiz_quad(self):
@@ -2156,6 +2268,12 @@ class StepGen:
         self.prologue()
         top = self.label()
         e("label", top)
+        if self.speculate:
+            # the Ruiz speculation (ruiz) restarts the step HERE when it fails: up to that point the step has only read
+            # memory, parked words in AGPRs / LDS, and stored the T0 it read
+            e("s_mov_b32", sg(S_EXACT), 0)
+            self.lab_restart = self.label_spec()
+            e("label", self.lab_restart)
         self.phase_a()
         self.admm()
         self.phase_c()
@@ -2276,10 +2394,12 @@ STRIDE = 4096
 PBASE = 0x00007E0080000000
 
 
-def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
+def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None, lanes=1, hits=False):
     """arrays: name -> float32 / int32 numpy vector indexed by ROW (one robot), or None for a null pointer; ints /
     floats: the StepParams scalars (ints without `stride`). Runs the whole kernel; arrays are updated in place.
-    Returns the executed instruction count (pseudo-instructions excluded)."""
+    Returns the executed instruction count (pseudo-instructions excluded).
+    lanes > 1 (lane form only): that many lanes of ONE wavefront -- the row arrays are C-contiguous [rows][lanes] then,
+    and scalar branches are taken for the wavefront as on the device. hits: simulate.last_hits[k] = executions of ins[k]."""
     import numpy as np
     from . import isasim
     base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(PTRS + ["impulse"])}
@@ -2287,7 +2407,8 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
     blob = bytearray(IMP_OFF + IMP_BYTES)
     for n in PTRS:
         struct.pack_into("<Q", blob, OFF[n], ptr_xform(base_of[n]) if arrays.get(n) is not None else 0)
-    allints = dict(ints, stride=STRIDE)
+    stride = STRIDE if lanes == 1 else 4 * lanes
+    allints = dict(ints, stride=stride)
     allints.setdefault("seq", 0)
     allints.setdefault("refstep", 0)      # bytes; a table of slices [9] per step in arrays["ref"] takes 9 * STRIDE
     for n in HIST_INTS:                   # bytes per step: 18 / 9 / 1 / 2 rows of STRIDE for tables of slices in the arrays
@@ -2297,14 +2418,20 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None):
     for n in FLOATS:
         struct.pack_into("<f", blob, OFF[n], float(floats[n]))
     # the third block: arrays["impulse"] = a table of slices [6] per step (rows 6k .. 6k+5 = slice k), impstep = 6 * STRIDE
-    allints.setdefault("impstep", 6 * STRIDE if arrays.get("impulse") is not None else 0)
+    allints.setdefault("impstep", 6 * stride if arrays.get("impulse") is not None else 0)
     struct.pack_into("<Q", blob, OFF["imp"], ptr_xform(base_of["impulse"]) if arrays.get("impulse") is not None else 0)
     struct.pack_into("<i", blob, OFF["impstep"], int(allints["impstep"]))
     regions = [(PBASE, 4, np.frombuffer(bytes(blob), np.uint32))] + \
-        [(base_of[n], 4 if n in FLAT else STRIDE, arrays[n]) for n in PTRS + ["impulse"] if arrays.get(n) is not None]
-    m = isasim.Machine(ins, regions=regions, sgpr={S_PARAM: PBASE & 0xFFFFFFFF, S_PARAM + 1: PBASE >> 32}, vgpr={0: 0},
-                       lds=np.zeros((1, NLDS), np.uint32), max_exec=max_exec, quad=_quad())
+        [(base_of[n], 4 if n in FLAT or lanes > 1 else STRIDE, arrays[n].reshape(-1))
+         for n in PTRS + ["impulse"] if arrays.get(n) is not None]
+    assert all(arrays[n].flags.c_contiguous for n in PTRS + ["impulse"] if arrays.get(n) is not None)
+    m = isasim.Machine(ins, lanes, regions=regions, sgpr={S_PARAM: PBASE & 0xFFFFFFFF, S_PARAM + 1: PBASE >> 32},
+                       vgpr={0: 4 * np.arange(lanes)}, lds=np.zeros((lanes, NLDS), np.uint32), max_exec=max_exec,
+                       quad=_quad() if lanes == 1 else None)
+    if hits:
+        m.hits = np.zeros(len(ins), np.int64)
     isasim.run(m)
+    simulate.last_hits = m.hits
     simulate.last_quad_sections = {("admm" if k is None else k): n for k, n in m.sections.items()}
     simulate.last_quad_instructions = sum(m.sections.values())
     return m.nexec

@@ -142,6 +142,7 @@ class Machine:
         self.max_exec, self.quad, self.log = max_exec, quad or {}, log
         self.nexec = 0
         self.sections = {}             # quad section name -> executed instructions
+        self.hits = None               # set to an int array [len(ins)] to count the executions of every instruction
         self.pend = {"vmcnt": [], "lgkmcnt": []}
         self.labels = {}
         for k, t in enumerate(ins):
@@ -350,6 +351,8 @@ class Machine:
                     return
                 self.nexec += 1
                 assert self.nexec < self.max_exec, "runaway program"
+                if self.hits is not None:
+                    self.hits[self.pc] += 1
                 if m == "s_waitcnt":
                     self.wait(t)
                 elif m == "s_barrier":
@@ -552,13 +555,8 @@ def _fmac(dpp=False):
 
 
 def _nanless(red):
-    def f(a, b, c):
-        out = np.empty_like(a)
-        for ln in range(len(a)):
-            vals = [x for x in (a[ln], b[ln], c[ln]) if x == x]
-            out[ln] = red(vals) if vals else f32(np.nan)
-        return out
-    return f
+    """min3 / max3: NaN operands are dropped (np.fmin / np.fmax: a NaN only where every operand is one)"""
+    return lambda a, b, c: red(red(a, b), c)
 
 
 def _f64op(op):
@@ -696,8 +694,8 @@ VECTOR = {
     "v_max_f32": _f32op(_fmax),
     "v_max_f32_dpp": _f32op(_fmax, True),
     "v_min_f32": _f32op(_fmin),
-    "v_max3_f32": _f32op(_nanless(max)),
-    "v_min3_f32": _f32op(_nanless(min)),
+    "v_max3_f32": _f32op(_nanless(np.fmax)),
+    "v_min3_f32": _f32op(_nanless(np.fmin)),
     "v_med3_f32": _f32op(lambda a, b, c: np.sort(np.stack([a, b, c]), 0)[1]),
     "v_rcp_f32": _f32op(lambda a: f32(1.0) / a),
     "v_rsq_f32": _f32op(lambda a: (1.0 / np.sqrt(a.astype(f64))).astype(f32)),
