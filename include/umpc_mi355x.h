@@ -401,6 +401,52 @@ int umpcBatchEnsemble(umpc_batch_t *h, const void *state_hist, const void *out_h
                       double tol_p, int after, const int32_t *order, const int32_t *offset, int G,
                       double *ens, void *stream);
 
+/* Ensemble quantiles: the order statistics of each group of robots -- the median curve with a percentile band of a
+ * Monte-Carlo cell, which the rows of umpcBatchEnsemble cannot give (one diverged draw owns the mean and the maximum of its
+ * cell at every later step; it moves a median by one rank), and the robust counterpart of umpcBatchScoreGroups' cost table.
+ * Both calls are pure functions of their arguments: they read no cursor of the handle, take only B, the dtype and taulim
+ * from it, are asynchronous on `stream` and allocate nothing. `probs` is a HOST array of nq doubles, 1 <= nq <=
+ * UMPC_QUANT_MAX_PROBS, each in [0, 1]: it is copied into the launch arguments -- no device memory, no synchronisation.
+ * The order statistic for probs[j] over the n values of a cell that enter, v[0] <= .. <= v[n - 1]:
+ *   v[k],  k = min(n - 1, max(0, (long long)ceil(probs[j] * (double)n) - 1))    (one IEEE double multiply)
+ * the inverted-CDF / nearest-rank rule: p = 0 the minimum, p = 1 the maximum, p = 0.5 the lower median; NaN when n = 0. The
+ * result is an ELEMENT of the cell, widened exactly, never an interpolation (ask for the two neighbouring ranks): it
+ * depends on the member set alone -- not on the algorithm, the grid, G, the other groups, how the step range is cut into
+ * calls, or the run. Quantiles do NOT combine across the blocks of a sharded job: keep a cell inside one block (cells of 64
+ * in contiguous blocks are).
+ * umpcBatchEnsembleQuantiles takes the tables, first, count, ref_first, after, order, offset and G exactly as
+ * umpcBatchEnsemble does. term chooses the per-member value, formed in the handle's dtype by the expressions of
+ * umpcBatchScore and used as it is: UMPC_TERM_EP e_p = |p - pdes|^2, UMPC_TERM_ES e_s = |s - sdes|^2, UMPC_TERM_TAU
+ * tau1^2 + tau2^2 clipped at +-taulim (needs out_hist). A member is scored at a step exactly when umpcBatchEnsemble with the
+ * same out_hist scores it: with out_hist given, out rows 1 and 2 enter the finiteness test whatever term is. quant
+ * [count][G][2 + nq] is DOUBLE whatever the dtype and is OVERWRITTEN; row i belongs to step first + i and every (step,
+ * group) row is independent of every other: a chunked run writes its chunks into disjoint slices of one `quant`.
+ *   0  members scored (n)           1  members skipped (not finite)          2 + j  the order statistic for probs[j]
+ * Rows 0 and 1 are rows 0 and 1 of umpcBatchEnsemble; p = 0 and p = 1 of UMPC_TERM_EP are its rows 5 and 4 bit for bit where
+ * row 0 > 0. A group of up to 64 members (cell = b / 64, contiguous: the fast case, as for umpcBatchEnsemble) is sorted in
+ * the registers of one wavefront; a larger group of any size is selected by radix in 8 KB of LDS, a path that is correct
+ * and not tuned.
+ * umpcBatchScoreQuantiles is the same selection over the robots of each group on a per-robot score [UMPC_SCORE_ROWS][B] in
+ * the handle's dtype: the value of robot b is (double)score[num][b] (den = -1) or (double)score[num][b] /
+ * (double)score[den][b] (den in 0..11, one IEEE double division: 1 / 0 is the per-robot mean tracking error). A robot enters
+ * when its score row 0 > 0 and the value is finite -- the rule of umpcBatchScoreGroups; the group's other members are
+ * counted in row 1. Values may be negative (rows 9 and 10 hold -1): the order is the total order of the values. quant
+ * [G][2 + nq], rows as above.
+ * Refused (-1, umpcLastError) BEFORE any HIP call: h, state_hist, score, order, offset, probs or quant NULL; both or neither
+ * of ref_tab and ref; count, first or ref_first < 0; count > 2^31 - 1; G < 1; nq outside 1..8; a probability outside [0, 1]
+ * or NaN; term outside 0..2; UMPC_TERM_TAU without out_hist; num outside 0..11, den outside -1..11. count == 0 is a
+ * successful no-op. */
+#define UMPC_QUANT_MAX_PROBS 8
+#define UMPC_TERM_EP 0   /* e_p = |p - pdes|^2 */
+#define UMPC_TERM_ES 1   /* e_s = |s - sdes|^2 */
+#define UMPC_TERM_TAU 2  /* tau1^2 + tau2^2, clipped at +-taulim; needs out_hist */
+int umpcBatchEnsembleQuantiles(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab,
+                               const void *ref, long long first, long long count, long long ref_first, int after,
+                               const int32_t *order, const int32_t *offset, int G, int term, const double *probs,
+                               int nq, double *quant, void *stream);
+int umpcBatchScoreQuantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order,
+                            const int32_t *offset, int G, const double *probs, int nq, double *quant, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

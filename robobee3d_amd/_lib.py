@@ -19,6 +19,8 @@ UMPC_F32, UMPC_F64 = 0, 1
 STATE_ROWS, CTRL_ROWS, REF_ROWS, OUT_ROWS, STAT_ROWS = 18, 127, 9, 9, 2
 SCORE_ROWS, GSCORE_ROWS = 12, 8
 ENS_ROWS = 16
+QUANT_MAX_PROBS = 8
+TERM_EP, TERM_ES, TERM_TAU = 0, 1, 2
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -29,7 +31,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchSetTask", "umpcBatchTime", "umpcBatchSetWeights", "umpcBatchSetStepKernel", "umpcBatchSetGlobalBatch", "umpcBatchGlobalBatch", "umpcBatchReactive", "umpcBatchReactiveRollout", "umpcBatchTaskReference",
            "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable", "umpcBatchSetHistory", "umpcBatchHistoryCursor",
            "umpcBatchSetImpulses", "umpcBatchImpulseCursor", "umpcBatchScoreInit", "umpcBatchScore", "umpcBatchScoreGroups",
-           "umpcBatchGroupIndex", "umpcBatchEnsemble",
+           "umpcBatchGroupIndex", "umpcBatchEnsemble", "umpcBatchEnsembleQuantiles", "umpcBatchScoreQuantiles",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -86,6 +88,15 @@ RESOURCE_LIMITS_MORE = {
     "umpc_ensemble_kernel": {"ScratchSize": 0},       # umpcBatchEnsemble: 8 forms by which tables there are x 2 dtypes
     "umpc_group_index_kernel": {"ScratchSize": 0},    # umpcBatchGroupIndex
 }
+# The quantile kernels (csrc/umpc_quantile.h), kept apart because tests/test_ensemble.py holds the dict above to its two
+# entries: 20 forms each of the two ensemble-quantile kernels (term x which tables there are x dtype) and 2 of the
+# score-quantile kernel. Neither the in-register sort (groups of up to 64) nor the radix select (larger groups) may spill;
+# LDS is the radix select's static block (8 histograms of 256 counters, the prefixes, ranks and probabilities).
+RESOURCE_LIMITS_QUANT = {
+    "umpc_ens_quantile_kernel": {"ScratchSize": 0, "LDS": 0},              # umpcBatchEnsembleQuantiles, n <= 64
+    "umpc_ens_quantile_block_kernel": {"ScratchSize": 0, "LDS": 8360},     # umpcBatchEnsembleQuantiles, n > 64
+    "umpc_score_quantile_kernel": {"ScratchSize": 0, "LDS": 8360},         # umpcBatchScoreQuantiles
+}
 
 
 def _check_resources(remarks):
@@ -119,7 +130,7 @@ def _validate_resources(res):
     import json
     if not os.path.exists(RESOURCE_LIMITS):
         return res
-    limits = dict(json.load(open(RESOURCE_LIMITS)), **RESOURCE_LIMITS_MORE)
+    limits = dict(json.load(open(RESOURCE_LIMITS)), **RESOURCE_LIMITS_MORE, **RESOURCE_LIMITS_QUANT)
     for pat, lim in limits.items():
         hits = [k for k in res if pat in k]
         if not hits:
@@ -158,7 +169,7 @@ def build(force=False, verbose=False):
     greg, gqp_units = codegen_qp.write()
     hdr = os.path.join(ROOT, "include", "umpc_mi355x.h")
     csrc = os.path.join(HERE, "csrc")
-    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_ensemble.h", "umpc_err.h")]),
+    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_ensemble.h", "umpc_quantile.h", "umpc_err.h")]),
              (SRC_BQP, [hdr, greg, os.path.join(csrc, "umpc_bqp_common.h"), os.path.join(csrc, "umpc_err.h")])]
     gen_hdrs = [os.path.join(csrc, "gen", f) for f in os.listdir(os.path.join(csrc, "gen")) if f.endswith(".h")]
     units += [(u, [os.path.join(csrc, "umpc_bqp_common.h")] + gen_hdrs) for u in gqp_units]
@@ -286,6 +297,10 @@ def lib():
         L.umpcBatchGroupIndex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.umpcBatchEnsemble.argtypes = [C.c_void_p] * 6 + [C.c_longlong] * 3 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]
+        L.umpcBatchEnsembleQuantiles.argtypes = [C.c_void_p] * 5 + [C.c_longlong] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchScoreQuantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

@@ -535,6 +535,78 @@ class BatchUprightMPC:
                                                  self._stream()))
         return out
 
+    def _group_index_arg(self, what, index):
+        order, offset = index
+        G = int(offset.numel()) - 1
+        for t, n, name in ((order, self.B, "order"), (offset, G + 1, "offset")):
+            if tuple(t.shape) != (n,) or t.dtype != torch.int32 or t.device != self.state.device or not t.is_contiguous():
+                raise ValueError("%s: index must be the (order, offset) pair of group_index() of this handle (%s)" % (what, name))
+        return order, offset, G
+
+    @staticmethod
+    def _probs_arg(what, probs):
+        from .score import QUANT_MAX_PROBS
+        probs = [float(p) for p in (probs if hasattr(probs, "__len__") else [probs])]
+        if not 1 <= len(probs) <= QUANT_MAX_PROBS or not all(0.0 <= p <= 1.0 for p in probs):
+            raise ValueError("%s: 1 to %d probabilities, each in [0, 1]" % (what, QUANT_MAX_PROBS))
+        return (C.c_double * len(probs))(*probs), len(probs)
+
+    def ensemble_quantiles(self, index, probs, term="ep", first=0, count=None, after=False, ref_table=None, ref_first=0, out=None):
+        """The recorded steps first .. first + count - 1 of the step history as per-step, per-group order statistics
+        [count, G, 2 + len(probs)] float64 on the device (umpcBatchEnsembleQuantiles; rows: robobee3d_amd/score.py -- members
+        scored, members skipped, then for each probability p the element v[min(n - 1, max(0, ceil(p n) - 1))] of the scored
+        members' terms in ascending order: 0 the minimum, 0.5 the lower median, 1 the maximum, NaN when nobody is scored): the
+        median curve and percentile band of a grid cell, which one diverged draw does not own as it owns the mean and the max
+        of ensemble(). term: "ep" |p - pdes|^2, "es" |s - sdes|^2, "tau" the clipped moments squared (needs the out record).
+        index = group_index(group, G); probs: 1 to 8 numbers in [0, 1], passed in the launch arguments (no copy to the
+        device, no synchronisation). first, count, after, ref_table, ref_first and out are those of ensemble(), and the
+        reference is resolved as there. An element of the cell, never an interpolation: bit-reproducible and independent of
+        everything but the member set. Quantiles of the blocks of a sharded job do not combine: keep a cell inside one block."""
+        from .score import TERM_NAMES
+        hist = getattr(self, "_hist", None)
+        if hist is None or hist["state"] is None:
+            raise RuntimeError("ensemble_quantiles needs a step history with the state record (record_history)")
+        order, offset, G = self._group_index_arg("ensemble_quantiles", index)
+        if term not in TERM_NAMES:
+            raise ValueError("ensemble_quantiles: term is one of %s" % (TERM_NAMES,))
+        if term == "tau" and hist["out"] is None:
+            raise RuntimeError("ensemble_quantiles: term 'tau' needs the out record of the step history")
+        cprobs, nq = self._probs_arg("ensemble_quantiles", probs)
+        cur = self.history_cursor
+        first = int(first)
+        count = cur - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > cur:
+            raise ValueError("ensemble_quantiles: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
+        reftab, rfirst = self._scoring_reference("ensemble_quantiles", first, count, ref_table, ref_first)
+        if out is None:
+            out = torch.empty((count, G, 2 + nq), dtype=torch.float64, device=self.device)
+        elif (tuple(out.shape) != (count, G, 2 + nq) or out.dtype != torch.float64 or out.device != self.state.device
+              or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous [%d, %d, %d] float64 tensor on the handle's device" % (count, G, 2 + nq))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchEnsembleQuantiles(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(reftab),
+                                                          None if reftab is not None else _ptr(self.ref), first, count, rfirst,
+                                                          int(bool(after)), _ptr(order), _ptr(offset), G, TERM_NAMES.index(term),
+                                                          cprobs, nq, _ptr(out), self._stream()))
+        return out
+
+    def score_quantiles(self, score, index, probs, num, den=None):
+        """[G, 2 + len(probs)] float64 order statistics of a per-robot score over the robots of each group
+        (umpcBatchScoreQuantiles; rows as ensemble_quantiles): the value of robot b is score[num, b], or score[num, b] /
+        score[den, b] in double (num = 1, den = 0: the per-robot mean tracking error, whose median over a cell is a cost
+        table that one crashed draw does not own, as it owns the sums of score_groups). A robot enters when its row 0 > 0
+        and its value is finite; the group's other members are counted in row 1. index = group_index(group, G)."""
+        order, offset, G = self._group_index_arg("score_quantiles", index)
+        if (tuple(score.shape) != (_lib.SCORE_ROWS, self.B) or score.dtype != self.dtype or score.device != self.state.device
+                or not score.is_contiguous()):
+            raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
+        cprobs, nq = self._probs_arg("score_quantiles", probs)
+        quant = torch.empty((G, 2 + nq), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchScoreQuantiles(self.h, _ptr(score), int(num), -1 if den is None else int(den), _ptr(order),
+                                                       _ptr(offset), G, cprobs, nq, _ptr(quant), self._stream()))
+        return quant
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

@@ -21,6 +21,7 @@
 #include "umpc_models.h"
 #include "umpc_score.h"    // scoring of recorded rollouts (umpcBatchScore / umpcBatchScoreGroups): stand-alone kernels
 #include "umpc_ensemble.h" // per-step, per-group statistics of recorded rollouts (umpcBatchEnsemble): stand-alone kernels
+#include "umpc_quantile.h" // per-step, per-group order statistics (umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles): stand-alone
 #include "umpc_err.h"
 #include "umpc_n3_general.h"   // the N = 3 QP as data for the general-structure solver (compat bounds-reject path only)
 
@@ -1013,6 +1014,67 @@ static int launch_ensemble(umpc_batch_t *h, const void *state_hist, const void *
   return launch_status("umpcBatchEnsemble");
 }
 
+// umpcBatchEnsembleQuantiles has checked the arguments; the table pointers are moved to the first slice of the call here
+template <typename T>
+static int launch_ens_quantiles(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab, const void *ref,
+                                long long first, long long count, long long ref_first, int after, const int32_t *order,
+                                const int32_t *offset, int G, int term, const double *probs, int nq, double *quant, void *stream) {
+  const size_t B = (size_t)h->B;
+  umpc::QuantArgs<T> e;
+  umpc::ScoreArgs<T> &a = e.t;
+  a.state = (const T *)state_hist + (size_t)(first + (after ? 1 : 0)) * 18 * B;
+  a.out = out_hist ? (const T *)out_hist + (size_t)first * 9 * B : nullptr;
+  a.status = nullptr;
+  a.reftab = ref_tab ? (const T *)ref_tab + (size_t)ref_first * 9 * B : nullptr;
+  a.ref = (const T *)ref;
+  a.score = nullptr;
+  a.B = h->B; a.count = (int)count; a.step0 = 0;
+  a.tol2 = T(0); a.taulim = (T)h->prm.taulim;
+  e.order = order; e.offset = offset; e.quant = quant; e.G = G;
+  for (int j = 0; j < umpc::kQuantMaxProbs; ++j) e.q.p[j] = j < nq ? probs[j] : 0.0;   // the probabilities travel in the launch arguments
+  e.q.nq = nq;
+  // slices of the step range as in launch_ensemble (which wavefront or block takes a step does not enter its row)
+  long long gy = (4096 + G - 1) / G;
+  const long long most = (count + 2 * umpc::kQuantWaves - 1) / (2 * umpc::kQuantWaves);
+  if (gy > most) gy = most;
+  if (gy > 65535) gy = 65535;
+  const dim3 grid((unsigned)G, (unsigned)gy), block(64, umpc::kQuantWaves);
+  const int form = term * 4 + (a.reftab ? 2 : 0) + (a.out ? 1 : 0);
+#define UMPC_QUANT_FORM(f)                                                                                              \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_ens_quantile_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, (f) / 4>), grid, block, 0,      \
+                       (hipStream_t)stream, e);                                                                         \
+    hipLaunchKernelGGL((umpc::umpc_ens_quantile_block_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, (f) / 4>), grid, block, 0, \
+                       (hipStream_t)stream, e);                                                                         \
+    break;
+  switch (form) {
+    UMPC_QUANT_FORM(0) UMPC_QUANT_FORM(1) UMPC_QUANT_FORM(2) UMPC_QUANT_FORM(3) UMPC_QUANT_FORM(4) UMPC_QUANT_FORM(5)
+    UMPC_QUANT_FORM(6) UMPC_QUANT_FORM(7) UMPC_QUANT_FORM(9) UMPC_QUANT_FORM(11)       // (term 2 needs out: forms 8 and 10 do not exist)
+  }
+#undef UMPC_QUANT_FORM
+  return launch_status("umpcBatchEnsembleQuantiles");
+}
+
+template <typename T>
+static int launch_score_quantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order, const int32_t *offset,
+                                  int G, const double *probs, int nq, double *quant, void *stream) {
+  umpc::ScoreQuantArgs<T> e;
+  e.score = (const T *)score; e.order = order; e.offset = offset; e.quant = quant;
+  e.B = h->B; e.num = num; e.den = den;
+  for (int j = 0; j < umpc::kQuantMaxProbs; ++j) e.q.p[j] = j < nq ? probs[j] : 0.0;
+  e.q.nq = nq;
+  hipLaunchKernelGGL(umpc::umpc_score_quantile_kernel<T>, dim3((unsigned)G), dim3(64, umpc::kQuantWaves), 0, (hipStream_t)stream, e);
+  return launch_status("umpcBatchScoreQuantiles");
+}
+
+// nq in 1 .. UMPC_QUANT_MAX_PROBS and every probability in [0, 1] (a NaN fails both comparisons)
+static bool quant_probs_ok(const double *probs, int nq) {
+  if (nq < 1 || nq > UMPC_QUANT_MAX_PROBS) return false;
+  for (int j = 0; j < nq; ++j)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return false;
+  return true;
+}
+
 extern "C" {
 
 const char *umpcLastError(void) { return g_err.c_str(); }
@@ -1197,6 +1259,36 @@ int umpcBatchEnsemble(umpc_batch_t *h, const void *state_hist, const void *out_h
   return h->dtype == UMPC_F32
              ? launch_ensemble<float>(h, state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, tol_p, after, order, offset, G, ens, stream)
              : launch_ensemble<double>(h, state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, tol_p, after, order, offset, G, ens, stream);
+}
+int umpcBatchEnsembleQuantiles(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab,
+                               const void *ref, long long first, long long count, long long ref_first, int after,
+                               const int32_t *order, const int32_t *offset, int G, int term, const double *probs,
+                               int nq, double *quant, void *stream) {
+  if (!h) { g_err = "umpcBatchEnsembleQuantiles: bad argument (no handle)"; return -1; }
+  if (!state_hist || !order || !offset || !probs || !quant) { g_err = "umpcBatchEnsembleQuantiles: bad argument (state_hist, order, offset, probs and quant must be given)"; return -1; }
+  if ((ref_tab != nullptr) == (ref != nullptr)) {
+    g_err = "umpcBatchEnsembleQuantiles: exactly one of ref_tab (a reference per step) and ref (a constant reference) must be given";
+    return -1;
+  }
+  if (count < 0 || first < 0 || ref_first < 0) { g_err = "umpcBatchEnsembleQuantiles: bad argument (count, first, ref_first >= 0)"; return -1; }
+  if (count > 0x7fffffffLL) { g_err = "umpcBatchEnsembleQuantiles: count too large for one call (2^31 - 1 steps at the most)"; return -1; }
+  if (G < 1) { g_err = "umpcBatchEnsembleQuantiles: bad argument (G >= 1)"; return -1; }
+  if (!quant_probs_ok(probs, nq)) { g_err = "umpcBatchEnsembleQuantiles: bad argument (1 to 8 probabilities, each in [0, 1])"; return -1; }
+  if (term < UMPC_TERM_EP || term > UMPC_TERM_TAU) { g_err = "umpcBatchEnsembleQuantiles: bad argument (term is UMPC_TERM_EP, UMPC_TERM_ES or UMPC_TERM_TAU)"; return -1; }
+  if (term == UMPC_TERM_TAU && !out_hist) { g_err = "umpcBatchEnsembleQuantiles: UMPC_TERM_TAU needs out_hist (the moments are read from it)"; return -1; }
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32
+             ? launch_ens_quantiles<float>(h, state_hist, out_hist, ref_tab, ref, first, count, ref_first, after, order, offset, G, term, probs, nq, quant, stream)
+             : launch_ens_quantiles<double>(h, state_hist, out_hist, ref_tab, ref, first, count, ref_first, after, order, offset, G, term, probs, nq, quant, stream);
+}
+int umpcBatchScoreQuantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order,
+                            const int32_t *offset, int G, const double *probs, int nq, double *quant, void *stream) {
+  if (!h || !score || !order || !offset || !probs || !quant) { g_err = "umpcBatchScoreQuantiles: bad argument (h, score, order, offset, probs and quant must be given)"; return -1; }
+  if (G < 1) { g_err = "umpcBatchScoreQuantiles: bad argument (G >= 1)"; return -1; }
+  if (!quant_probs_ok(probs, nq)) { g_err = "umpcBatchScoreQuantiles: bad argument (1 to 8 probabilities, each in [0, 1])"; return -1; }
+  if (num < 0 || num >= UMPC_SCORE_ROWS || den < -1 || den >= UMPC_SCORE_ROWS) { g_err = "umpcBatchScoreQuantiles: bad argument (num in 0..11, den in -1..11)"; return -1; }
+  return h->dtype == UMPC_F32 ? launch_score_quantiles<float>(h, score, num, den, order, offset, G, probs, nq, quant, stream)
+                              : launch_score_quantiles<double>(h, score, num, den, order, offset, G, probs, nq, quant, stream);
 }
 
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,

@@ -1,7 +1,8 @@
 """Scores of recorded rollouts: the row names of umpcBatchScore / umpcBatchScoreGroups (include/umpc_mi355x.h) and their
 numpy fp64 mirrors. The device path is BatchUprightMPC.score / score_groups (batch.py); nothing here touches a device, and
 the mirrors are the definition the kernels are tested against, not a fallback. The same holds for the ensemble rows of
-umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble) further down.
+umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble) and for the order statistics of
+umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles) further down.
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -29,6 +30,11 @@ ENS_ROW_NAMES = ("n", "skipped", "sum_ep", "sum_ep2", "max_ep", "min_ep", "sum_e
                  "not_solved", "sum_dx", "sum_dy", "sum_dz", "argmax_ep")
 ENS_ADD_ROWS = (E_N, E_SKIPPED, E_SUM_EP, E_SUM_EP2, E_SUM_ES, E_SUM_TAU2, E_OVER, E_NOT_SOLVED, E_SUM_DX, E_SUM_DY, E_SUM_DZ)
 ENS_MAX_ROWS = (E_MAX_EP, E_MAX_ES, E_MAX_TAU2)
+# quantile rows, per (step, group) or per group: members that enter, members that do not, then one row per probability
+Q_N, Q_SKIPPED, Q_FIRST = 0, 1, 2
+QUANT_MAX_PROBS = 8
+TERM_EP, TERM_ES, TERM_TAU = 0, 1, 2
+TERM_NAMES = ("ep", "es", "tau")
 
 
 def score_identity(B, dtype=np.float64):
@@ -220,3 +226,91 @@ def combine_ensembles(parts, los=None):
         total[..., mx] = xp.maximum(total[..., mx], p[..., mx])
         total[..., E_MIN_EP] = xp.minimum(total[..., E_MIN_EP], p[..., E_MIN_EP])
     return total
+
+
+def quantile_rank(p, n):
+    """The index k of the order statistic for probability p among n >= 1 values in ascending order (inverted CDF / nearest
+    rank): k = min(n - 1, max(0, ceil(p * n) - 1)), the product one IEEE double multiply. p = 0 the minimum, p = 1 the
+    maximum, p = 0.5 the lower median."""
+    return min(int(n) - 1, max(0, int(math.ceil(float(p) * float(n))) - 1))
+
+
+def _check_probs(probs, what):
+    probs = [float(p) for p in np.atleast_1d(np.asarray(probs, np.float64))]
+    if not 1 <= len(probs) <= QUANT_MAX_PROBS or not all(0.0 <= p <= 1.0 for p in probs):
+        raise ValueError("%s: 1 to %d probabilities, each in [0, 1]" % (what, QUANT_MAX_PROBS))
+    return probs
+
+
+def _quantile_row(values, members, probs):
+    """[2 + nq]: values = the members' values that enter (any order), members = the size of the group"""
+    v = sorted(float(x) for x in values)
+    row = [float(len(v)), float(members - len(v))]
+    row += [v[quantile_rank(p, len(v))] if v else float("nan") for p in probs]
+    return row
+
+
+def ensemble_quantiles_reference(state_hist, out_hist, ref, first, count, ref_first, after, taulim, order, offset, probs,
+                                 term=TERM_EP):
+    """umpcBatchEnsembleQuantiles in numpy, step by step and group by group: [count, G, 2 + nq]. The tables, first, count,
+    ref_first, after, order and offset are those of ensemble_reference; a member is scored at a step exactly when
+    ensemble_reference with the same out_hist scores it. term: TERM_EP |p - pdes|^2, TERM_ES |s - sdes|^2, TERM_TAU the
+    moments squared, clipped at +-taulim (needs out_hist), in the mirror's fp64. Row 0 = members scored (n), row 1 = members
+    skipped, row 2 + j = v[quantile_rank(probs[j], n)] over the scored members' terms v in ascending order -- an explicit
+    sort and an explicit rank --, NaN when n = 0.
+    Quantiles do NOT combine across the blocks of a sharded job (there is no combine_quantiles): keep a cell inside one
+    block. Cells of 64 in contiguous blocks are."""
+    st = np.asarray(state_hist, np.float64)
+    out = None if out_hist is None else np.asarray(out_hist, np.float64)
+    ref = np.asarray(ref, np.float64)
+    order, offset = np.asarray(order), np.asarray(offset)
+    first, count, ref_first, after, term = int(first), int(count), int(ref_first), int(bool(after)), int(term)
+    G = len(offset) - 1
+    probs = _check_probs(probs, "ensemble_quantiles_reference")
+    if count < 0 or first < 0 or ref_first < 0 or G < 1 or term not in (TERM_EP, TERM_ES, TERM_TAU) or (term == TERM_TAU and out is None):
+        raise ValueError("ensemble_quantiles_reference: bad argument")
+    tl = float(taulim)
+    quant = np.zeros((count, G, 2 + len(probs)))
+    for i in range(count):
+        c = first + i
+        y = st[c + after]
+        r = ref[ref_first + i] if ref.ndim == 3 else ref
+        p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
+        ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
+        if out is not None:
+            ok &= np.isfinite(out[c, 1:3]).all(0)
+        with np.errstate(invalid="ignore", over="ignore"):
+            if term == TERM_EP:
+                x = ((p - pdes) ** 2).sum(0)
+            elif term == TERM_ES:
+                x = ((s - sdes) ** 2).sum(0)
+            else:
+                x = (np.clip(out[c, 1:3], -tl, tl) ** 2).sum(0)
+        for g in range(G):
+            mem = order[offset[g]:offset[g + 1]]
+            quant[i, g] = _quantile_row(x[mem[ok[mem]]], len(mem), probs)
+    return quant
+
+
+def score_quantiles_reference(score, order, offset, probs, num, den=None):
+    """umpcBatchScoreQuantiles in numpy: [G, 2 + nq] over the robots of each group of a per-robot score [12, B]. The value of
+    robot b is score[num, b], or the IEEE double quotient score[num, b] / score[den, b] (den None or -1: no division;
+    SUM_EP / STEPS is the per-robot mean tracking error). A robot enters when its row 0 > 0 and the value is finite (the
+    rule of group_reference); the other members of the group are counted in row 1. Values may be negative."""
+    sc = np.asarray(score)
+    order, offset = np.asarray(order), np.asarray(offset)
+    num, den = int(num), -1 if den is None else int(den)
+    G = len(offset) - 1
+    probs = _check_probs(probs, "score_quantiles_reference")
+    if G < 1 or not 0 <= num < SCORE_ROWS or not -1 <= den < SCORE_ROWS:
+        raise ValueError("score_quantiles_reference: bad argument")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        x = sc[num].astype(np.float64)
+        if den >= 0:
+            x = x / sc[den].astype(np.float64)
+    ok = (sc[STEPS] > 0) & np.isfinite(x)
+    quant = np.zeros((G, 2 + len(probs)))
+    for g in range(G):
+        mem = order[offset[g]:offset[g + 1]]
+        quant[g] = _quantile_row(x[mem[ok[mem]]], len(mem), probs)
+    return quant
