@@ -447,6 +447,48 @@ int umpcBatchEnsembleQuantiles(umpc_batch_t *h, const void *state_hist, const vo
 int umpcBatchScoreQuantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order,
                             const int32_t *offset, int G, const double *probs, int nq, double *quant, void *stream);
 
+/* Bootstrap intervals of a per-group cost table: how far to trust a number that is an estimate from the draws of one grid
+ * cell. The scored values of each group are resampled with replacement R times on the device, a statistic is taken of
+ * every resample, and each group gets its point estimate, the mean and standard error of the R replicates and their
+ * percentile interval. A pure function of its arguments like umpcBatchScoreQuantiles: it reads no cursor of the handle,
+ * takes only B and the dtype from it, is asynchronous on `stream` and allocates nothing; probs is a HOST array as there.
+ * Value of robot b: x_b = (double)score[num][b] (den = -1) or (double)score[num][b] / (double)score[den][b] (den in 0..11,
+ * one IEEE double division), the rule of umpcBatchScoreQuantiles. With `other` (a second score [UMPC_SCORE_ROWS][B] of the
+ * same dtype, e.g. the reactive run of the same sweep on the same tables; may be NULL) y_b is formed the same way from it
+ * and the value is x_b - y_b in double: a comparison PAIRED by draw. A robot enters when score[0][b] > 0, other[0][b] > 0
+ * if other is given, and the value is finite; the group's other members are counted as skipped. The scored values of group
+ * g in the order of its member list order[offset[g] .. offset[g + 1]) are v[0 .. nsc).
+ * Replicate r (0 <= r < R), slot m (0 <= m < nsc): u = u01(seed, (r << 32) + m, salt 41) -- the counter hash of the
+ * library's Monte-Carlo draws: idx + seed * 0x9E3779B97F4A7C15 + salt, two multiply-xorshift rounds, the top 53 bits --,
+ * j = min(nsc - 1, floor(u * nsc)) in double; the resample is v[j(r, 0)], .., v[j(r, nsc - 1)]. The draw depends on
+ * (seed, r, m, nsc) and on NOTHING else: not on g, G, the grid or the other groups. Groups with equal nsc are therefore
+ * resampled with the same indices -- common random numbers: when draw m of every cell carries the same perturbation,
+ * reps[g1] - reps[g2] is a paired bootstrap of the difference between two cells.
+ * Statistic of a resample: UMPC_BOOT_MEAN its sum in fp64 (in an order that is a function of nsc alone) divided by nsc;
+ * UMPC_BOOT_QUANTILE the element at rank min(nsc - 1, max(0, ceil(stat_p * nsc) - 1)) of the resample in the total order of
+ * the values (-0 before +0): an element, never an interpolation. stat_p is ignored by UMPC_BOOT_MEAN but must be in [0, 1].
+ * boot [G][UMPC_BOOT_ROWS + nq], DOUBLE, overwritten:
+ *   0  members scored (nsc)     1  members skipped     2  the statistic of v itself (the point estimate)
+ *   3  mean of the R replicates t_r     4  their standard error sqrt(sum (t_r - mean)^2 / (R - 1)), two passes, fixed order
+ *   5 + k  the nearest-rank element of the R replicates at probs[k] (rank as above with R for nsc): the percentile interval
+ * nsc = 0 gives NaN in columns 2 and up. reps [G][R], DOUBLE, overwritten: every replicate t_r of every group, NaN rows for
+ * empty groups -- what a caller differences between groups. work: DOUBLE [B + G], scratch of the call (the compacted
+ * values and nsc per group); the caller owns it, and two calls in flight need two. Bit-reproducible: no atomics, every order
+ * of summation fixed. A group of up to 64 scored values is resampled in the registers of one wavefront; a larger one of any
+ * size through L2 by a block, a path that is correct and not tuned. Like quantiles, the rows of the blocks of a sharded
+ * job do NOT combine: keep a cell inside one block.
+ * Refused (-1, umpcLastError) BEFORE any HIP call: score, order, offset, probs, boot, reps or work NULL; G < 1; R outside
+ * 2..UMPC_BOOT_MAX_REPS; stat neither of the two; stat_p outside [0, 1] or NaN; nq outside 1..8; a probability outside
+ * [0, 1] or NaN; num outside 0..11, den outside -1..11; h NULL. */
+#define UMPC_BOOT_MEAN 0
+#define UMPC_BOOT_QUANTILE 1
+#define UMPC_BOOT_ROWS 5   /* columns ahead of the percentile columns */
+#define UMPC_BOOT_MAX_REPS 1048576
+int umpcBatchScoreBootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den,
+                            const int32_t *order, const int32_t *offset, int G, int stat, double stat_p,
+                            int R, unsigned long long seed, const double *probs, int nq,
+                            double *boot, double *reps, double *work, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

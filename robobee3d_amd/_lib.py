@@ -21,6 +21,7 @@ SCORE_ROWS, GSCORE_ROWS = 12, 8
 ENS_ROWS = 16
 QUANT_MAX_PROBS = 8
 TERM_EP, TERM_ES, TERM_TAU = 0, 1, 2
+BOOT_MEAN, BOOT_QUANTILE, BOOT_ROWS, BOOT_MAX_REPS = 0, 1, 5, 1 << 20
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -31,7 +32,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchSetTask", "umpcBatchTime", "umpcBatchSetWeights", "umpcBatchSetStepKernel", "umpcBatchSetGlobalBatch", "umpcBatchGlobalBatch", "umpcBatchReactive", "umpcBatchReactiveRollout", "umpcBatchTaskReference",
            "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable", "umpcBatchSetHistory", "umpcBatchHistoryCursor",
            "umpcBatchSetImpulses", "umpcBatchImpulseCursor", "umpcBatchScoreInit", "umpcBatchScore", "umpcBatchScoreGroups",
-           "umpcBatchGroupIndex", "umpcBatchEnsemble", "umpcBatchEnsembleQuantiles", "umpcBatchScoreQuantiles",
+           "umpcBatchGroupIndex", "umpcBatchEnsemble", "umpcBatchEnsembleQuantiles", "umpcBatchScoreQuantiles", "umpcBatchScoreBootstrap",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -97,6 +98,17 @@ RESOURCE_LIMITS_QUANT = {
     "umpc_ens_quantile_block_kernel": {"ScratchSize": 0, "LDS": 8360},     # umpcBatchEnsembleQuantiles, n > 64
     "umpc_score_quantile_kernel": {"ScratchSize": 0, "LDS": 8360},         # umpcBatchScoreQuantiles
 }
+# The bootstrap kernels (csrc/umpc_bootstrap.h), one entry per kernel, apart for the same reason (tests/test_quantiles.py
+# holds the dict above to its three entries): 4 forms of the compaction (dtype x with / without a second table), 2 of the
+# small-cell replicate kernel (mean, quantile), one each of the others. LDS: the block mean's 256 partial sums; the radix
+# select's block plus its row of 10 doubles; that plus the 2 x 256 doubles of the row kernel's double-double tree.
+RESOURCE_LIMITS_BOOT = {
+    "umpc_boot_compact_kernel": {"ScratchSize": 0, "LDS": 0},
+    "umpc_boot_rep_kernel": {"ScratchSize": 0, "LDS": 0},                  # nsc <= 64: registers only
+    "umpc_boot_mean_block_kernel": {"ScratchSize": 0, "LDS": 2048},        # nsc > 64
+    "umpc_boot_quantile_block_kernel": {"ScratchSize": 0, "LDS": 8440},    # nsc > 64
+    "umpc_boot_row_kernel": {"ScratchSize": 0, "LDS": 12536},
+}
 
 
 def _check_resources(remarks):
@@ -130,7 +142,7 @@ def _validate_resources(res):
     import json
     if not os.path.exists(RESOURCE_LIMITS):
         return res
-    limits = dict(json.load(open(RESOURCE_LIMITS)), **RESOURCE_LIMITS_MORE, **RESOURCE_LIMITS_QUANT)
+    limits = dict(json.load(open(RESOURCE_LIMITS)), **RESOURCE_LIMITS_MORE, **RESOURCE_LIMITS_QUANT, **RESOURCE_LIMITS_BOOT)
     for pat, lim in limits.items():
         hits = [k for k in res if pat in k]
         if not hits:
@@ -169,7 +181,7 @@ def build(force=False, verbose=False):
     greg, gqp_units = codegen_qp.write()
     hdr = os.path.join(ROOT, "include", "umpc_mi355x.h")
     csrc = os.path.join(HERE, "csrc")
-    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_ensemble.h", "umpc_quantile.h", "umpc_err.h")]),
+    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_ensemble.h", "umpc_quantile.h", "umpc_bootstrap.h", "umpc_err.h")]),
              (SRC_BQP, [hdr, greg, os.path.join(csrc, "umpc_bqp_common.h"), os.path.join(csrc, "umpc_err.h")])]
     gen_hdrs = [os.path.join(csrc, "gen", f) for f in os.listdir(os.path.join(csrc, "gen")) if f.endswith(".h")]
     units += [(u, [os.path.join(csrc, "umpc_bqp_common.h")] + gen_hdrs) for u in gqp_units]
@@ -301,6 +313,9 @@ def lib():
                                                  C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchScoreQuantiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                               C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchScoreBootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.POINTER(C.c_double), C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

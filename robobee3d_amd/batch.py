@@ -607,6 +607,43 @@ class BatchUprightMPC:
                                                        _ptr(offset), G, cprobs, nq, _ptr(quant), self._stream()))
         return quant
 
+    def score_bootstrap(self, score, index, num, den=None, other=None, stat="mean", p=0.5, reps=1000, seed=0,
+                        probs=(0.025, 0.975), return_reps=False):
+        """[G, 5 + len(probs)] float64 bootstrap table of a per-robot score over the draws of each group
+        (umpcBatchScoreBootstrap; rows: robobee3d_amd/score.py BOOT_N scored, BOOT_SKIPPED, BOOT_POINT the statistic of the
+        cell, BOOT_MEAN and BOOT_SE of the replicates, then their nearest-rank element for each probability: (0.025, 0.975)
+        is a 95 % percentile interval). The value of robot b is that of score_quantiles (score[num, b], or score[num, b] /
+        score[den, b] in double); with other= (a second score of the same shape and dtype: the reactive run of the same
+        sweep on the same tables) the same expression of `other` is subtracted, a comparison paired by draw, and a robot
+        missing in either table is skipped. stat: "mean", or "quantile" with p (0.5 the lower median): an element of the
+        resample, never an interpolation. The cell's scored values are resampled with replacement `reps` times by the
+        counter hash of the Monte-Carlo draws; the indices depend on (seed, replicate, slot, members scored) alone, so cells
+        with equal counts share them (common random numbers): with return_reps=True the replicates [G, reps] come back
+        too, and reps[g1] - reps[g2] is a paired bootstrap of the difference between two cells when draw m of every cell
+        carries the same perturbation. index = group_index(group, G). No host synchronisation; bit-reproducible. The rows of
+        the blocks of a sharded job do not combine: keep a cell inside one block."""
+        from .score import BOOT_FIRST, BOOT_MAX_REPS, BOOT_STATS
+        order, offset, G = self._group_index_arg("score_bootstrap", index)
+        for name, t in (("score", score), ("other", other)):
+            if t is not None and (tuple(t.shape) != (_lib.SCORE_ROWS, self.B) or t.dtype != self.dtype
+                                  or t.device != self.state.device or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous [12, %d] tensor of the handle's dtype on its device" % (name, self.B))
+        if stat not in BOOT_STATS or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("score_bootstrap: stat is one of %s, p in [0, 1]" % (BOOT_STATS,))
+        R = int(reps)
+        if not 2 <= R <= BOOT_MAX_REPS:
+            raise ValueError("score_bootstrap: 2 <= reps <= %d" % BOOT_MAX_REPS)
+        cprobs, nq = self._probs_arg("score_bootstrap", probs)
+        boot = torch.empty((G, BOOT_FIRST + nq), dtype=torch.float64, device=self.device)
+        rep = torch.empty((G, R), dtype=torch.float64, device=self.device)
+        work = torch.empty((self.B + G,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchScoreBootstrap(self.h, _ptr(score), _ptr(other), int(num), -1 if den is None else int(den),
+                                                       _ptr(order), _ptr(offset), G, BOOT_STATS.index(stat), float(p), R,
+                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, cprobs, nq, _ptr(boot), _ptr(rep),
+                                                       _ptr(work), self._stream()))
+        return (boot, rep) if return_reps else boot
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

@@ -22,6 +22,7 @@
 #include "umpc_score.h"    // scoring of recorded rollouts (umpcBatchScore / umpcBatchScoreGroups): stand-alone kernels
 #include "umpc_ensemble.h" // per-step, per-group statistics of recorded rollouts (umpcBatchEnsemble): stand-alone kernels
 #include "umpc_quantile.h" // per-step, per-group order statistics (umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles): stand-alone
+#include "umpc_bootstrap.h" // bootstrap intervals of a per-group cost table (umpcBatchScoreBootstrap): stand-alone
 #include "umpc_err.h"
 #include "umpc_n3_general.h"   // the N = 3 QP as data for the general-structure solver (compat bounds-reject path only)
 
@@ -1075,6 +1076,41 @@ static bool quant_probs_ok(const double *probs, int nq) {
   return true;
 }
 
+// umpcBatchScoreBootstrap has checked the arguments: compaction, the replicates of the small and of the large cells, the rows
+template <typename T>
+static int launch_score_bootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den, const int32_t *order,
+                                  const int32_t *offset, int G, int stat, double stat_p, int R, unsigned long long seed,
+                                  const double *probs, int nq, double *boot, double *reps, double *work, void *stream) {
+  umpc::BootCompactArgs<T> c;
+  c.score = (const T *)score; c.other = (const T *)other; c.order = order; c.offset = offset; c.work = work;
+  c.B = h->B; c.num = num; c.den = den;
+  umpc::BootArgs e;
+  e.offset = offset; e.work = work; e.boot = boot; e.reps = reps;
+  e.c0 = seed * 0x9E3779B97F4A7C15ull + umpc::kBootSalt;      // (wraps: the hash is arithmetic modulo 2^64)
+  e.stat_p = stat_p; e.B = h->B; e.R = R;
+  for (int j = 0; j < umpc::kQuantMaxProbs; ++j) e.q.p[j] = j < nq ? probs[j] : 0.0;
+  e.q.nq = nq;
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 block(64, umpc::kBootWaves);
+  if (other) hipLaunchKernelGGL((umpc::umpc_boot_compact_kernel<T, true>), dim3((unsigned)G), dim3(64), 0, s, c);
+  else hipLaunchKernelGGL((umpc::umpc_boot_compact_kernel<T, false>), dim3((unsigned)G), dim3(64), 0, s, c);
+  // a wavefront of the small-cell kernel takes chunks of 64 replicates; a block of the large-cell kernels one replicate
+  const int chunks = (R + 63) / 64;
+  const dim3 grid_a((unsigned)G, (unsigned)((chunks + umpc::kBootWaves - 1) / umpc::kBootWaves));
+  int gy = (4096 + G - 1) / G;
+  if (gy > R) gy = R;
+  const dim3 grid_b((unsigned)G, (unsigned)gy);
+  if (stat == UMPC_BOOT_MEAN) {
+    hipLaunchKernelGGL(umpc::umpc_boot_rep_kernel<umpc::kBootMean>, grid_a, block, 0, s, e);
+    hipLaunchKernelGGL(umpc::umpc_boot_mean_block_kernel, grid_b, block, 0, s, e);
+  } else {
+    hipLaunchKernelGGL(umpc::umpc_boot_rep_kernel<umpc::kBootQuantile>, grid_a, block, 0, s, e);
+    hipLaunchKernelGGL(umpc::umpc_boot_quantile_block_kernel, grid_b, block, 0, s, e);
+  }
+  hipLaunchKernelGGL(umpc::umpc_boot_row_kernel, dim3((unsigned)G), block, 0, s, e);
+  return launch_status("umpcBatchScoreBootstrap");
+}
+
 extern "C" {
 
 const char *umpcLastError(void) { return g_err.c_str(); }
@@ -1289,6 +1325,24 @@ int umpcBatchScoreQuantiles(umpc_batch_t *h, const void *score, int num, int den
   if (num < 0 || num >= UMPC_SCORE_ROWS || den < -1 || den >= UMPC_SCORE_ROWS) { g_err = "umpcBatchScoreQuantiles: bad argument (num in 0..11, den in -1..11)"; return -1; }
   return h->dtype == UMPC_F32 ? launch_score_quantiles<float>(h, score, num, den, order, offset, G, probs, nq, quant, stream)
                               : launch_score_quantiles<double>(h, score, num, den, order, offset, G, probs, nq, quant, stream);
+}
+int umpcBatchScoreBootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den,
+                            const int32_t *order, const int32_t *offset, int G, int stat, double stat_p,
+                            int R, unsigned long long seed, const double *probs, int nq,
+                            double *boot, double *reps, double *work, void *stream) {
+  if (!score || !order || !offset || !probs) { g_err = "umpcBatchScoreBootstrap: bad argument (score, order, offset and probs must be given)"; return -1; }
+  if (!boot || !reps || !work) { g_err = "umpcBatchScoreBootstrap: bad argument (boot [G][5 + nq], reps [G][R] and work [B + G] must be given)"; return -1; }
+  if (G < 1) { g_err = "umpcBatchScoreBootstrap: bad argument (G >= 1)"; return -1; }
+  if (R < 2 || R > UMPC_BOOT_MAX_REPS) { g_err = "umpcBatchScoreBootstrap: bad argument (2 <= R <= 1048576 replicates)"; return -1; }
+  if (stat != UMPC_BOOT_MEAN && stat != UMPC_BOOT_QUANTILE) { g_err = "umpcBatchScoreBootstrap: bad argument (stat is UMPC_BOOT_MEAN or UMPC_BOOT_QUANTILE)"; return -1; }
+  if (!(stat_p >= 0.0 && stat_p <= 1.0)) { g_err = "umpcBatchScoreBootstrap: bad argument (stat_p in [0, 1])"; return -1; }
+  if (!quant_probs_ok(probs, nq)) { g_err = "umpcBatchScoreBootstrap: bad argument (1 to 8 probabilities, each in [0, 1])"; return -1; }
+  if (num < 0 || num >= UMPC_SCORE_ROWS || den < -1 || den >= UMPC_SCORE_ROWS) { g_err = "umpcBatchScoreBootstrap: bad argument (num in 0..11, den in -1..11)"; return -1; }
+  // (the handle last: every other refusal can be met without one; nothing above reads it)
+  if (!h) { g_err = "umpcBatchScoreBootstrap: bad argument (no handle)"; return -1; }
+  return h->dtype == UMPC_F32
+             ? launch_score_bootstrap<float>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream)
+             : launch_score_bootstrap<double>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream);
 }
 
 int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,

@@ -2,7 +2,8 @@
 numpy fp64 mirrors. The device path is BatchUprightMPC.score / score_groups (batch.py); nothing here touches a device, and
 the mirrors are the definition the kernels are tested against, not a fallback. The same holds for the ensemble rows of
 umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble) and for the order statistics of
-umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles) further down.
+umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles) and the bootstrap of
+umpcBatchScoreBootstrap (score_bootstrap) further down.
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -35,6 +36,12 @@ Q_N, Q_SKIPPED, Q_FIRST = 0, 1, 2
 QUANT_MAX_PROBS = 8
 TERM_EP, TERM_ES, TERM_TAU = 0, 1, 2
 TERM_NAMES = ("ep", "es", "tau")
+# bootstrap rows, per group: members that enter, members that do not, the statistic of the cell's own values, the mean and
+# the standard error of the replicates, then one row per probability (the percentile interval)
+BOOT_N, BOOT_SKIPPED, BOOT_POINT, BOOT_MEAN, BOOT_SE, BOOT_FIRST = 0, 1, 2, 3, 4, 5
+BOOT_STATS = ("mean", "quantile")      # UMPC_BOOT_MEAN, UMPC_BOOT_QUANTILE
+BOOT_MAX_REPS = 1 << 20
+BOOT_SALT = 41
 
 
 def score_identity(B, dtype=np.float64):
@@ -314,3 +321,110 @@ def score_quantiles_reference(score, order, offset, probs, num, den=None):
         mem = order[offset[g]:offset[g + 1]]
         quant[g] = _quantile_row(x[mem[ok[mem]]], len(mem), probs)
     return quant
+
+
+def bootstrap_u01(seed, idx, salt):
+    """The counter hash of the library's Monte-Carlo draws (batch._u01, restated here because this module imports no torch):
+    idx + seed * 0x9E3779B97F4A7C15 + salt modulo 2^64, two multiply-xorshift rounds, the top 53 bits as a double in [0, 1).
+    idx: an array of counters, any integer dtype."""
+    with np.errstate(over="ignore"):
+        v = np.asarray(idx).astype(np.uint64) + np.uint64((int(seed) * 0x9E3779B97F4A7C15 + int(salt)) & 0xFFFFFFFFFFFFFFFF)
+        v ^= v >> np.uint64(30); v *= np.uint64(0xBF58476D1CE4E5B9)
+        v ^= v >> np.uint64(27); v *= np.uint64(0x94D049BB133111EB)
+        v ^= v >> np.uint64(31)
+    return (v >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+
+
+def bootstrap_indices(nsc, R, seed):
+    """[R, nsc] int64: the member slot m of replicate r takes, j = min(nsc - 1, floor(u * nsc)) in double with
+    u = bootstrap_u01(seed, (r << 32) + m, 41). A function of (seed, r, m, nsc) alone -- not of the cell, the number of cells
+    or anything else: cells with equal nsc are resampled with the same indices (common random numbers)."""
+    nsc, R = int(nsc), int(R)
+    idx = (np.arange(R, dtype=np.uint64)[:, None] << np.uint64(32)) + np.arange(nsc, dtype=np.uint64)[None, :]
+    u = bootstrap_u01(seed, idx, BOOT_SALT)
+    return np.minimum(nsc - 1, np.floor(u * float(nsc)).astype(np.int64))
+
+
+def _total_order_image(v):
+    """the unsigned image whose integer order is the total order of the doubles (-0 before +0): the kernels' quant_image"""
+    b = np.ascontiguousarray(v, np.float64).view(np.uint64)
+    return np.where(b >> np.uint64(63) != 0, ~b, b | np.uint64(1 << 63))
+
+
+def _boot_statistic(sample, stat, p):
+    """of one sample (a 1-d float64 array, at least one value): fsum / n, or the element at quantile_rank(p, n) of the sample
+    sorted by its total-order image"""
+    n = len(sample)
+    if stat == 0:
+        return math.fsum(sample.tolist()) / n
+    return float(sample[np.argsort(_total_order_image(sample), kind="stable")[quantile_rank(p, n)]])
+
+
+def score_bootstrap_values(score, num, den=None, other=None):
+    """(value [B] float64, enters [B] bool) of umpcBatchScoreBootstrap: x_b = score[num, b] or the IEEE double quotient
+    score[num, b] / score[den, b]; with `other` the same expression of the second table is subtracted in double. A robot
+    enters when row 0 > 0 in score (and in other, if given) and the value is finite."""
+    num, den = int(num), -1 if den is None else int(den)
+    if not 0 <= num < SCORE_ROWS or not -1 <= den < SCORE_ROWS:
+        raise ValueError("score_bootstrap_values: bad argument (num in 0..11, den in -1..11)")
+
+    def value(sc):
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            x = sc[num].astype(np.float64)
+            return x / sc[den].astype(np.float64) if den >= 0 else x
+    sc = np.asarray(score)
+    x, ok = value(sc), sc[STEPS] > 0
+    if other is not None:
+        ot = np.asarray(other)
+        if ot.shape != sc.shape or ot.dtype != sc.dtype:
+            raise ValueError("score_bootstrap_values: other must have the shape and dtype of score")
+        with np.errstate(invalid="ignore", over="ignore"):
+            x = x - value(ot)
+        ok = ok & (ot[STEPS] > 0)
+    return x, ok & np.isfinite(x)
+
+
+def score_bootstrap_reference(score, order, offset, num, den=None, other=None, stat="mean", p=0.5, reps=1000, seed=0,
+                              probs=(0.025, 0.975)):
+    """umpcBatchScoreBootstrap in numpy, cell by cell and replicate by replicate: (boot [G, 5 + nq], reps [G, R]).
+    The scored values of cell g in member-list order, v[0 .. nsc), are resampled R = reps times with bootstrap_indices(nsc,
+    R, seed); the statistic of a sample is its math.fsum divided by nsc (stat "mean") or the element at quantile_rank(p, nsc)
+    of the sample sorted in the total order of the values, -0 before +0 (stat "quantile"): an element, never an
+    interpolation. boot rows: BOOT_N scored, BOOT_SKIPPED the cell's other members, BOOT_POINT the statistic of v itself,
+    BOOT_MEAN fsum(t) / R over the replicates t, BOOT_SE sqrt(fsum((t - mean)^2) / (R - 1)), BOOT_FIRST + k the element
+    at quantile_rank(probs[k], R) of the sorted replicates (the percentile interval). nsc = 0: NaN from BOOT_POINT on and a NaN
+    row of reps. Every sum is an fsum: the mirror has no order of summation of its own.
+    Cells with equal nsc share their indices. Lay a sweep out so that draw m of every cell carries the same perturbation (the
+    task_table examples of INTEGRATION.md do): then reps[g1] - reps[g2] is a paired bootstrap of the difference between two
+    cells. With other= (the reactive run of the same sweep on the same tables) the values are differences paired by draw.
+    Like quantiles, the rows of the blocks of a sharded job do not combine: keep a cell inside one block."""
+    order, offset = np.asarray(order), np.asarray(offset)
+    G, R = len(offset) - 1, int(reps)
+    probs = _check_probs(probs, "score_bootstrap_reference")
+    if stat not in BOOT_STATS or not 0.0 <= float(p) <= 1.0 or not 2 <= R <= BOOT_MAX_REPS or G < 1:
+        raise ValueError("score_bootstrap_reference: bad argument (stat 'mean' or 'quantile', p in [0, 1], 2 <= reps <= 2^20)")
+    st, p = BOOT_STATS.index(stat), float(p)
+    x, ok = score_bootstrap_values(score, num, den, other)
+    boot = np.full((G, BOOT_FIRST + len(probs)), np.nan)
+    out = np.full((G, R), np.nan)
+    tables = {}
+    for g in range(G):
+        mem = order[offset[g]:offset[g + 1]]
+        v = x[mem[ok[mem]]]
+        nsc = len(v)
+        boot[g, BOOT_N], boot[g, BOOT_SKIPPED] = nsc, len(mem) - nsc
+        if nsc == 0:
+            continue
+        if nsc not in tables:
+            tables[nsc] = bootstrap_indices(nsc, R, seed)
+        t = out[g]
+        for r in range(R):
+            t[r] = _boot_statistic(v[tables[nsc][r]], st, p)
+        boot[g, BOOT_POINT] = _boot_statistic(v, st, p)
+        mean = math.fsum(t.tolist()) / R
+        boot[g, BOOT_MEAN] = mean
+        boot[g, BOOT_SE] = math.sqrt(math.fsum(((t - mean) ** 2).tolist()) / (R - 1))
+        ts = t[np.argsort(_total_order_image(t), kind="stable")]
+        for k, q in enumerate(probs):
+            boot[g, BOOT_FIRST + k] = ts[quantile_rank(q, R)]
+    return boot, out
