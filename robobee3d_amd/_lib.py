@@ -82,33 +82,6 @@ class UprightMPC_t(C.Structure):
 
 
 RESOURCE_LIMITS = os.path.join(HERE, "csrc", "resource_limits.json")
-# Limits of the kernels added since tests/test_reactive_steps.py (sha256 of the file) and tests/test_step_history.py (its exact
-# set of entries) hold csrc/resource_limits.json as it is: same format, checked by the same _validate_resources. Streaming
-# kernels: nothing may spill. A later change that may touch those two tests moves these entries into the file.
-RESOURCE_LIMITS_MORE = {
-    "umpc_ensemble_kernel": {"ScratchSize": 0},       # umpcBatchEnsemble: 8 forms by which tables there are x 2 dtypes
-    "umpc_group_index_kernel": {"ScratchSize": 0},    # umpcBatchGroupIndex
-}
-# The quantile kernels (csrc/umpc_quantile.h), kept apart because tests/test_ensemble.py holds the dict above to its two
-# entries: 20 forms each of the two ensemble-quantile kernels (term x which tables there are x dtype) and 2 of the
-# score-quantile kernel. Neither the in-register sort (groups of up to 64) nor the radix select (larger groups) may spill;
-# LDS is the radix select's static block (8 histograms of 256 counters, the prefixes, ranks and probabilities).
-RESOURCE_LIMITS_QUANT = {
-    "umpc_ens_quantile_kernel": {"ScratchSize": 0, "LDS": 0},              # umpcBatchEnsembleQuantiles, n <= 64
-    "umpc_ens_quantile_block_kernel": {"ScratchSize": 0, "LDS": 8360},     # umpcBatchEnsembleQuantiles, n > 64
-    "umpc_score_quantile_kernel": {"ScratchSize": 0, "LDS": 8360},         # umpcBatchScoreQuantiles
-}
-# The bootstrap kernels (csrc/umpc_bootstrap.h), one entry per kernel, apart for the same reason (tests/test_quantiles.py
-# holds the dict above to its three entries): 4 forms of the compaction (dtype x with / without a second table), 2 of the
-# small-cell replicate kernel (mean, quantile), one each of the others. LDS: the block mean's 256 partial sums; the radix
-# select's block plus its row of 10 doubles; that plus the 2 x 256 doubles of the row kernel's double-double tree.
-RESOURCE_LIMITS_BOOT = {
-    "umpc_boot_compact_kernel": {"ScratchSize": 0, "LDS": 0},
-    "umpc_boot_rep_kernel": {"ScratchSize": 0, "LDS": 0},                  # nsc <= 64: registers only
-    "umpc_boot_mean_block_kernel": {"ScratchSize": 0, "LDS": 2048},        # nsc > 64
-    "umpc_boot_quantile_block_kernel": {"ScratchSize": 0, "LDS": 8440},    # nsc > 64
-    "umpc_boot_row_kernel": {"ScratchSize": 0, "LDS": 12536},
-}
 
 
 def _check_resources(remarks):
@@ -142,8 +115,7 @@ def _validate_resources(res):
     import json
     if not os.path.exists(RESOURCE_LIMITS):
         return res
-    limits = dict(json.load(open(RESOURCE_LIMITS)), **RESOURCE_LIMITS_MORE, **RESOURCE_LIMITS_QUANT, **RESOURCE_LIMITS_BOOT)
-    for pat, lim in limits.items():
+    for pat, lim in json.load(open(RESOURCE_LIMITS)).items():
         hits = [k for k in res if pat in k]
         if not hits:
             raise RuntimeError("resource check: no kernel matches %r" % pat)

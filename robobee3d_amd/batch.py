@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .score import u01 as _u01      # counter-based uniform in [0, 1): a hash of (seed, global robot index, salt)
 
 _DT = {torch.float32: _lib.UMPC_F32, torch.float64: _lib.UMPC_F64}
 
@@ -27,15 +28,8 @@ def hover_initial_conditions(B, seed, dtype=np.float32, tilt=0.5, index_offset=0
     Returns state[18,B] (R column-major) and ref[9,B] (pdes=0, dpdes=0, sdes=e3)."""
     idx = np.arange(index_offset, index_offset + B, dtype=np.uint64)
     # counter-based: two uniforms per robot from a hash of (seed, index)
-    def u01(salt):
-        v = (idx + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(salt)) & np.uint64(0xFFFFFFFFFFFFFFFF)
-        v ^= v >> np.uint64(30); v *= np.uint64(0xBF58476D1CE4E5B9)
-        v ^= v >> np.uint64(27); v *= np.uint64(0x94D049BB133111EB)
-        v ^= v >> np.uint64(31)
-        return (v >> np.uint64(11)).astype(np.float64) / float(1 << 53)
-    with np.errstate(over="ignore"):
-        a = (2 * u01(1) - 1) * tilt
-        b = (2 * u01(2) - 1) * tilt
+    a = (2 * _u01(seed, idx, 1) - 1) * tilt
+    b = (2 * _u01(seed, idx, 2) - 1) * tilt
     ca, sa, cb, sb = np.cos(a), np.sin(a), np.cos(b), np.sin(b)
     # R = Rx(a) @ Ry(b)
     R = np.empty((B, 3, 3))
@@ -48,16 +42,6 @@ def hover_initial_conditions(B, seed, dtype=np.float32, tilt=0.5, index_offset=0
     ref = np.zeros((9, B), dtype)
     ref[8] = 1.0
     return state, ref
-
-
-def _u01(seed, idx, salt):
-    """Counter-based uniform in [0, 1): a hash of (seed, global robot index, salt)."""
-    with np.errstate(over="ignore"):
-        v = (idx + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(salt)) & np.uint64(0xFFFFFFFFFFFFFFFF)
-        v ^= v >> np.uint64(30); v *= np.uint64(0xBF58476D1CE4E5B9)
-        v ^= v >> np.uint64(27); v *= np.uint64(0x94D049BB133111EB)
-        v ^= v >> np.uint64(31)
-    return (v >> np.uint64(11)).astype(np.float64) / float(1 << 53)
 
 
 def monte_carlo_draws(B, seed, dtype=np.float32, spread=0.2, index_offset=0):
@@ -410,6 +394,40 @@ class BatchUprightMPC:
         """impulse_table() for this handle: [steps, 6, B] in its dtype, on its device."""
         return impulse_table(steps, self.B, events, self.dtype, self.device)
 
+    def _history_window(self, what, first, count):
+        """(hist, first, count) for a method `what` that reads the recorded steps first .. first + count - 1 of the step history;
+        count None = up to the history cursor"""
+        hist = getattr(self, "_hist", None)
+        if hist is None or hist["state"] is None:
+            raise RuntimeError("%s needs a step history with the state record (record_history)" % what)
+        cur = self.history_cursor
+        first = int(first)
+        count = cur - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > cur:
+            raise ValueError("%s: steps [%d, %d) are not inside the %d recorded steps" % (what, first, first + count, cur))
+        return hist, first, count
+
+    def _score_arg(self, name, t):
+        if (tuple(t.shape) != (_lib.SCORE_ROWS, self.B) or t.dtype != self.dtype or t.device != self.state.device
+                or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous [12, %d] tensor of the handle's dtype on its device" % (name, self.B))
+
+    def _out_arg(self, out, shape):
+        """`out` checked against `shape` [count, G, rows], or a new tensor of that shape"""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float64, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float64 or out.device != self.state.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [%d, %d, %d] float64 tensor on the handle's device" % shape)
+        return out
+
+    def _group_index_arg(self, what, index):
+        order, offset = index
+        G = int(offset.numel()) - 1
+        for t, n, name in ((order, self.B, "order"), (offset, G + 1, "offset")):
+            if tuple(t.shape) != (n,) or t.dtype != torch.int32 or t.device != self.state.device or not t.is_contiguous():
+                raise ValueError("%s: index must be the (order, offset) pair of group_index() of this handle (%s)" % (what, name))
+        return order, offset, G
+
     def _scoring_reference(self, what, first, count, ref_table, ref_first):
         """What the recorded steps first .. first + count - 1 are scored against (score, ensemble): (table, its first slice) --
         `ref_table` when given, else the table of set_reference_trajectory -- or (None, 0) for the constant `self.ref`; a
@@ -447,22 +465,14 @@ class BatchUprightMPC:
         trajectory / `self.ref` / the task: recorded step c is scored against its slice ref_first + c -- a run that followed
         per-robot tasks or the handle's task (reactive_steps, rollout) is scored against task_table(...) without switching
         the controller to step-held references."""
-        hist = getattr(self, "_hist", None)
-        if hist is None or hist["state"] is None:
-            raise RuntimeError("score needs a step history with the state record (record_history)")
-        cur = self.history_cursor
-        first = int(first)
-        count = cur - first if count is None else int(count)
-        if first < 0 or count < 0 or first + count > cur:
-            raise ValueError("score: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
+        hist, first, count = self._history_window("score", first, count)
         reftab, rfirst = self._scoring_reference("score", first, count, ref_table, ref_first)
         with torch.cuda.device(self.device):
             if score is None:
                 score = torch.empty((_lib.SCORE_ROWS, self.B), dtype=self.dtype, device=self.device)
                 self._check(self.L.umpcBatchScoreInit(self.h, _ptr(score), self._stream()))
-            elif (tuple(score.shape) != (_lib.SCORE_ROWS, self.B) or score.dtype != self.dtype or score.device != self.state.device
-                  or not score.is_contiguous()):
-                raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
+            else:
+                self._score_arg("score", score)
             self._check(self.L.umpcBatchScore(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
                                               _ptr(reftab), None if reftab is not None else _ptr(self.ref), first, count,
                                               rfirst, first if step0 is None else int(step0), float(tol), int(bool(after)),
@@ -478,9 +488,7 @@ class BatchUprightMPC:
         group = torch.as_tensor(group).to(torch.int32).to(self.device).contiguous()
         if tuple(group.shape) != (self.B,):
             raise ValueError("group must be [%d]" % self.B)
-        if (tuple(score.shape) != (_lib.SCORE_ROWS, self.B) or score.dtype != self.dtype or score.device != self.state.device
-                or not score.is_contiguous()):
-            raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
+        self._score_arg("score", score)
         gstat = torch.empty((int(G), _lib.GSCORE_ROWS), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             self._check(self.L.umpcBatchScoreGroups(self.h, _ptr(score), _ptr(group), int(G), _ptr(gstat), self._stream()))
@@ -509,39 +517,16 @@ class BatchUprightMPC:
         (step, group) row is independent and bit-reproducible; `out` [count, G, 16], when given, is overwritten and returned
         (a slice of a larger tensor serves a chunked run). Keep the cells contiguous in the batch (cell = b // 64): scattered
         ids are correct and an order of magnitude slower per load."""
-        hist = getattr(self, "_hist", None)
-        if hist is None or hist["state"] is None:
-            raise RuntimeError("ensemble needs a step history with the state record (record_history)")
-        order, offset = index
-        G = int(offset.numel()) - 1
-        for t, n, name in ((order, self.B, "order"), (offset, G + 1, "offset")):
-            if tuple(t.shape) != (n,) or t.dtype != torch.int32 or t.device != self.state.device or not t.is_contiguous():
-                raise ValueError("ensemble: index must be the (order, offset) pair of group_index() of this handle (%s)" % name)
-        cur = self.history_cursor
-        first = int(first)
-        count = cur - first if count is None else int(count)
-        if first < 0 or count < 0 or first + count > cur:
-            raise ValueError("ensemble: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
+        hist, first, count = self._history_window("ensemble", first, count)
+        order, offset, G = self._group_index_arg("ensemble", index)
         reftab, rfirst = self._scoring_reference("ensemble", first, count, ref_table, ref_first)
-        if out is None:
-            out = torch.empty((count, G, _lib.ENS_ROWS), dtype=torch.float64, device=self.device)
-        elif (tuple(out.shape) != (count, G, _lib.ENS_ROWS) or out.dtype != torch.float64 or out.device != self.state.device
-              or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous [%d, %d, 16] float64 tensor on the handle's device" % (count, G))
+        out = self._out_arg(out, (count, G, _lib.ENS_ROWS))
         with torch.cuda.device(self.device):
             self._check(self.L.umpcBatchEnsemble(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(hist["status"]),
                                                  _ptr(reftab), None if reftab is not None else _ptr(self.ref), first, count,
                                                  rfirst, float(tol), int(bool(after)), _ptr(order), _ptr(offset), G, _ptr(out),
                                                  self._stream()))
         return out
-
-    def _group_index_arg(self, what, index):
-        order, offset = index
-        G = int(offset.numel()) - 1
-        for t, n, name in ((order, self.B, "order"), (offset, G + 1, "offset")):
-            if tuple(t.shape) != (n,) or t.dtype != torch.int32 or t.device != self.state.device or not t.is_contiguous():
-                raise ValueError("%s: index must be the (order, offset) pair of group_index() of this handle (%s)" % (what, name))
-        return order, offset, G
 
     @staticmethod
     def _probs_arg(what, probs):
@@ -563,26 +548,15 @@ class BatchUprightMPC:
         reference is resolved as there. An element of the cell, never an interpolation: bit-reproducible and independent of
         everything but the member set. Quantiles of the blocks of a sharded job do not combine: keep a cell inside one block."""
         from .score import TERM_NAMES
-        hist = getattr(self, "_hist", None)
-        if hist is None or hist["state"] is None:
-            raise RuntimeError("ensemble_quantiles needs a step history with the state record (record_history)")
+        hist, first, count = self._history_window("ensemble_quantiles", first, count)
         order, offset, G = self._group_index_arg("ensemble_quantiles", index)
         if term not in TERM_NAMES:
             raise ValueError("ensemble_quantiles: term is one of %s" % (TERM_NAMES,))
         if term == "tau" and hist["out"] is None:
             raise RuntimeError("ensemble_quantiles: term 'tau' needs the out record of the step history")
         cprobs, nq = self._probs_arg("ensemble_quantiles", probs)
-        cur = self.history_cursor
-        first = int(first)
-        count = cur - first if count is None else int(count)
-        if first < 0 or count < 0 or first + count > cur:
-            raise ValueError("ensemble_quantiles: steps [%d, %d) are not inside the %d recorded steps" % (first, first + count, cur))
         reftab, rfirst = self._scoring_reference("ensemble_quantiles", first, count, ref_table, ref_first)
-        if out is None:
-            out = torch.empty((count, G, 2 + nq), dtype=torch.float64, device=self.device)
-        elif (tuple(out.shape) != (count, G, 2 + nq) or out.dtype != torch.float64 or out.device != self.state.device
-              or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous [%d, %d, %d] float64 tensor on the handle's device" % (count, G, 2 + nq))
+        out = self._out_arg(out, (count, G, 2 + nq))
         with torch.cuda.device(self.device):
             self._check(self.L.umpcBatchEnsembleQuantiles(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(reftab),
                                                           None if reftab is not None else _ptr(self.ref), first, count, rfirst,
@@ -597,9 +571,7 @@ class BatchUprightMPC:
         table that one crashed draw does not own, as it owns the sums of score_groups). A robot enters when its row 0 > 0
         and its value is finite; the group's other members are counted in row 1. index = group_index(group, G)."""
         order, offset, G = self._group_index_arg("score_quantiles", index)
-        if (tuple(score.shape) != (_lib.SCORE_ROWS, self.B) or score.dtype != self.dtype or score.device != self.state.device
-                or not score.is_contiguous()):
-            raise ValueError("score must be a contiguous [12, %d] tensor of the handle's dtype on its device" % self.B)
+        self._score_arg("score", score)
         cprobs, nq = self._probs_arg("score_quantiles", probs)
         quant = torch.empty((G, 2 + nq), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
@@ -624,10 +596,9 @@ class BatchUprightMPC:
         the blocks of a sharded job do not combine: keep a cell inside one block."""
         from .score import BOOT_FIRST, BOOT_MAX_REPS, BOOT_STATS
         order, offset, G = self._group_index_arg("score_bootstrap", index)
-        for name, t in (("score", score), ("other", other)):
-            if t is not None and (tuple(t.shape) != (_lib.SCORE_ROWS, self.B) or t.dtype != self.dtype
-                                  or t.device != self.state.device or not t.is_contiguous()):
-                raise ValueError("%s must be a contiguous [12, %d] tensor of the handle's dtype on its device" % (name, self.B))
+        self._score_arg("score", score)
+        if other is not None:
+            self._score_arg("other", other)
         if stat not in BOOT_STATS or not 0.0 <= float(p) <= 1.0:
             raise ValueError("score_bootstrap: stat is one of %s, p in [0, 1]" % (BOOT_STATS,))
         R = int(reps)

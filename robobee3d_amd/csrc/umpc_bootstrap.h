@@ -121,20 +121,12 @@ __device__ __forceinline__ void boot_wave_stat(double (&x)[NS], int nsc, int k, 
 
 // ---- 1. compaction ----------------------------------------------------------------------------------------------------
 // the value of robot b and whether it enters: quant_score_value's rule on one table, or on both and their difference
-template <typename T>
-__device__ __forceinline__ double boot_table_value(const T *score, size_t B, int num, int den, int b, bool &ok) {
-  const T n0 = score[b];
-  double x = (double)score[(size_t)num * B + b];
-  if (den >= 0) x = x / (double)score[(size_t)den * B + b];
-  ok = n0 > T(0);
-  return x;
-}
 template <typename T, bool PAIR>
 __device__ __forceinline__ double boot_score_value(const BootCompactArgs<T> &e, int b, bool &ok) {
-  double x = boot_table_value(e.score, (size_t)e.B, e.num, e.den, b, ok);
+  double x = score_table_value(e.score, (size_t)e.B, e.num, e.den, b, ok);
   if (PAIR) {
     bool ok2;
-    x = x - boot_table_value(e.other, (size_t)e.B, e.num, e.den, b, ok2);
+    x = x - score_table_value(e.other, (size_t)e.B, e.num, e.den, b, ok2);
     ok &= ok2;
   }
   ok &= __builtin_isfinite(x);
@@ -144,7 +136,7 @@ __device__ __forceinline__ double boot_score_value(const BootCompactArgs<T> &e, 
 template <typename T, bool PAIR>
 __global__ __launch_bounds__(64) void umpc_boot_compact_kernel(const BootCompactArgs<T> e) {
   const int g = blockIdx.x, lane = threadIdx.x;
-  const int lo = __builtin_amdgcn_readfirstlane(e.offset[g]), n = __builtin_amdgcn_readfirstlane(e.offset[g + 1]) - lo;
+  const auto [lo, n] = group_window(e.offset, g);
   const int32_t *mem = e.order + lo;
   double *v = e.work + lo;
   int at = 0;
@@ -288,7 +280,7 @@ __global__ __launch_bounds__(kBootThreads) void umpc_boot_row_kernel(const BootA
   __shared__ BootRowLds lds;
   const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y), tid = wave * 64 + lane;
   const int g = blockIdx.x;
-  const int n = __builtin_amdgcn_readfirstlane(e.offset[g + 1]) - __builtin_amdgcn_readfirstlane(e.offset[g]);
+  const int n = group_window(e.offset, g).n;
   const int nsc = __builtin_amdgcn_readfirstlane((int)e.work[(size_t)e.B + g]);
   const int R = e.R, nq = e.q.nq;
   double *boot = e.boot + (size_t)g * (kBootRows + nq);

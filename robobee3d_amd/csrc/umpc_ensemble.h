@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64 * kEnsWaves) void umpc_ensemble_kernel(const Ens
   // (blockDim = (64, kEnsWaves): threadIdx.y is the same in every lane of a wavefront -- said to the compiler)
   const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
   const int g = blockIdx.x;
-  const int lo = __builtin_amdgcn_readfirstlane(e.offset[g]), n = __builtin_amdgcn_readfirstlane(e.offset[g + 1]) - lo;
+  const auto [lo, n] = group_window(e.offset, g);
   const long long stride = (long long)gridDim.y * kEnsWaves, count = e.t.count;
   const int32_t *mem = e.order + lo;
   // the first trip's robot is the same for every step of this wavefront (n == 0: no trip, nothing is read)

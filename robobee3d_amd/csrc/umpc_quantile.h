@@ -299,11 +299,8 @@ struct QuantStepKey {
   __device__ __forceinline__ QuantKeyOf<T> operator()(int m, bool &ok) const {
     const size_t B = (size_t)a.B;
     const int b = mem[m];
-    T rc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
-    if (!TAB) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { rc[j] = a.ref[(size_t)j * B + b]; rc[3 + j] = a.ref[(size_t)(6 + j) * B + b]; }
-    }
+    T rc[6];
+    score_const_ref<T, TAB>(a, B, b, rc);
     ScoreStep<T> v;
     score_load<T, false, TAB, OUT, false>(a, B, 0, (unsigned)b, i, rc, v);
     const ScoreTerms<T> t = score_terms(a.taulim, v);
@@ -331,7 +328,7 @@ __global__ __launch_bounds__(kQuantThreads) void umpc_ens_quantile_block_kernel(
   __shared__ QuantLds lds;
   const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
   const int g = blockIdx.x;
-  const int lo = __builtin_amdgcn_readfirstlane(e.offset[g]), n = __builtin_amdgcn_readfirstlane(e.offset[g + 1]) - lo;
+  const auto [lo, n] = group_window(e.offset, g);
   if (n <= 64) return;
   quant_block_steps<T, TAB, OUT, TERM>(e, e.order + lo, n, g, lane, wave, lds);
 }
@@ -341,7 +338,7 @@ __global__ __launch_bounds__(kQuantThreads) void umpc_ens_quantile_kernel(const 
   // (blockDim = (64, kQuantWaves): threadIdx.y is the same in every lane of a wavefront -- said to the compiler)
   const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
   const int g = blockIdx.x;
-  const int lo = __builtin_amdgcn_readfirstlane(e.offset[g]), n = __builtin_amdgcn_readfirstlane(e.offset[g + 1]) - lo;
+  const auto [lo, n] = group_window(e.offset, g);
   if (n > 64) return;                                   // umpc_ens_quantile_block_kernel's
   const long long count = e.t.count;
   const int32_t *mem = e.order + lo;
@@ -367,14 +364,21 @@ __global__ __launch_bounds__(kQuantThreads) void umpc_ens_quantile_kernel(const 
   if (i < count) quant_steps<T, TAB, OUT, TERM, 1>(e, n, b, rc, p, lane, g, i, stride);
 }
 
-// the value of robot b for umpcBatchScoreQuantiles and whether it enters (the rule of umpcBatchScoreGroups: row 0 > 0)
+// the value of robot b in a score table, score[num][b] or the IEEE double quotient score[num][b] / score[den][b], and whether
+// the robot has one (the rule of umpcBatchScoreGroups: row 0 > 0)
+template <typename T>
+__device__ __forceinline__ double score_table_value(const T *score, size_t B, int num, int den, int b, bool &ok) {
+  const T n0 = score[b];
+  double x = (double)score[(size_t)num * B + b];
+  if (den >= 0) x = x / (double)score[(size_t)den * B + b];
+  ok = n0 > T(0);
+  return x;
+}
+// for umpcBatchScoreQuantiles: it enters when it is finite, too
 template <typename T>
 __device__ __forceinline__ double quant_score_value(const ScoreQuantArgs<T> &e, int b, bool &ok) {
-  const size_t B = (size_t)e.B;
-  const T n0 = e.score[b];
-  double x = (double)e.score[(size_t)e.num * B + b];
-  if (e.den >= 0) x = x / (double)e.score[(size_t)e.den * B + b];
-  ok = (n0 > T(0)) & __builtin_isfinite(x);
+  const double x = score_table_value(e.score, (size_t)e.B, e.num, e.den, b, ok);
+  ok = ok & __builtin_isfinite(x);
   return x;
 }
 
@@ -383,7 +387,7 @@ __global__ __launch_bounds__(kQuantThreads) void umpc_score_quantile_kernel(cons
   __shared__ QuantLds lds;
   const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
   const int g = blockIdx.x;
-  const int lo = __builtin_amdgcn_readfirstlane(e.offset[g]), n = __builtin_amdgcn_readfirstlane(e.offset[g + 1]) - lo;
+  const auto [lo, n] = group_window(e.offset, g);
   const int32_t *mem = e.order + lo;
   double *row = e.quant + (size_t)g * (2 + e.q.nq);
   if (n > 64) {

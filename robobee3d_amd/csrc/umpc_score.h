@@ -104,6 +104,22 @@ __device__ __forceinline__ void score_load(const ScoreArgs<T> &a, size_t B, size
   v.st = STAT ? score_ld<NT>(a.status + ((size_t)i * B + col) + lane) : 1;
 }
 
+// rc = the six words robot b reads of a constant reference (rows 0..2 and 6..8), fetched once per robot; zeros, and never
+// read, with a reference table. (ens_steps and umpc_ens_quantile_kernel keep these lines written out: with the call hipcc
+// allocates their scalar registers in another order.)
+template <typename T, bool TAB, typename I>
+__device__ __forceinline__ void score_const_ref(const ScoreArgs<T> &a, size_t B, I b, T (&rc)[6]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { rc[j] = TAB ? T(0) : a.ref[(size_t)j * B + b]; rc[3 + j] = TAB ? T(0) : a.ref[(size_t)(6 + j) * B + b]; }
+}
+
+// the members of group g are order[lo .. lo + n): the same in every lane, said to the compiler
+struct GroupWindow { int lo, n; };
+__device__ __forceinline__ GroupWindow group_window(const int32_t *offset, int g) {
+  const int lo = __builtin_amdgcn_readfirstlane(offset[g]);
+  return {lo, __builtin_amdgcn_readfirstlane(offset[g + 1]) - lo};
+}
+
 // what one robot-step contributes, in the dtype: the one place these expressions are written (the scoring kernel folds them
 // over the steps of a robot, the ensemble kernel of umpc_ensemble.h over the robots of a step)
 template <typename T>
@@ -162,11 +178,8 @@ __global__ __launch_bounds__(64 * kScoreSlices, sizeof(T) == 4 ? 4 : 2) void ump
   const bool live = b < B;                 // (a lane past the batch loads nothing, but meets the barrier)
   ScorePart<T> q;
   if (live) {
-    T rc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
-    if (!TAB) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) { rc[j] = a.ref[(size_t)j * B + b]; rc[3 + j] = a.ref[(size_t)(6 + j) * B + b]; }
-    }
+    T rc[6];
+    score_const_ref<T, TAB>(a, B, b, rc);
     // two steps per trip: the loads of both are issued before the first is used
     int i = slice;                         // (count <= 2^31 - 1 - 2 kScoreSlices, umpcBatchScore: no sum here wraps)
     for (; i + kScoreSlices < a.count; i += 2 * kScoreSlices) {

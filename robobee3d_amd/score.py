@@ -51,6 +51,23 @@ def score_identity(B, dtype=np.float64):
     return s
 
 
+def _step_terms(y, o, r, tl):
+    """What one step contributes, per robot: (ok, d, ep, es, p2, tau2) from the state slice y [18, B], the out slice o [9, B] or
+    None, the reference slice r [9, B] and taulim. ok: every word the step reads is finite; d = p - pdes [3, B], ep = |d|^2,
+    es = |s - sdes|^2, p2 = |p|^2, tau2 = the moments squared, clipped at +-taulim (zeros without an out slice)."""
+    p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
+    ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
+    if o is not None:
+        ok &= np.isfinite(o[1:3]).all(0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = p - pdes
+        ep = (d ** 2).sum(0)
+        es = ((s - sdes) ** 2).sum(0)
+        p2 = (p ** 2).sum(0)
+        tau2 = (np.clip(o[1:3], -tl, tl) ** 2).sum(0) if o is not None else np.zeros_like(ep)
+    return ok, d, ep, es, p2, tau2
+
+
 def score_reference(state_hist, out_hist, status_hist, ref, first, count, ref_first, step0, tol_p, after, taulim, score=None):
     """umpcBatchScore in numpy fp64, step by step in order. state_hist [.., 18, B], out_hist [.., 9, B] or None, status_hist
     [.., B] or None are taken as given; ref is a table [.., 9, B] (slice ref_first + i) or one constant reference [9, B].
@@ -68,18 +85,8 @@ def score_reference(state_hist, out_hist, status_hist, ref, first, count, ref_fi
     tol2, tl = float(tol_p) ** 2, float(taulim)
     for i in range(count):
         c, k = first + i, step0 + i
-        y = st[c + after]
-        r = ref[ref_first + i] if ref.ndim == 3 else ref
-        p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
-        ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
-        if out is not None:
-            ok &= np.isfinite(out[c, 1:3]).all(0)
-        with np.errstate(invalid="ignore", over="ignore"):
-            ep = ((p - pdes) ** 2).sum(0)
-            es = ((s - sdes) ** 2).sum(0)
-            p2 = (p ** 2).sum(0)
-            if out is not None:
-                tau2 = (np.clip(out[c, 1:3], -tl, tl) ** 2).sum(0)
+        ok, _, ep, es, p2, tau2 = _step_terms(st[c + after], None if out is None else out[c],
+                                              ref[ref_first + i] if ref.ndim == 3 else ref, tl)
         sc[SKIPPED] += ~ok
         sc[STEPS] += ok
         sc[SUM_EP, ok] += ep[ok]
@@ -171,17 +178,8 @@ def ensemble_reference(state_hist, out_hist, status_hist, ref, first, count, ref
     ens = np.zeros((count, G, ENS_ROWS))
     for i in range(count):
         c = first + i
-        y = st[c + after]
-        r = ref[ref_first + i] if ref.ndim == 3 else ref
-        p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
-        ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
-        if out is not None:
-            ok &= np.isfinite(out[c, 1:3]).all(0)
-        with np.errstate(invalid="ignore", over="ignore"):
-            d = p - pdes
-            ep = (d ** 2).sum(0)
-            es = ((s - sdes) ** 2).sum(0)
-            tau2 = (np.clip(out[c, 1:3], -tl, tl) ** 2).sum(0) if out is not None else np.zeros_like(ep)
+        ok, d, ep, es, _, tau2 = _step_terms(st[c + after], None if out is None else out[c],
+                                             ref[ref_first + i] if ref.ndim == 3 else ref, tl)
         for g in range(G):
             mem = order[offset[g]:offset[g + 1]]
             sel = mem[ok[mem]]                                  # the scored members, in list order
@@ -280,23 +278,23 @@ def ensemble_quantiles_reference(state_hist, out_hist, ref, first, count, ref_fi
     quant = np.zeros((count, G, 2 + len(probs)))
     for i in range(count):
         c = first + i
-        y = st[c + after]
-        r = ref[ref_first + i] if ref.ndim == 3 else ref
-        p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
-        ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
-        if out is not None:
-            ok &= np.isfinite(out[c, 1:3]).all(0)
-        with np.errstate(invalid="ignore", over="ignore"):
-            if term == TERM_EP:
-                x = ((p - pdes) ** 2).sum(0)
-            elif term == TERM_ES:
-                x = ((s - sdes) ** 2).sum(0)
-            else:
-                x = (np.clip(out[c, 1:3], -tl, tl) ** 2).sum(0)
+        ok, _, ep, es, _, tau2 = _step_terms(st[c + after], None if out is None else out[c],
+                                             ref[ref_first + i] if ref.ndim == 3 else ref, tl)
+        x = ep if term == TERM_EP else es if term == TERM_ES else tau2
         for g in range(G):
             mem = order[offset[g]:offset[g + 1]]
             quant[i, g] = _quantile_row(x[mem[ok[mem]]], len(mem), probs)
     return quant
+
+
+def _table_value(sc, num, den):
+    """(value [B] float64, enters [B] bool) of a score table [12, B]: sc[num], or the IEEE double quotient sc[num] / sc[den]
+    when den >= 0; a robot enters when its row 0 > 0 and the value is finite"""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        x = sc[num].astype(np.float64)
+        if den >= 0:
+            x = x / sc[den].astype(np.float64)
+    return x, (sc[STEPS] > 0) & np.isfinite(x)
 
 
 def score_quantiles_reference(score, order, offset, probs, num, den=None):
@@ -311,11 +309,7 @@ def score_quantiles_reference(score, order, offset, probs, num, den=None):
     probs = _check_probs(probs, "score_quantiles_reference")
     if G < 1 or not 0 <= num < SCORE_ROWS or not -1 <= den < SCORE_ROWS:
         raise ValueError("score_quantiles_reference: bad argument")
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        x = sc[num].astype(np.float64)
-        if den >= 0:
-            x = x / sc[den].astype(np.float64)
-    ok = (sc[STEPS] > 0) & np.isfinite(x)
+    x, ok = _table_value(sc, num, den)
     quant = np.zeros((G, 2 + len(probs)))
     for g in range(G):
         mem = order[offset[g]:offset[g + 1]]
@@ -323,16 +317,19 @@ def score_quantiles_reference(score, order, offset, probs, num, den=None):
     return quant
 
 
-def bootstrap_u01(seed, idx, salt):
-    """The counter hash of the library's Monte-Carlo draws (batch._u01, restated here because this module imports no torch):
-    idx + seed * 0x9E3779B97F4A7C15 + salt modulo 2^64, two multiply-xorshift rounds, the top 53 bits as a double in [0, 1).
-    idx: an array of counters, any integer dtype."""
+def u01(seed, idx, salt):
+    """The counter hash of the library's Monte-Carlo draws, the one numpy definition (batch._u01 is this function; the kernels'
+    boot_u01 and batch._u01_device restate it): idx + seed * 0x9E3779B97F4A7C15 + salt modulo 2^64, two multiply-xorshift
+    rounds, the top 53 bits as a double in [0, 1). idx: an array of counters, any integer dtype."""
     with np.errstate(over="ignore"):
         v = np.asarray(idx).astype(np.uint64) + np.uint64((int(seed) * 0x9E3779B97F4A7C15 + int(salt)) & 0xFFFFFFFFFFFFFFFF)
         v ^= v >> np.uint64(30); v *= np.uint64(0xBF58476D1CE4E5B9)
         v ^= v >> np.uint64(27); v *= np.uint64(0x94D049BB133111EB)
         v ^= v >> np.uint64(31)
     return (v >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+
+
+bootstrap_u01 = u01
 
 
 def bootstrap_indices(nsc, R, seed):
@@ -367,21 +364,17 @@ def score_bootstrap_values(score, num, den=None, other=None):
     num, den = int(num), -1 if den is None else int(den)
     if not 0 <= num < SCORE_ROWS or not -1 <= den < SCORE_ROWS:
         raise ValueError("score_bootstrap_values: bad argument (num in 0..11, den in -1..11)")
-
-    def value(sc):
-        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-            x = sc[num].astype(np.float64)
-            return x / sc[den].astype(np.float64) if den >= 0 else x
     sc = np.asarray(score)
-    x, ok = value(sc), sc[STEPS] > 0
+    x, ok = _table_value(sc, num, den)
     if other is not None:
         ot = np.asarray(other)
         if ot.shape != sc.shape or ot.dtype != sc.dtype:
             raise ValueError("score_bootstrap_values: other must have the shape and dtype of score")
+        y, ok2 = _table_value(ot, num, den)
         with np.errstate(invalid="ignore", over="ignore"):
-            x = x - value(ot)
-        ok = ok & (ot[STEPS] > 0)
-    return x, ok & np.isfinite(x)
+            x = x - y               # (finite only when both values are)
+        ok = ok & ok2 & np.isfinite(x)
+    return x, ok
 
 
 def score_bootstrap_reference(score, order, offset, num, den=None, other=None, stat="mean", p=0.5, reps=1000, seed=0,

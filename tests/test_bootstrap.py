@@ -273,31 +273,26 @@ def test_bootstrap_exports_and_refusals_without_a_handle():
 
 def test_bootstrap_kernels_use_no_scratch():
     """the resource remarks of the build: every form of the five bootstrap kernels has no private frame and the static LDS that
-    RESOURCE_LIMITS_BOOT states; a form with a frame is refused; the three older tables are as they were"""
+    its entry of csrc/resource_limits.json states; a form with a frame is refused"""
     import json
     from robobee3d_amd import _lib
     _lib.build()
     res = json.load(open(_lib.RESOURCES_JSON))
+    limits = json.load(open(_lib.RESOURCE_LIMITS))
     forms = {"umpc_boot_compact_kernel": (4, 0), "umpc_boot_rep_kernel": (2, 0), "umpc_boot_mean_block_kernel": (1, 2048),
              "umpc_boot_quantile_block_kernel": (1, 8440), "umpc_boot_row_kernel": (1, 12536)}
-    assert set(_lib.RESOURCE_LIMITS_BOOT) == set(forms)
+    assert {k for k in limits if "boot" in k} == set(forms)
     for pat, (n, lds) in forms.items():
         hits = [k for k in res if pat in k]
         assert len(hits) == n, (pat, hits)
         for k in hits:
             assert res[k]["ScratchSize"] == 0 and res[k]["LDS"] == lds, (k, res[k])
-        assert _lib.RESOURCE_LIMITS_BOOT[pat] == {"ScratchSize": 0, "LDS": lds}
+        assert {f: x for f, x in limits[pat].items() if f != "_note"} == {"ScratchSize": 0, "LDS": lds}
         with pytest.raises(RuntimeError, match=pat):
             _lib._validate_resources(dict(res, **{"a_form_of_%s_with_a_frame" % pat: {"ScratchSize": 8, "LDS": lds}}))
     assert len([k for k in res if "umpc_boot" in k]) == 9
     for older in ("umpc_score_quantile_kernel", "umpc_ens_quantile", "umpc_ensemble_kernel"):
         assert not [k for k in res if "umpc_boot" in k and older in k]
-    assert _lib.RESOURCE_LIMITS_MORE == {"umpc_ensemble_kernel": {"ScratchSize": 0}, "umpc_group_index_kernel": {"ScratchSize": 0}}
-    assert _lib.RESOURCE_LIMITS_QUANT == {"umpc_ens_quantile_kernel": {"ScratchSize": 0, "LDS": 0},
-                                          "umpc_ens_quantile_block_kernel": {"ScratchSize": 0, "LDS": 8360},
-                                          "umpc_score_quantile_kernel": {"ScratchSize": 0, "LDS": 8360}}
-    limits = json.load(open(_lib.RESOURCE_LIMITS))
-    assert not [k for k in limits if "boot" in k]
 
 
 # ------------------------------------------------------------------------------------------------------------------

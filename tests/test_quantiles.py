@@ -194,18 +194,17 @@ def test_quantile_kernels_use_no_scratch():
     from robobee3d_amd import _lib
     _lib.build()
     res = json.load(open(_lib.RESOURCES_JSON))
+    limits = json.load(open(_lib.RESOURCE_LIMITS))
     for pat, n, lds in (("umpc_ens_quantile_kernel", 20, 0), ("umpc_ens_quantile_block_kernel", 20, 8360),
                         ("umpc_score_quantile_kernel", 2, 8360)):
         hits = [k for k in res if pat in k]
         assert len(hits) == n, (pat, hits)
         for k in hits:
             assert res[k]["ScratchSize"] == 0 and res[k]["LDS"] == lds, (k, res[k])
-        assert _lib.RESOURCE_LIMITS_QUANT[pat] == {"ScratchSize": 0, "LDS": lds}
-    assert len(_lib.RESOURCE_LIMITS_QUANT) == 3
-    assert _lib.RESOURCE_LIMITS_MORE == {"umpc_ensemble_kernel": {"ScratchSize": 0}, "umpc_group_index_kernel": {"ScratchSize": 0}}
-    for pat in _lib.RESOURCE_LIMITS_QUANT:
+        assert {f: x for f, x in limits[pat].items() if f != "_note"} == {"ScratchSize": 0, "LDS": lds}
         with pytest.raises(RuntimeError, match=pat):
-            _lib._validate_resources(dict(res, **{"a_form_of_%s_with_a_frame" % pat: {"ScratchSize": 8, "LDS": _lib.RESOURCE_LIMITS_QUANT[pat]["LDS"]}}))
+            _lib._validate_resources(dict(res, **{"a_form_of_%s_with_a_frame" % pat: {"ScratchSize": 8, "LDS": lds}}))
+    assert len([k for k in limits if "quantile" in k and "boot" not in k]) == 3
 
 
 # ------------------------------------------------------------------------------------------------------------------
