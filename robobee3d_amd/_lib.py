@@ -10,10 +10,13 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO_PATH = os.path.join(HERE, "libumpc_mi355x.so")
-SRC = os.path.join(HERE, "csrc", "umpc_mi355x.hip")
-SRC_BQP = os.path.join(HERE, "csrc", "umpc_bqp.hip")
-OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
+CSRC = os.path.join(HERE, "csrc")
+SRC = os.path.join(CSRC, "umpc_mi355x.hip")          # the step path and the handle (tools/build_variant.py swaps this unit)
+CHECKED_UNITS = [SRC, os.path.join(CSRC, "umpc_scoring.hip"), os.path.join(CSRC, "umpc_sim.hip")]
+UNITS = CHECKED_UNITS + [os.path.join(CSRC, "umpc_bqp.hip")]      # build() adds the generated units of codegen_qp
+OBJ_DIR = os.path.join(CSRC, "_obj")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17"]
+RESOURCE_FLAGS = ["-Rpass-analysis=kernel-resource-usage"]     # CHECKED_UNITS: their kernels are held to resource_limits.json
 
 UMPC_F32, UMPC_F64 = 0, 1
 STATE_ROWS, CTRL_ROWS, REF_ROWS, OUT_ROWS, STAT_ROWS = 18, 127, 9, 9, 2
@@ -84,13 +87,12 @@ class UprightMPC_t(C.Structure):
 RESOURCE_LIMITS = os.path.join(HERE, "csrc", "resource_limits.json")
 
 
-def _check_resources(remarks):
-    """Parses hipcc's -Rpass-analysis=kernel-resource-usage remarks of the step-kernel translation unit and fails
-    the build when a kernel's register / scratch / LDS outcome is no longer the measured one (csrc/resource_limits.json):
-    the fp32 step kernel hands registers v0/v1/s[4:11] to a generated assembly block that clobbers v2-v245 and every
-    AGPR, so a compiler change that grows the scratch frame or drops the 512-register allocation must be seen here,
-    not as a silent slowdown on the GPU."""
-    import json
+def _parse_resources(remarks):
+    """{kernel: figures} from the -Rpass-analysis=kernel-resource-usage remarks of one hipcc run. build() keeps them next to
+    the object and fails when a kernel's register / scratch / LDS outcome is no longer the measured one
+    (csrc/resource_limits.json): the fp32 step kernel hands registers v0/v1/s[4:11] to a generated assembly block that
+    clobbers v2-v245 and every AGPR, so a compiler change that grows the scratch frame or drops the 512-register allocation
+    must be seen here, not as a silent slowdown on the GPU."""
     import re
     res, cur = {}, None
     for line in remarks.splitlines():
@@ -101,14 +103,10 @@ def _check_resources(remarks):
         m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    _validate_resources(res)
-    # persisted next to the object: a later build that REUSES the object validates this record again
-    with open(RESOURCES_JSON, "w") as f:
-        json.dump(res, f, indent=1, sort_keys=True)
     return res
 
 
-RESOURCES_JSON = os.path.join(OBJ_DIR, "resources.json")
+RESOURCES_JSON = os.path.join(OBJ_DIR, "resources.json")     # every unit's record merged: {kernel: figures}
 
 
 def _validate_resources(res):
@@ -130,9 +128,21 @@ def _validate_resources(res):
     return res
 
 
+def _stale(obj):
+    """Must this object be compiled again? Yes when it, its depfile (hipcc -MMD: the files the compiler read, relative to
+    csrc) or its resource record is missing, or when a file the depfile names is missing or newer than the object."""
+    try:
+        t = os.path.getmtime(obj)
+        os.stat(obj + ".resources.json")
+        deps = open(obj + ".d").read().replace("\\\n", " ").split(": ", 1)[1].split()
+        return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in deps)
+    except (OSError, IndexError):
+        return True
+
+
 def build(force=False, verbose=False):
     """Generate umpc_gen.h / umpc_admm_asm.h and compile the HIP library for gfx950 (works without a GPU).
-    One object per translation unit (recompiled only when it or its headers changed), then one link."""
+    One object per translation unit (recompiled only when it or a file it read changed), then one link."""
     from . import asmgen, asmgen64, asmstep, codegen, codegen_n3, codegen_qp
     sw = asmgen.generator_switches()
     # (a scratch COPY of the tree may be built under switches for A/B experiments: UMPC_VARIANT_ROOT must name exactly the
@@ -143,67 +153,53 @@ def build(force=False, verbose=False):
         # Variants are built by tools/build_variant.py into robobee3d_amd/variants/ and selected with UMPC_LIB.
         raise RuntimeError("generator switches are set in the environment (%s): refusing to regenerate the shipped kernels; "
                            "unset them, or build a variant with tools/build_variant.py" % " ".join("%s=%s" % kv for kv in sw.items()))
-    gen, _ = codegen.write()
-    gn3 = codegen_n3.write()
-    gasm, _ = asmgen.write()
-    gasm64 = asmgen64.write()[0]
-    gasm64q = asmgen64.write_quad()[0]
-    gstep, _ = asmstep.write()
-    gquad, _ = asmstep.write(quad=True)
-    greg, gqp_units = codegen_qp.write()
-    hdr = os.path.join(ROOT, "include", "umpc_mi355x.h")
-    csrc = os.path.join(HERE, "csrc")
-    units = [(SRC, [gen, gasm, gasm64, gasm64q, gstep, gquad, gn3, hdr] + [os.path.join(csrc, f) for f in ("umpc_step.h", "umpc_models.h", "umpc_score.h", "umpc_ensemble.h", "umpc_quantile.h", "umpc_bootstrap.h", "umpc_err.h")]),
-             (SRC_BQP, [hdr, greg, os.path.join(csrc, "umpc_bqp_common.h"), os.path.join(csrc, "umpc_err.h")])]
-    gen_hdrs = [os.path.join(csrc, "gen", f) for f in os.listdir(os.path.join(csrc, "gen")) if f.endswith(".h")]
-    units += [(u, [os.path.join(csrc, "umpc_bqp_common.h")] + gen_hdrs) for u in gqp_units]
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    codegen.write(), codegen_n3.write(), asmgen.write(), asmgen64.write(), asmgen64.write_quad()
+    asmstep.write(), asmstep.write(quad=True)
+    units = UNITS + codegen_qp.write()[1]
     os.makedirs(OBJ_DIR, exist_ok=True)
-    objs, relink = [], force or not os.path.exists(SO_PATH)
-    todo = []
-    for src, deps in units:
-        obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
-        objs.append(obj)
-        if (force or not os.path.exists(obj)
-                or any(os.path.getmtime(obj) < os.path.getmtime(d) for d in [src] + deps)):
-            extra = ["-Rpass-analysis=kernel-resource-usage"] if src == SRC else []
-            todo.append(["hipcc"] + HIPCC_FLAGS + extra + ["-c", "-o", obj, src])
-            relink = True
-    step_obj = os.path.join(OBJ_DIR, os.path.basename(SRC) + ".o")
-    if not any(c[-1] == SRC for c in todo):
-        # the step-kernel object is reused: its recorded resource usage must still pass (and must exist)
-        import json
-        try:
-            _validate_resources(json.load(open(RESOURCES_JSON)))
-        except Exception:
-            todo.insert(0, ["hipcc"] + HIPCC_FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", step_obj, SRC])
-            relink = True
-    for stale in set(os.listdir(OBJ_DIR)) - {os.path.basename(o) for o in objs} - {os.path.basename(RESOURCES_JSON)}:
-        os.remove(os.path.join(OBJ_DIR, stale))
-    # one hipcc per translation unit, at most one per host CPU at a time
-    running, width = [], max(1, min(len(todo), os.cpu_count() or 1))
-    while todo or running:
-        while todo and len(running) < width:
-            cmd = todo.pop(0)
-            if verbose:
-                print(" ".join(cmd))
-            running.append((cmd, subprocess.Popen(cmd, cwd=csrc, stderr=subprocess.PIPE)))
-        cmd, p = running.pop(0)
-        _, err = p.communicate()
+    objs = [os.path.join(OBJ_DIR, os.path.basename(src) + ".o") for src in units]
+    # the source goes to hipcc relative to csrc: the depfile then names local files only, the same on every machine
+    todo = [(obj, ["hipcc"] + HIPCC_FLAGS + (RESOURCE_FLAGS if src in CHECKED_UNITS else [])
+             + ["-MMD", "-MF", obj + ".d", "-c", "-o", obj, os.path.relpath(src, CSRC)])
+            for src, obj in zip(units, objs) if force or _stale(obj)]
+    relink = bool(todo) or not os.path.exists(SO_PATH)
+    keep = {os.path.basename(o) + ext for o in objs for ext in ("", ".d", ".resources.json")} | {os.path.basename(RESOURCES_JSON)}
+    for old in set(os.listdir(OBJ_DIR)) - keep:
+        os.remove(os.path.join(OBJ_DIR, old))
+    # one hipcc per translation unit; at most 16 at a time, fewer where the environment or the machine says so
+    # (os.cpu_count() is the whole machine, of which a job may own a part)
+    jobs = int(os.environ.get("CMAKE_BUILD_PARALLEL_LEVEL") or os.environ.get("MAX_JOBS") or 16)
+    def compile_unit(job):
+        obj, cmd = job
+        if verbose:
+            print(" ".join(cmd))
+        p = subprocess.run(cmd, cwd=CSRC, stderr=subprocess.PIPE)
+        err = p.stderr.decode()
         if p.returncode != 0:
-            for _, q in running:
-                q.kill()
-            raise RuntimeError("hipcc failed: %s\n%s" % (" ".join(cmd), (err or b"").decode()[-4000:]))
-        if cmd[-1] == SRC:
-            try:
-                _check_resources((err or b"").decode())
-            except Exception:
-                os.remove(cmd[-2])     # the object must not survive a failed check (it would be reused unchecked)
-                raise
+            raise RuntimeError("hipcc failed: %s\n%s" % (" ".join(cmd), err[-4000:]))
+        with open(obj + ".resources.json", "w") as f:      # (empty for a unit compiled without RESOURCE_FLAGS)
+            json.dump(_parse_resources(err), f, indent=1, sort_keys=True)
+
+    # (a slot is refilled as soon as ANY unit ends; after a failure the units already started end, the others never start)
+    pool = ThreadPoolExecutor(max(1, min(jobs, 16, os.cpu_count() or 1)))
+    try:
+        list(pool.map(compile_unit, todo))
+    finally:
+        pool.shutdown(cancel_futures=True)
+    # every build checks every kernel, whether its object is new or reused
+    res = {}
+    for obj in objs:
+        res.update(json.load(open(obj + ".resources.json")))
+    with open(RESOURCES_JSON, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+    _validate_resources(res)
     if relink or any(os.path.getmtime(SO_PATH) < os.path.getmtime(o) for o in objs):
         cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO_PATH] + objs
         if verbose:
             print(" ".join(cmd))
-        subprocess.run(cmd, check=True, cwd=csrc, stderr=None if verbose else subprocess.DEVNULL)
+        subprocess.run(cmd, check=True, cwd=CSRC, stderr=None if verbose else subprocess.DEVNULL)
     build_ext(verbose=verbose)
     return SO_PATH
 

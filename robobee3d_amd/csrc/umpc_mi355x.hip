@@ -1,5 +1,7 @@
 // libumpc_mi355x.so: HIP kernels (gfx950) + the C ABI declared in include/umpc_mi355x.h.
 // No torch, no reference code, no CPU fallback: every entry point launches a kernel.
+// This unit is the step path (the rollout kernels and their dispatch, the B = 1 drop-in) and the handle's bookkeeping;
+// scoring lives in umpc_scoring.hip, simulation without the solver in umpc_sim.hip, what they share in umpc_handle.h.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -11,19 +13,13 @@
 #include <mutex>
 #include <string>
 
-#include "../../include/umpc_mi355x.h"
+#include "umpc_handle.h"
 #include "umpc_step.h"
 #ifndef UMPC_STEP_ASM_HEADER   // tools/build_variant.py points this at another generated stream (A/B timing)
 #define UMPC_STEP_ASM_HEADER "umpc_step_asm.h"
 #endif
 #include UMPC_STEP_ASM_HEADER
 #include "umpc_step_asm_quad.h"   // the same stream with one robot per lane QUAD (asmquad.py): the latency-bound shapes
-#include "umpc_models.h"
-#include "umpc_score.h"    // scoring of recorded rollouts (umpcBatchScore / umpcBatchScoreGroups): stand-alone kernels
-#include "umpc_ensemble.h" // per-step, per-group statistics of recorded rollouts (umpcBatchEnsemble): stand-alone kernels
-#include "umpc_quantile.h" // per-step, per-group order statistics (umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles): stand-alone
-#include "umpc_bootstrap.h" // bootstrap intervals of a per-group cost table (umpcBatchScoreBootstrap): stand-alone
-#include "umpc_err.h"
 #include "umpc_n3_general.h"   // the N = 3 QP as data for the general-structure solver (compat bounds-reject path only)
 
 namespace {
@@ -31,18 +27,7 @@ namespace {
 using umpc::DevParams;
 using namespace umpcgen;
 
-constexpr int kBlock = 64;  // one wavefront per workgroup: 64 robots, no barriers anywhere
-
 thread_local std::string g_err;
-int fail(hipError_t e, const char *what) {
-  g_err = std::string(what) + ": " + hipGetErrorString(e);
-  return (int)e;
-}
-// after a kernel launch: 0, or the launch error under the entry point's name
-int launch_status(const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(e, what);
-}
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -179,33 +164,6 @@ __global__ __launch_bounds__(kBlock) void umpc_dropin_quad_kernel(const umpcasm:
 }
 
 template <typename T>
-__global__ __launch_bounds__(kBlock) void umpc_plant_kernel(DevParams<T> prm, int B_, int nsub, T *state,
-                                                            const T *u, const T *IbA, const T *gainA) {
-  const int b = blockIdx.x * kBlock + threadIdx.x;
-  if (b >= B_) return;
-  const size_t B = (size_t)B_;
-  T p[3], R[9], dq[6], uq[3], Ib[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { p[i] = state[(size_t)i * B + b]; uq[i] = u[(size_t)i * B + b]; }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = state[(size_t)(3 + i) * B + b];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) dq[i] = state[(size_t)(12 + i) * B + b];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Ib[i] = IbA ? IbA[(size_t)i * B + b] : prm.Ib[i];
-  const T gain = gainA ? gainA[b] : T(1);
-  const T Ibinv[3] = {T(1) / Ib[0], T(1) / Ib[1], T(1) / Ib[2]};
-#pragma nounroll
-  for (int s = 0; s < nsub; ++s) umpc::plant_step(p, R, dq, uq, prm.dtsim, Ib, Ibinv, gain, prm.plant_mode);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) state[(size_t)i * B + b] = p[i];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) state[(size_t)(3 + i) * B + b] = R[i];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) state[(size_t)(12 + i) * B + b] = dq[i];
-}
-
-template <typename T>
 __global__ __launch_bounds__(kBlock) void umpc_assemble_kernel(DevParams<T> prm, int B_, const T *state,
                                                                const T *ctrl, const T *refA, const T *IbA,
                                                                const T *actualT0, T *l, T *u, T *q, T *Px, T *Ax) {
@@ -258,261 +216,6 @@ __device__ __forceinline__ void assemble_rows(const DevParams<T> &prm, int B_, i
     for (int i = 0; i < 6; ++i) Ax[(size_t)(o++) * B + b] = qp.Btaudt[i];
 }
 
-// reactiveController (template/template_controllers.py:282-296) in the closed loop of controlTest with
-// useMPC=False (template/uprightmpc2.py:121-151): the reference evaluates it at every plant substep
-// (hlInterval=None); `every` > 1 holds the command for that many substeps (fixed schedule).
-// gains rows: kpos[2], kz[2], ks[2] (defaults 5e-3, 5e-1 | 1e-1, 1 | 10, 1e2).
-template <typename T>
-__device__ __forceinline__ void reactive_controller(const T (&p)[3], const T (&R)[9], const T (&dq)[6],
-                                                    const T (&pdes)[3], const T (&k)[6], T (&u)[3]) {
-  T sdes[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    sdes[i] = umpc::umpc_min(umpc::umpc_max(k[0] * (pdes[i] - p[i]) - k[1] * dq[i], T(-0.5)), T(0.5));
-  sdes[2] = T(1);
-  T ds[3], fT[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    ds[r] = -(R[r] * (-dq[4]) + R[r + 3] * dq[3]);      // -Rb e3h omega
-    fT[r] = k[4] * (R[6 + r] - sdes[r]) + k[5] * ds[r];
-  }
-  fT[2] = T(0);
-  // fAorn = -e3h Rb' fTorn = ((Rb' f)_y, -(Rb' f)_x, 0)
-  const T wx = (R[0] * fT[0] + R[1] * fT[1]) + R[2] * fT[2];
-  const T wy = (R[3] * fT[0] + R[4] * fT[1]) + R[5] * fT[2];
-  u[0] = k[2] * (pdes[2] - p[2]) - k[3] * dq[2];
-  u[1] = wy;
-  u[2] = -wx;
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void umpc_reactive_kernel(DevParams<T> prm, int B_, int nsteps, int every, T t0,
-                                                              T *state, const T *ref, const T *gains, const T *IbA,
-                                                              const T *gainA, T *out, T *stats, const T *imp, int nsub) {
-  const int b = blockIdx.x * kBlock + threadIdx.x;
-  if (b >= B_) return;
-  const size_t B = (size_t)B_;
-  T p[3], R[9], dq[6], Ib[3], rf0[9], k[6] = {T(5e-3), T(5e-1), T(1e-1), T(1e0), T(10e0), T(1e2)}, u[3] = {T(0), T(0), T(0)};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) p[i] = state[(size_t)i * B + b];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = state[(size_t)(3 + i) * B + b];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) dq[i] = state[(size_t)(12 + i) * B + b];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) rf0[i] = ref[(size_t)i * B + b];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Ib[i] = IbA ? IbA[(size_t)i * B + b] : prm.Ib[i];
-  if (gains) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) k[i] = gains[(size_t)i * B + b];
-  }
-  const T gain = gainA ? gainA[b] : T(1);
-  const T Ibinv[3] = {T(1) / Ib[0], T(1) / Ib[1], T(1) / Ib[2]};
-  T s_err = stats ? stats[b] : T(0), s_eff = stats ? stats[B + b] : T(0);
-#pragma nounroll
-  for (int ti = 0; ti < nsteps; ++ti) {
-    if (ti % every == 0) {
-      T rf[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) rf[i] = rf0[i];
-      umpc::task_reference(prm.task, prm.task_p, t0 + T(ti) * prm.dtsim, rf);
-      const T pdes[3] = {rf[0], rf[1], rf[2]};
-      reactive_controller(p, R, dq, pdes, k, u);
-      u[1] = umpc::umpc_min(umpc::umpc_max(u[1], -prm.taulim), prm.taulim);
-      u[2] = umpc::umpc_min(umpc::umpc_max(u[2], -prm.taulim), prm.taulim);
-    }
-    umpc::plant_step(p, R, dq, u, prm.dtsim, Ib, Ibinv, gain, prm.plant_mode);
-    s_err += p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
-    s_eff += u[1] * u[1] + u[2] * u[2];
-    // velocity impulses (umpcBatchSetImpulses): slice j of `imp` after substep (j + 1) * nsub - 1, where the rollout adds it
-    if (imp && (ti + 1) % nsub == 0) {
-      const T *const imp_j = imp + (size_t)((ti + 1) / nsub - 1) * 6 * B;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) dq[i] += imp_j[(size_t)i * B + b];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) state[(size_t)i * B + b] = p[i];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) state[(size_t)(3 + i) * B + b] = R[i];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) state[(size_t)(12 + i) * B + b] = dq[i];
-  if (out) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[(size_t)i * B + b] = u[i];
-  }
-  if (stats) { stats[b] = s_err; stats[B + b] = s_eff; }
-}
-
-// The reactive baseline on the tables of the MPC rollout (umpcBatchReactiveRollout): K closed-loop steps of nsub substeps,
-// with a reference per robot, the impulse table and the step history. Where pdes comes from is decided on the host, once
-// per call, and is a template parameter: the substep loop holds no test of a table pointer and no load.
-//   kRefHandle  the handle's task at t = t0 + T(k nsub + j) dtsim -- the expression of umpc_reactive_kernel, so with no
-//               table set the two kernels run the same arithmetic on the same values
-//   kRefRobot   the same expression with the robot's own task id and parameters (lanes of different tasks diverge inside
-//               task_reference: a sweep keeps the robots of one task adjacent)
-//   kRefTable   rows 0..2 of one slice of the reference trajectory per step, held over its substeps: no time expression
-// One lane per robot, robot index fastest: every access below is one coalesced row segment, nothing crosses robots. The
-// table pointers move on one slice per step as 64-bit pointers, so a table may pass 4 GB.
-enum { kRefHandle = 0, kRefRobot = 1, kRefTable = 2 };
-
-template <typename T>
-struct ReactiveSteps {
-  DevParams<T> prm;
-  int B, K, nsub, every;
-  T t0;
-  T *state;
-  const T *ref, *gains, *Ib, *gain;
-  T *out, *stats;
-  const int32_t *task;     // kRefRobot: [B] ids
-  const T *task_params;    // kRefRobot: [4][B] or null (= the handle's)
-  const T *reftab;         // kRefTable: the slice of step 0
-  const T *imp;            // the impulse slice of step 0, or null
-  T *h_state;              // the history slices of step 0 (state: the slice BEFORE it), each may be null
-  T *h_out;
-  int32_t *h_status;
-  T *h_info;
-};
-
-template <typename T, int SRC>
-__global__ __launch_bounds__(kBlock) void umpc_reactive_steps_kernel(ReactiveSteps<T> a) {
-  const int b = blockIdx.x * kBlock + threadIdx.x;
-  if (b >= a.B) return;
-  const size_t B = (size_t)a.B;
-  const DevParams<T> &prm = a.prm;
-  T p[3], R[9], dq[6], Ib[3], ip[3] = {T(0), T(0), T(0)}, tp[4];
-  T k[6] = {T(5e-3), T(5e-1), T(1e-1), T(1e0), T(10e0), T(1e2)}, u[3] = {T(0), T(0), T(0)};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) p[i] = a.state[(size_t)i * B + b];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = a.state[(size_t)(3 + i) * B + b];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) dq[i] = a.state[(size_t)(12 + i) * B + b];
-  // state slice c of the history: the registers just loaded
-  T *hs = a.h_state;
-  if (hs) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) hs[(size_t)i * B + b] = p[i];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) hs[(size_t)(3 + i) * B + b] = R[i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) hs[(size_t)(12 + i) * B + b] = dq[i];
-    hs += 18 * B;
-  }
-  int tk = prm.task;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) tp[i] = prm.task_p[i];
-  if constexpr (SRC != kRefTable) {
-    // (the reactive controller reads pdes only, and every generator takes rows 0..2 = initialPos and nothing else)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ip[i] = a.ref[(size_t)i * B + b];
-  }
-  if constexpr (SRC == kRefRobot) {
-    tk = a.task[b];
-    if (a.task_params) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) tp[i] = a.task_params[(size_t)i * B + b];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Ib[i] = a.Ib ? a.Ib[(size_t)i * B + b] : prm.Ib[i];
-  if (a.gains) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) k[i] = a.gains[(size_t)i * B + b];
-  }
-  const T gain = a.gain ? a.gain[b] : T(1);
-  const T Ibinv[3] = {T(1) / Ib[0], T(1) / Ib[1], T(1) / Ib[2]};
-  T s_err = a.stats ? a.stats[b] : T(0), s_eff = a.stats ? a.stats[B + b] : T(0);
-  const T *imp = a.imp, *rt = a.reftab;
-  T *ho = a.h_out, *hi = a.h_info;
-  int32_t *hst = a.h_status;
-  int ti = 0;
-#pragma nounroll
-  for (int ks = 0; ks < a.K; ++ks) {
-    // the words of this step that come from tables, ahead of its substeps (which hide the miss); used after the last one
-    T kick[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, pdes[3] = {ip[0], ip[1], ip[2]};
-    if (imp) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) kick[i] = imp[(size_t)i * B + b];
-      imp += 6 * B;
-    }
-    if constexpr (SRC == kRefTable) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) pdes[i] = rt[(size_t)i * B + b];
-      rt += 9 * B;
-    }
-    int hold = 0;      // substeps until the controller fires again: j % every == 0, counted down
-#pragma nounroll
-    for (int j = 0; j < a.nsub; ++j, ++ti) {
-      if (hold == 0) {
-        hold = a.every;
-        if constexpr (SRC != kRefTable) {
-          T rf[9] = {ip[0], ip[1], ip[2], T(0), T(0), T(0), T(0), T(0), T(0)};
-          umpc::task_reference(tk, tp, a.t0 + T(ti) * prm.dtsim, rf);
-          pdes[0] = rf[0]; pdes[1] = rf[1]; pdes[2] = rf[2];
-        }
-        reactive_controller(p, R, dq, pdes, k, u);
-        u[1] = umpc::umpc_min(umpc::umpc_max(u[1], -prm.taulim), prm.taulim);
-        u[2] = umpc::umpc_min(umpc::umpc_max(u[2], -prm.taulim), prm.taulim);
-      }
-      --hold;
-      umpc::plant_step(p, R, dq, u, prm.dtsim, Ib, Ibinv, gain, prm.plant_mode);
-      s_err += p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
-      s_eff += u[1] * u[1] + u[2] * u[2];
-    }
-    // velocity impulse of the step (umpcBatchSetImpulses): after its last substep, ahead of everything it stores
-    if (imp) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) dq[i] += kick[i];
-    }
-    // the records of the step (wave-uniform tests, once per step; the stores are issued and not waited for)
-    if (hs) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) hs[(size_t)i * B + b] = p[i];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) hs[(size_t)(3 + i) * B + b] = R[i];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) hs[(size_t)(12 + i) * B + b] = dq[i];
-      hs += 18 * B;
-    }
-    if (ho) {      // (thrust, clipped moments, accdes = 0: a reactive controller has none)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) ho[(size_t)i * B + b] = u[i];
-#pragma unroll
-      for (int i = 3; i < 9; ++i) ho[(size_t)i * B + b] = T(0);
-      ho += 9 * B;
-    }
-    if (hst) { hst[b] = 1; hst += B; }      // OSQP_SOLVED: the step counts as solved in a score
-    if (hi) { hi[b] = T(0); hi[B + b] = T(0); hi += 2 * B; }
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) a.state[(size_t)i * B + b] = p[i];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) a.state[(size_t)(3 + i) * B + b] = R[i];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) a.state[(size_t)(12 + i) * B + b] = dq[i];
-  if (a.out) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) a.out[(size_t)i * B + b] = u[i];
-  }
-  if (a.stats) { a.stats[b] = s_err; a.stats[B + b] = s_eff; }
-}
-
-// (pdes, dpdes, sdes) of the handle's task at time t for every robot (what the step kernel evaluates at a fire)
-template <typename T>
-__global__ void umpc_taskref_kernel(DevParams<T> prm, int B_, T t, const T *ref, T *out) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B_) return;
-  const size_t B = (size_t)B_;
-  T r[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r[i] = ref[(size_t)i * B + b];
-  umpc::task_reference(prm.task, prm.task_p, t, r);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out[(size_t)i * B + b] = r[i];
-}
-
 // Task table of the all-assembly step kernel: the time-dependent part of (pdes, dpdes, sdes) is the same for every
 // robot (template/flight_tasks.py:6-49 add it to initialPos), so it is evaluated ONCE per closed-loop step of the
 // launch -- 8 floats per step: dp[3], dpdes[3], sdes_x, sdes_z (sdes_y is 0 in every task) -- with the same
@@ -527,36 +230,6 @@ __global__ void umpc_taskf_kernel(DevParams<float> prm, int K, float t0, float *
   o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = r[5]; o[6] = r[6]; o[7] = r[8];
 }
 
-// Per-robot task tables (umpcBatchTaskTable): slice k of tab [steps][9][B] = task_reference(task[b], params[.][b], t_k, ref
-// column b) at the fire time t_k of closed-loop step k -- the SAME device function and the SAME expression for t_k, in the
-// same scalar type, as closed_loop_step (umpc_step.h) and umpc_taskf_kernel, so a table with batch-constant parameters holds
-// exactly what the step kernel would generate. 2-D grid: x = robots (robot index fastest: every store of a warp is one
-// coalesced row segment), y = a grid stride over the steps; a thread loads its robot's task, parameters and ref column once
-// and reuses them for all its steps. task 0 copies the ref column.
-template <typename T>
-__global__ void umpc_task_table_kernel(DevParams<T> prm, int B_, long long steps, T t0, const int32_t *task, const T *params,
-                                       const T *ref, T *tab) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B_) return;
-  const size_t B = (size_t)B_;
-  const int tk = task ? task[b] : prm.task;
-  T tp[4], r0[9];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) tp[i] = params ? params[(size_t)i * B + b] : prm.task_p[i];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r0[i] = ref[(size_t)i * B + b];
-  for (long long k = blockIdx.y; k < steps; k += gridDim.y) {
-    T r[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r[i] = r0[i];
-    const T tnow = t0 + T(k) * (T(prm.nsub) * prm.dtsim);
-    umpc::task_reference(tk, tp, tnow, r);
-    T *o = tab + (size_t)k * 9 * B;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o[(size_t)i * B + b] = r[i];
-  }
-}
-
 template <typename T>
 __global__ void umpc_init_ctrl_kernel(int B_, T *ctrl) {
   const size_t B = (size_t)B_;
@@ -565,78 +238,7 @@ __global__ void umpc_init_ctrl_kernel(int B_, T *ctrl) {
     ctrl[i] = (i / B) >= (size_t)(NX + 2 * NC + 1) ? T(1) : T(0);
 }
 
-template <typename T>
-DevParams<T> make_dev(const umpc_batch_params_t &p) {
-  DevParams<T> d;
-  d.dt = (T)p.dt; d.g = (T)p.g;
-  d.Tmax = (T)p.TtoWmax * (T)p.g;  // uprightmpc2.c:25
-  d.wpr = (T)p.wpr; d.wpf = (T)p.wpf; d.ws = (T)p.ws; d.wvr = (T)p.wvr; d.wvf = (T)p.wvf;
-  d.wds = (T)p.wds; d.wthrust = (T)p.wthrust; d.wmom = (T)p.wmom;
-  for (int i = 0; i < 3; ++i) d.Ib[i] = (T)p.Ib[i];
-  d.dtsim = (T)p.dtsim; d.taulim = (T)p.taulim;
-  d.maxIter = p.maxIter; d.nsub = p.nsub; d.plant_mode = p.plant_mode;
-  d.task = 0;
-  for (int i = 0; i < 4; ++i) d.task_p[i] = T(0);
-  return d;
-}
-
 }  // namespace
-
-// A table the handle keeps by pointer and walks with a cursor (reference trajectory, step history, impulses): `steps` slices,
-// the next closed-loop step uses slice `cursor`. One rule for all of them: a setter takes 0 <= cursor0 <= steps, and a launch
-// that would pass the end is refused before anything is launched or copied.
-struct CursorTable {
-  long long steps = 0, cursor = 0;
-  static bool valid(const char *setter, long long steps, long long cursor0) {
-    if (steps >= 1 && cursor0 >= 0 && cursor0 <= steps) return true;
-    g_err = std::string(setter) + ": bad argument (steps >= 1, 0 <= cursor0 <= steps)";
-    return false;
-  }
-  // do the n slices of a launch fit? `n_name` is what the message calls n ("K " in a rollout)
-  bool fits(const char *who, const char *table, const char *n_name, long long n) const {
-    if (cursor + n <= steps) return true;
-    g_err = std::string(who) + ": the " + table + " ends before the launch does (cursor " + std::to_string(cursor) + " + " + n_name +
-            std::to_string(n) + " > steps " + std::to_string(steps) + ")";
-    return false;
-  }
-};
-
-struct umpc_batch {
-  umpc_batch_params_t prm;
-  int B, dtype;
-  long long global_B = 0;        // size of the whole (sharded) job, umpcBatchSetGlobalBatch; the lane / quad choice is made from it
-  int task = 0;
-  double task_p[4] = {0, 0, 0, 0};
-  double t_ms = 0;               // time of the next MPC step
-  const void *weights = nullptr;  // [8][B] device table or null
-  void *ws;  // [WS_ROWS][B] scratch the step parks Ruiz scalings / x_prev / delta_y in
-  int step_kernel = 0;            // 0 = automatic, 1 = always the C++ / loop-assembly kernel, 2 / 3 = the all-assembly stream with one lane / one lane quad per robot
-  umpc::WLDev *wl = nullptr;      // device copy of the WL parameters (umpcBatchSetWL), null = no coupling
-  void *wlu = nullptr, *wlw = nullptr;
-  float wl_md2 = 0.f;             // M0[2,2] of the WL coupling (host copy, for the kernel's mb g)
-  const char *last_kernel = "";   // the kernel the last umpcBatchRollout / umpcBatchUpdate dispatched (umpcBatchKernelName)
-  float *taskf = nullptr;         // task table of the all-assembly kernel: 8 floats per step of a launch
-  int taskf_cap = 0;              // ... steps it holds
-  const void *reftab = nullptr;   // reference trajectory [steps][9][B] (umpcBatchSetRefTrajectory), kept by pointer; null = off
-  CursorTable ref_c;              // ... its slices; the cursor is the slice the next closed-loop step reads
-  // step history (umpcBatchSetHistory), kept by pointer; each may be null = that record is off
-  void *hist_state = nullptr;     // [steps+1][18][B]
-  void *hist_out = nullptr;       // [steps][9][B]
-  int32_t *hist_status = nullptr; // [steps][B]
-  void *hist_info = nullptr;      // [steps][2][B]
-  CursorTable hist_c;             // ... the steps the tables hold; the cursor is the step the next rollout records first
-  const void *imptab = nullptr;   // velocity impulses [steps][6][B] (umpcBatchSetImpulses), kept by pointer; null = off
-  CursorTable imp_c;              // ... its slices; the cursor is the slice the next closed-loop step adds
-  // the history and the impulses belong to closed-loop steps with a plant: only those are recorded, kicked and range-checked,
-  // and only they advance the two cursors (the reference trajectory is read, and checked, by every call)
-  bool hist_on(int K, int nsub) const { return (hist_state || hist_out || hist_status || hist_info) && nsub > 0 && K >= 1; }
-  bool imp_on(int K, int nsub) const { return imptab && nsub > 0 && K >= 1; }
-  // THE place the clock and the cursors advance: callers come here after every launch and copy of their call has returned
-  // hipSuccess, so a refused or failed call leaves the handle where it was
-  void advance(double ms, long long ref_n, long long hist_n, long long imp_n) {
-    t_ms += ms; ref_c.cursor += ref_n; hist_c.cursor += hist_n; imp_c.cursor += imp_n;
-  }
-};
 
 // the caller's arrays of one umpcBatchRollout / umpcBatchUpdate, by name (null = not given)
 struct RolloutArrays {
@@ -649,15 +251,6 @@ struct RolloutArrays {
 
 // elements the state / out / status / info pointers advance per closed-loop step of one launch (0 = in place)
 struct HistStep { size_t state = 0, out = 0, status = 0, info = 0; };
-
-// DevParams of a handle, its task included
-template <typename T>
-static DevParams<T> make_dev_task(const umpc_batch_t *h) {
-  DevParams<T> d = make_dev<T>(h->prm);
-  d.task = h->task;
-  for (int i = 0; i < 4; ++i) d.task_p[i] = (T)h->task_p[i];
-  return d;
-}
 
 // after a launch: the kernel's name for umpcBatchKernelName, and the launch error if there is one
 static int launched(umpc_batch_t *h, const char *kernel) {
@@ -877,259 +470,6 @@ static int launch_rollout(umpc_batch_t *h, int K, int nsub, const RolloutArrays 
 
 void umpc_set_error(const char *msg) { g_err = msg; }
 
-template <typename T>
-static int launch_reactive(umpc_batch_t *h, int nsteps, int every, void *state, const void *ref, const void *gains,
-                           const void *Ib, const void *gain, void *out, void *stats, void *stream) {
-  const int grid = (h->B + kBlock - 1) / kBlock;
-  // velocity impulses: slice cursor + j after substep (j + 1) * nsub - 1 (umpcBatchReactive has made the range checks)
-  const int nsub = h->prm.nsub;
-  const T *imp = h->imptab ? (const T *)h->imptab + (size_t)h->imp_c.cursor * 6 * (size_t)h->B : nullptr;
-  hipLaunchKernelGGL(umpc_reactive_kernel<T>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, make_dev_task<T>(h), h->B, nsteps, every,
-                     (T)h->t_ms, (T *)state, (const T *)ref, (const T *)gains, (const T *)Ib, (const T *)gain, (T *)out,
-                     (T *)stats, imp, nsub > 0 ? nsub : 1);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(e, "umpcBatchReactive");      // (the clock and the cursor stay where they were)
-  h->advance((double)nsteps * h->prm.dtsim, 0, 0, imp ? nsteps / nsub : 0);
-  return 0;
-}
-
-// umpcBatchReactiveRollout has made every check; the slices of the three tables are taken from the cursors here, the form of
-// the kernel is chosen from where the reference comes from, and the clock and the cursors move last
-template <typename T>
-static int launch_reactive_steps(umpc_batch_t *h, int K, int every, void *state, const void *ref, const void *gains,
-                                 const int32_t *task, const void *task_params, const void *Ib, const void *gain, void *out,
-                                 void *stats, void *stream) {
-  const int nsub = h->prm.nsub;
-  const bool hist = h->hist_on(K, nsub), imp = h->imp_on(K, nsub);
-  const size_t B = (size_t)h->B, c = (size_t)h->hist_c.cursor;
-  ReactiveSteps<T> a;
-  a.prm = make_dev_task<T>(h);
-  a.B = h->B; a.K = K; a.nsub = nsub; a.every = every; a.t0 = (T)h->t_ms;
-  a.state = (T *)state; a.ref = (const T *)ref; a.gains = (const T *)gains; a.Ib = (const T *)Ib; a.gain = (const T *)gain;
-  a.out = (T *)out; a.stats = (T *)stats;
-  a.task = task; a.task_params = (const T *)task_params;
-  a.reftab = h->reftab ? (const T *)h->reftab + (size_t)h->ref_c.cursor * 9 * B : nullptr;
-  a.imp = imp ? (const T *)h->imptab + (size_t)h->imp_c.cursor * 6 * B : nullptr;
-  a.h_state = hist && h->hist_state ? (T *)h->hist_state + c * 18 * B : nullptr;
-  a.h_out = hist && h->hist_out ? (T *)h->hist_out + c * 9 * B : nullptr;
-  a.h_status = hist && h->hist_status ? h->hist_status + c * B : nullptr;
-  a.h_info = hist && h->hist_info ? (T *)h->hist_info + c * 2 * B : nullptr;
-  const dim3 grid((unsigned)((h->B + kBlock - 1) / kBlock)), block(kBlock);
-  const hipStream_t s = (hipStream_t)stream;
-  if (h->reftab) hipLaunchKernelGGL((umpc_reactive_steps_kernel<T, kRefTable>), grid, block, 0, s, a);
-  else if (task) hipLaunchKernelGGL((umpc_reactive_steps_kernel<T, kRefRobot>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((umpc_reactive_steps_kernel<T, kRefHandle>), grid, block, 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(e, "umpcBatchReactiveRollout");      // (the clock and the cursors stay where they were)
-  h->advance((double)((long long)K * nsub) * h->prm.dtsim, h->reftab ? K : 0, hist ? K : 0, imp ? K : 0);
-  return 0;
-}
-
-template <typename T>
-static int launch_task_table(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
-                             const void *ref, void *tab, void *stream) {
-  // enough blocks in y to fill the device when B is small, never more than the steps there are (or the grid limit)
-  const unsigned gx = (unsigned)((h->B + 255) / 256);
-  long long gy = (2048 + gx - 1) / gx;
-  if (gy > steps) gy = steps;
-  if (gy > 65535) gy = 65535;
-  hipLaunchKernelGGL(umpc_task_table_kernel<T>, dim3(gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, make_dev_task<T>(h), h->B, steps,
-                     (T)t_ms, task, (const T *)params, (const T *)ref, (T *)tab);
-  return launch_status("umpcBatchTaskTable");
-}
-
-// UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
-static bool score_nt() {
-  static const bool v = [] { const char *e_ = getenv("UMPC_SCORE_NT"); return e_ && atoi(e_) != 0; }();
-  return v;
-}
-
-// ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchScoreBootstrap) ----------------------
-// the recorded tables and the window of a call, as the C ABI passes them
-struct ScoreWindow {
-  const void *state_hist, *out_hist;
-  const int32_t *status_hist;
-  const void *ref_tab, *ref;
-  long long first, count, ref_first;
-  int after;
-};
-
-// the tables as the kernels read them: the pointers moved to the first slice of the call (state: slice first + after)
-template <typename T>
-static umpc::ScoreArgs<T> score_args(const umpc_batch_t *h, const ScoreWindow &w, double tol_p, long long step0, void *score) {
-  const size_t B = (size_t)h->B;
-  umpc::ScoreArgs<T> a;
-  a.state = (const T *)w.state_hist + (size_t)(w.first + (w.after ? 1 : 0)) * 18 * B;
-  a.out = w.out_hist ? (const T *)w.out_hist + (size_t)w.first * 9 * B : nullptr;
-  a.status = w.status_hist ? w.status_hist + (size_t)w.first * B : nullptr;
-  a.reftab = w.ref_tab ? (const T *)w.ref_tab + (size_t)w.ref_first * 9 * B : nullptr;
-  a.ref = (const T *)w.ref;
-  a.score = (T *)score;
-  a.B = h->B; a.count = (int)w.count; a.step0 = step0;
-  a.tol2 = (T)(tol_p * tol_p); a.taulim = (T)h->prm.taulim;
-  return a;
-}
-
-// slices of the step range on a grid (group, slice) of blocks of `waves` wavefronts: enough blocks to fill the device when G
-// is small, never fewer than two steps per wavefront while there are that many (which wavefront or block takes a step does
-// not enter its row)
-static unsigned step_slices(int G, long long count, int waves) {
-  long long gy = (4096 + G - 1) / G;
-  const long long most = (count + 2 * waves - 1) / (2 * waves);
-  if (gy > most) gy = most;
-  if (gy > 65535) gy = 65535;
-  return (unsigned)gy;
-}
-
-// the probabilities travel in the launch arguments
-static umpc::QuantProbs quant_probs(const double *probs, int nq) {
-  umpc::QuantProbs q;
-  for (int j = 0; j < umpc::kQuantMaxProbs; ++j) q.p[j] = j < nq ? probs[j] : 0.0;
-  q.nq = nq;
-  return q;
-}
-
-// A refusal: "<entry point>: <reason>" for umpcLastError, -1 for the caller to return. The checks below return it as it is.
-static int refuse(const char *fn, const char *why) {
-  g_err = std::string(fn) + ": " + why;
-  return -1;
-}
-static int check_one_reference(const char *fn, const ScoreWindow &w) {
-  return (w.ref_tab != nullptr) == (w.ref != nullptr)
-             ? refuse(fn, "exactly one of ref_tab (a reference per step) and ref (a constant reference) must be given") : 0;
-}
-// (umpcBatchScore has a step0 and a count limit of its own next to these)
-static int check_window(const char *fn, const ScoreWindow &w) {
-  if (check_one_reference(fn, w)) return -1;
-  if (w.count < 0 || w.first < 0 || w.ref_first < 0) return refuse(fn, "bad argument (count, first, ref_first >= 0)");
-  return w.count > 0x7fffffffLL ? refuse(fn, "count too large for one call (2^31 - 1 steps at the most)") : 0;
-}
-static int check_tol(const char *fn, double tol_p) {
-  return !(tol_p >= 0) || !(tol_p <= 1.79769313486231570815e308) ? refuse(fn, "bad argument (tol_p must be finite and >= 0)") : 0;
-}
-static int check_groups(const char *fn, int G) { return G < 1 ? refuse(fn, "bad argument (G >= 1)") : 0; }
-// nq in 1 .. UMPC_QUANT_MAX_PROBS and every probability in [0, 1] (a NaN fails both comparisons)
-static int check_probs(const char *fn, const double *probs, int nq) {
-  bool ok = nq >= 1 && nq <= UMPC_QUANT_MAX_PROBS;
-  for (int j = 0; ok && j < nq; ++j) ok = probs[j] >= 0.0 && probs[j] <= 1.0;
-  return ok ? 0 : refuse(fn, "bad argument (1 to 8 probabilities, each in [0, 1])");
-}
-static int check_rows(const char *fn, int num, int den) {
-  return num < 0 || num >= UMPC_SCORE_ROWS || den < -1 || den >= UMPC_SCORE_ROWS ? refuse(fn, "bad argument (num in 0..11, den in -1..11)") : 0;
-}
-
-// the entry points have checked the arguments
-template <typename T>
-static int launch_score(umpc_batch_t *h, const ScoreWindow &w, long long step0, double tol_p, void *score, void *stream) {
-  const umpc::ScoreArgs<T> a = score_args<T>(h, w, tol_p, step0, score);
-  const dim3 grid((unsigned)((h->B + 63) / 64)), block(64, umpc::kScoreSlices);
-  // which tables there are is decided HERE, once: each combination is a kernel of its own whose loop has no branch
-  const int form = (score_nt() ? 8 : 0) | (a.reftab ? 4 : 0) | (a.out ? 2 : 0) | (a.status ? 1 : 0);
-#define UMPC_SCORE_FORM(f)                                                                                              \
-  case f:                                                                                                               \
-    hipLaunchKernelGGL((umpc::umpc_score_kernel<T, ((f) & 8) != 0, ((f) & 4) != 0, ((f) & 2) != 0, ((f) & 1) != 0>), grid, \
-                       block, 0, (hipStream_t)stream, a);                                                               \
-    break;
-  switch (form) {
-    UMPC_SCORE_FORM(0) UMPC_SCORE_FORM(1) UMPC_SCORE_FORM(2) UMPC_SCORE_FORM(3) UMPC_SCORE_FORM(4) UMPC_SCORE_FORM(5)
-    UMPC_SCORE_FORM(6) UMPC_SCORE_FORM(7) UMPC_SCORE_FORM(8) UMPC_SCORE_FORM(9) UMPC_SCORE_FORM(10) UMPC_SCORE_FORM(11)
-    UMPC_SCORE_FORM(12) UMPC_SCORE_FORM(13) UMPC_SCORE_FORM(14) UMPC_SCORE_FORM(15)
-  }
-#undef UMPC_SCORE_FORM
-  return launch_status("umpcBatchScore");
-}
-
-template <typename T>
-static int launch_ensemble(umpc_batch_t *h, const ScoreWindow &w, double tol_p, const int32_t *order, const int32_t *offset, int G,
-                           double *ens, void *stream) {
-  umpc::EnsArgs<T> e;
-  e.t = score_args<T>(h, w, tol_p, 0, nullptr);
-  e.order = order; e.offset = offset; e.ens = ens; e.G = G;
-  const dim3 grid((unsigned)G, step_slices(G, w.count, umpc::kEnsWaves)), block(64, umpc::kEnsWaves);
-  const int form = (w.ref_tab ? 4 : 0) | (w.out_hist ? 2 : 0) | (w.status_hist ? 1 : 0);
-#define UMPC_ENS_FORM(f)                                                                                                \
-  case f:                                                                                                               \
-    hipLaunchKernelGGL((umpc::umpc_ensemble_kernel<T, ((f) & 4) != 0, ((f) & 2) != 0, ((f) & 1) != 0>), grid, block, 0,   \
-                       (hipStream_t)stream, e);                                                                         \
-    break;
-  switch (form) {
-    UMPC_ENS_FORM(0) UMPC_ENS_FORM(1) UMPC_ENS_FORM(2) UMPC_ENS_FORM(3) UMPC_ENS_FORM(4) UMPC_ENS_FORM(5)
-    UMPC_ENS_FORM(6) UMPC_ENS_FORM(7)
-  }
-#undef UMPC_ENS_FORM
-  return launch_status("umpcBatchEnsemble");
-}
-
-// (w carries no status record and there is no tube: the kernels read neither)
-template <typename T>
-static int launch_ens_quantiles(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G, int term,
-                                const double *probs, int nq, double *quant, void *stream) {
-  umpc::QuantArgs<T> e;
-  e.t = score_args<T>(h, w, 0.0, 0, nullptr);
-  e.order = order; e.offset = offset; e.quant = quant; e.G = G;
-  e.q = quant_probs(probs, nq);
-  const dim3 grid((unsigned)G, step_slices(G, w.count, umpc::kQuantWaves)), block(64, umpc::kQuantWaves);
-  const int form = term * 4 + (w.ref_tab ? 2 : 0) + (w.out_hist ? 1 : 0);
-#define UMPC_QUANT_FORM(f)                                                                                              \
-  case f:                                                                                                               \
-    hipLaunchKernelGGL((umpc::umpc_ens_quantile_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, (f) / 4>), grid, block, 0,      \
-                       (hipStream_t)stream, e);                                                                         \
-    hipLaunchKernelGGL((umpc::umpc_ens_quantile_block_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, (f) / 4>), grid, block, 0, \
-                       (hipStream_t)stream, e);                                                                         \
-    break;
-  switch (form) {
-    UMPC_QUANT_FORM(0) UMPC_QUANT_FORM(1) UMPC_QUANT_FORM(2) UMPC_QUANT_FORM(3) UMPC_QUANT_FORM(4) UMPC_QUANT_FORM(5)
-    UMPC_QUANT_FORM(6) UMPC_QUANT_FORM(7) UMPC_QUANT_FORM(9) UMPC_QUANT_FORM(11)       // (term 2 needs out: forms 8 and 10 do not exist)
-  }
-#undef UMPC_QUANT_FORM
-  return launch_status("umpcBatchEnsembleQuantiles");
-}
-
-template <typename T>
-static int launch_score_quantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order, const int32_t *offset,
-                                  int G, const double *probs, int nq, double *quant, void *stream) {
-  umpc::ScoreQuantArgs<T> e;
-  e.score = (const T *)score; e.order = order; e.offset = offset; e.quant = quant;
-  e.B = h->B; e.num = num; e.den = den;
-  e.q = quant_probs(probs, nq);
-  hipLaunchKernelGGL(umpc::umpc_score_quantile_kernel<T>, dim3((unsigned)G), dim3(64, umpc::kQuantWaves), 0, (hipStream_t)stream, e);
-  return launch_status("umpcBatchScoreQuantiles");
-}
-
-// compaction, the replicates of the small and of the large cells, the rows
-template <typename T>
-static int launch_score_bootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den, const int32_t *order,
-                                  const int32_t *offset, int G, int stat, double stat_p, int R, unsigned long long seed,
-                                  const double *probs, int nq, double *boot, double *reps, double *work, void *stream) {
-  umpc::BootCompactArgs<T> c;
-  c.score = (const T *)score; c.other = (const T *)other; c.order = order; c.offset = offset; c.work = work;
-  c.B = h->B; c.num = num; c.den = den;
-  umpc::BootArgs e;
-  e.offset = offset; e.work = work; e.boot = boot; e.reps = reps;
-  e.c0 = seed * 0x9E3779B97F4A7C15ull + umpc::kBootSalt;      // (wraps: the hash is arithmetic modulo 2^64)
-  e.stat_p = stat_p; e.B = h->B; e.R = R;
-  e.q = quant_probs(probs, nq);
-  const hipStream_t s = (hipStream_t)stream;
-  const dim3 block(64, umpc::kBootWaves);
-  if (other) hipLaunchKernelGGL((umpc::umpc_boot_compact_kernel<T, true>), dim3((unsigned)G), dim3(64), 0, s, c);
-  else hipLaunchKernelGGL((umpc::umpc_boot_compact_kernel<T, false>), dim3((unsigned)G), dim3(64), 0, s, c);
-  // a wavefront of the small-cell kernel takes chunks of 64 replicates; a block of the large-cell kernels one replicate
-  const int chunks = (R + 63) / 64;
-  const dim3 grid_a((unsigned)G, (unsigned)((chunks + umpc::kBootWaves - 1) / umpc::kBootWaves));
-  int gy = (4096 + G - 1) / G;
-  if (gy > R) gy = R;
-  const dim3 grid_b((unsigned)G, (unsigned)gy);
-  if (stat == UMPC_BOOT_MEAN) {
-    hipLaunchKernelGGL(umpc::umpc_boot_rep_kernel<umpc::kBootMean>, grid_a, block, 0, s, e);
-    hipLaunchKernelGGL(umpc::umpc_boot_mean_block_kernel, grid_b, block, 0, s, e);
-  } else {
-    hipLaunchKernelGGL(umpc::umpc_boot_rep_kernel<umpc::kBootQuantile>, grid_a, block, 0, s, e);
-    hipLaunchKernelGGL(umpc::umpc_boot_quantile_block_kernel, grid_b, block, 0, s, e);
-  }
-  hipLaunchKernelGGL(umpc::umpc_boot_row_kernel, dim3((unsigned)G), block, 0, s, e);
-  return launch_status("umpcBatchScoreBootstrap");
-}
-
 extern "C" {
 
 const char *umpcLastError(void) { return g_err.c_str(); }
@@ -1253,106 +593,6 @@ int umpcBatchSetImpulses(umpc_batch_t *h, const void *tab, long long steps, long
 }
 long long umpcBatchImpulseCursor(const umpc_batch_t *h) { return h ? h->imp_c.cursor : 0; }
 
-int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
-  if (!h || !score) { g_err = "umpcBatchScoreInit: bad argument"; return -1; }
-  const dim3 grid((unsigned)((h->B + 255) / 256));
-  if (h->dtype == UMPC_F32) hipLaunchKernelGGL(umpc::umpc_score_init_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (float *)score, h->B);
-  else hipLaunchKernelGGL(umpc::umpc_score_init_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (double *)score, h->B);
-  return launch_status("umpcBatchScoreInit");
-}
-int umpcBatchScore(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
-                   const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
-                   long long step0, double tol_p, int after, void *score, void *stream) {
-  const char *fn = "umpcBatchScore";
-  const ScoreWindow w = {state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, after};
-  if (!h) return refuse(fn, "bad argument (no handle)");
-  if (!score || !state_hist) return refuse(fn, "bad argument (score and state_hist must be given)");
-  if (check_one_reference(fn, w)) return -1;
-  if (count < 0 || first < 0 || ref_first < 0 || step0 < 0) return refuse(fn, "bad argument (count, first, ref_first, step0 >= 0)");
-  if (check_tol(fn, tol_p)) return -1;
-  if (count > 0x7fffffffLL - 2 * umpc::kScoreSlices) return refuse(fn, "count too large for one call (2^31 - 17 steps at the most)");
-  // counts and step numbers are scalars of the dtype: fp32 holds integers exactly up to 2^24. Row 0 never exceeds the
-  // number of steps scored, which is at most step0 + count when step0 counts the steps from the start of the run.
-  if (h->dtype == UMPC_F32 && step0 + count > (1LL << 24))
-    return refuse(fn, "step0 + count passes 2^24, the largest step number and count an fp32 score holds exactly (score in fp64, or in parts)");
-  if (count == 0) return 0;
-  return h->dtype == UMPC_F32 ? launch_score<float>(h, w, step0, tol_p, score, stream)
-                              : launch_score<double>(h, w, step0, tol_p, score, stream);
-}
-int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *group, int G, double *gstat, void *stream) {
-  if (!h || !score || !group || !gstat || G < 1) return refuse("umpcBatchScoreGroups", "bad argument (score, group, gstat and G >= 1 must be given)");
-  if (h->dtype == UMPC_F32)
-    hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<float>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float *)score, group, h->B, gstat);
-  else
-    hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<double>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const double *)score, group, h->B, gstat);
-  return launch_status("umpcBatchScoreGroups");
-}
-int umpcBatchGroupIndex(umpc_batch_t *h, const int32_t *group, int G, int32_t *order, int32_t *offset, void *stream) {
-  if (!h || !group || !order || !offset || G < 1) return refuse("umpcBatchGroupIndex", "bad argument (group, order, offset and G >= 1 must be given)");
-  hipLaunchKernelGGL(umpc::umpc_group_index_kernel, dim3((unsigned)G + 1u), dim3(64), 0, (hipStream_t)stream, group, h->B, G, order, offset);
-  return launch_status("umpcBatchGroupIndex");
-}
-int umpcBatchEnsemble(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
-                      const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
-                      double tol_p, int after, const int32_t *order, const int32_t *offset, int G,
-                      double *ens, void *stream) {
-  const char *fn = "umpcBatchEnsemble";
-  const ScoreWindow w = {state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, after};
-  if (!h) return refuse(fn, "bad argument (no handle)");
-  if (!state_hist || !order || !offset || !ens) return refuse(fn, "bad argument (state_hist, order, offset and ens must be given)");
-  if (check_window(fn, w) || check_tol(fn, tol_p) || check_groups(fn, G)) return -1;
-  if (count == 0) return 0;
-  return h->dtype == UMPC_F32 ? launch_ensemble<float>(h, w, tol_p, order, offset, G, ens, stream)
-                              : launch_ensemble<double>(h, w, tol_p, order, offset, G, ens, stream);
-}
-int umpcBatchEnsembleQuantiles(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab,
-                               const void *ref, long long first, long long count, long long ref_first, int after,
-                               const int32_t *order, const int32_t *offset, int G, int term, const double *probs,
-                               int nq, double *quant, void *stream) {
-  const char *fn = "umpcBatchEnsembleQuantiles";
-  const ScoreWindow w = {state_hist, out_hist, nullptr, ref_tab, ref, first, count, ref_first, after};
-  if (!h) return refuse(fn, "bad argument (no handle)");
-  if (!state_hist || !order || !offset || !probs || !quant) return refuse(fn, "bad argument (state_hist, order, offset, probs and quant must be given)");
-  if (check_window(fn, w) || check_groups(fn, G) || check_probs(fn, probs, nq)) return -1;
-  if (term < UMPC_TERM_EP || term > UMPC_TERM_TAU) return refuse(fn, "bad argument (term is UMPC_TERM_EP, UMPC_TERM_ES or UMPC_TERM_TAU)");
-  if (term == UMPC_TERM_TAU && !out_hist) return refuse(fn, "UMPC_TERM_TAU needs out_hist (the moments are read from it)");
-  if (count == 0) return 0;
-  return h->dtype == UMPC_F32 ? launch_ens_quantiles<float>(h, w, order, offset, G, term, probs, nq, quant, stream)
-                              : launch_ens_quantiles<double>(h, w, order, offset, G, term, probs, nq, quant, stream);
-}
-int umpcBatchScoreQuantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order,
-                            const int32_t *offset, int G, const double *probs, int nq, double *quant, void *stream) {
-  const char *fn = "umpcBatchScoreQuantiles";
-  if (!h || !score || !order || !offset || !probs || !quant) return refuse(fn, "bad argument (h, score, order, offset, probs and quant must be given)");
-  if (check_groups(fn, G) || check_probs(fn, probs, nq) || check_rows(fn, num, den)) return -1;
-  return h->dtype == UMPC_F32 ? launch_score_quantiles<float>(h, score, num, den, order, offset, G, probs, nq, quant, stream)
-                              : launch_score_quantiles<double>(h, score, num, den, order, offset, G, probs, nq, quant, stream);
-}
-int umpcBatchScoreBootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den,
-                            const int32_t *order, const int32_t *offset, int G, int stat, double stat_p,
-                            int R, unsigned long long seed, const double *probs, int nq,
-                            double *boot, double *reps, double *work, void *stream) {
-  const char *fn = "umpcBatchScoreBootstrap";
-  if (!score || !order || !offset || !probs) return refuse(fn, "bad argument (score, order, offset and probs must be given)");
-  if (!boot || !reps || !work) return refuse(fn, "bad argument (boot [G][5 + nq], reps [G][R] and work [B + G] must be given)");
-  if (check_groups(fn, G)) return -1;
-  if (R < 2 || R > UMPC_BOOT_MAX_REPS) return refuse(fn, "bad argument (2 <= R <= 1048576 replicates)");
-  if (stat != UMPC_BOOT_MEAN && stat != UMPC_BOOT_QUANTILE) return refuse(fn, "bad argument (stat is UMPC_BOOT_MEAN or UMPC_BOOT_QUANTILE)");
-  if (!(stat_p >= 0.0 && stat_p <= 1.0)) return refuse(fn, "bad argument (stat_p in [0, 1])");
-  if (check_probs(fn, probs, nq) || check_rows(fn, num, den)) return -1;
-  // (the handle last: every other refusal can be met without one; nothing above reads it)
-  if (!h) return refuse(fn, "bad argument (no handle)");
-  return h->dtype == UMPC_F32
-             ? launch_score_bootstrap<float>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream)
-             : launch_score_bootstrap<double>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream);
-}
-
-int umpcBatchTaskTable(umpc_batch_t *h, long long steps, double t_ms, const int32_t *task, const void *params,
-                       const void *ref, void *tab, void *stream) {
-  if (!h || steps < 1 || !ref || !tab) { g_err = "umpcBatchTaskTable: bad argument"; return -1; }
-  return h->dtype == UMPC_F32 ? launch_task_table<float>(h, steps, t_ms, task, params, ref, tab, stream)
-                              : launch_task_table<double>(h, steps, t_ms, task, params, ref, tab, stream);
-}
 int umpcBatchSetWeights(umpc_batch_t *h, const void *weights) {
   if (!h) return -1;
   if (weights) {
@@ -1402,83 +642,12 @@ int umpcBatchRollout(umpc_batch_t *h, int K, void *state, void *ctrl, const void
                               : launch_rollout<double>(h, K, h->prm.nsub, io, stream);
 }
 
-int umpcBatchTaskReference(umpc_batch_t *h, double t_ms, const void *ref, void *out, void *stream) {
-  if (!h || !ref || !out) { g_err = "umpcBatchTaskReference: bad argument"; return -1; }
-  if (h->reftab) { g_err = "umpcBatchTaskReference: a reference trajectory is set (its slices ARE the reference)"; return -1; }
-  const int grid = (h->B + 255) / 256;
-  if (h->dtype == UMPC_F32)
-    hipLaunchKernelGGL(umpc_taskref_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, make_dev_task<float>(h), h->B,
-                       (float)t_ms, (const float *)ref, (float *)out);
-  else
-    hipLaunchKernelGGL(umpc_taskref_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, make_dev_task<double>(h), h->B,
-                       t_ms, (const double *)ref, (double *)out);
-  return launch_status("umpcBatchTaskReference");
-}
-
-int umpcBatchReactive(umpc_batch_t *h, int nsteps, int every, void *state, const void *ref, const void *gains,
-                      const void *Ib, const void *gain, void *out, void *stats, void *stream) {
-  if (!h || nsteps < 0 || every < 1 || !state || !ref) { g_err = "umpcBatchReactive: bad argument"; return -1; }
-  if (h->reftab) { g_err = "umpcBatchReactive: a reference trajectory is set (it has one slice per MPC step, not per substep)"; return -1; }
-  if (h->imptab) {      // (set only on handles with nsub >= 1)
-    const int nsub = h->prm.nsub;
-    if (nsteps % nsub != 0) {
-      g_err = "umpcBatchReactive: impulses are set (one slice per nsub = " + std::to_string(nsub) + " substeps): nsteps must be a multiple of nsub";
-      return -1;
-    }
-    if (!h->imp_c.fits("umpcBatchReactive", "impulse table", "", nsteps / nsub)) return -1;
-  }
-  return h->dtype == UMPC_F32 ? launch_reactive<float>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream)
-                              : launch_reactive<double>(h, nsteps, every, state, ref, gains, Ib, gain, out, stats, stream);
-}
-
-int umpcBatchReactiveRollout(umpc_batch_t *h, int K, int every, void *state, const void *ref, const void *gains,
-                             const int32_t *task, const void *task_params, const void *Ib, const void *thrust_gain, void *out,
-                             void *stats, void *stream) {
-  const char *const me = "umpcBatchReactiveRollout";
-  if (!h) { g_err = std::string(me) + ": bad argument (no handle)"; return -1; }
-  const int nsub = h->prm.nsub;
-  if (K < 1 || every < 1 || !state) { g_err = std::string(me) + ": bad argument (K >= 1, every >= 1, state must be given)"; return -1; }
-  if (nsub == 0) { g_err = std::string(me) + ": the handle has no plant (nsub = 0): there is no closed-loop step to run"; return -1; }
-  if (nsub % every != 0) {
-    g_err = std::string(me) + ": every = " + std::to_string(every) + " does not divide nsub = " + std::to_string(nsub) +
-            " (a run cut into several launches must fire at the same substeps)";
-    return -1;
-  }
-  if ((long long)K * nsub > 0x7fffffffLL) { g_err = std::string(me) + ": K * nsub passes 2^31 - 1 substeps"; return -1; }
-  if (!ref && !h->reftab) { g_err = std::string(me) + ": bad argument (ref must be given when no reference trajectory is set)"; return -1; }
-  if (task_params && !task) { g_err = std::string(me) + ": task_params without task"; return -1; }
-  if (task && h->reftab) {
-    g_err = std::string(me) + ": per-robot tasks and a reference trajectory (umpcBatchSetRefTrajectory) exclude each other";
-    return -1;
-  }
-  if (h->reftab && !h->ref_c.fits(me, "reference trajectory", "K ", K)) return -1;
-  if (h->hist_on(K, nsub) && !h->hist_c.fits(me, "step history", "K ", K)) return -1;
-  if (h->imp_on(K, nsub) && !h->imp_c.fits(me, "impulse table", "K ", K)) return -1;
-  return h->dtype == UMPC_F32
-             ? launch_reactive_steps<float>(h, K, every, state, ref, gains, task, task_params, Ib, thrust_gain, out, stats, stream)
-             : launch_reactive_steps<double>(h, K, every, state, ref, gains, task, task_params, Ib, thrust_gain, out, stats, stream);
-}
-
 int umpcBatchUpdate(umpc_batch_t *h, const void *state, void *ctrl, const void *ref, const void *actualT0,
                     const void *Ib, void *out, int32_t *status, void *info, void *stream) {
   // one step without a plant (nsub = 0): the state is only read, there is no thrust gain and there are no statistics
   const RolloutArrays io = {.state = (void *)state, .ctrl = ctrl, .ref = ref, .actualT0 = actualT0, .Ib = Ib,
                             .out = out, .status = status, .info = info};
   return h->dtype == UMPC_F32 ? launch_rollout<float>(h, 1, 0, io, stream) : launch_rollout<double>(h, 1, 0, io, stream);
-}
-
-int umpcBatchPlant(umpc_batch_t *h, int nsub, void *state, const void *u, const void *Ib, const void *gain,
-                   void *stream) {
-  const int grid = (h->B + kBlock - 1) / kBlock;
-  if (h->dtype == UMPC_F32)
-    hipLaunchKernelGGL(umpc_plant_kernel<float>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
-                       make_dev<float>(h->prm), h->B, nsub, (float *)state, (const float *)u, (const float *)Ib,
-                       (const float *)gain);
-  else
-    hipLaunchKernelGGL(umpc_plant_kernel<double>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream,
-                       make_dev<double>(h->prm), h->B, nsub, (double *)state, (const double *)u, (const double *)Ib,
-                       (const double *)gain);
-  return launch_status("umpcBatchPlant");
 }
 
 static int assemble_launch(umpc_batch_t *h, const void *state, const void *ctrl, const void *ref, const void *Ib,
@@ -1836,189 +1005,6 @@ void umpcRelease(UprightMPC_t *up) {
   std::lock_guard<std::mutex> lk(g_mu);
   release_locked(pod_id(up));
   memset(up->smin, 0, 2 * sizeof(float));
-}
-
-// ---------------------------------------------------------------------------
-// Part 3: wrench-linearisation step, funapprox.c
-// ---------------------------------------------------------------------------
-}  // extern "C"
-
-namespace {
-using umpc::WLDev;
-
-// one lane = one robot: w0 = w(u0), A1 = dw/du(u0), one clipped gradient step (funapprox.c:118-165)
-template <typename T>
-__global__ __launch_bounds__(256) void umpc_wl_kernel(WLDev p, int B_, T *u, const T *h0, const T *pd, T *w0out) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B_) return;
-  const size_t B = (size_t)B_;
-  T u0[4], h[6], d[6], w[6];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) u0[j] = u[(size_t)j * B + b];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { h[i] = h0[(size_t)i * B + b]; d[i] = pd[(size_t)i * B + b]; }
-  umpc::wl_step(p, u0, h, d, w);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) w0out[(size_t)i * B + b] = w[i];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) u[(size_t)j * B + b] = u0[j];
-}
-
-// a19 / a20 vector fields: nsub == 0 evaluates ydot (ca6 also appends wrench and bias h), nsub > 0
-// advances y by nsub RK4 steps of dt with u held
-template <typename T, int MODEL>
-__global__ __launch_bounds__(256) void umpc_model_kernel(int B_, int nsub, T dt, T *y, const T *u, T *aux) {
-  constexpr int NYV = MODEL == 0 ? 18 : 12, NUV = MODEL == 0 ? 6 : 4;
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B_) return;
-  const size_t B = (size_t)B_;
-  T yv[NYV], uv[NUV];
-#pragma unroll
-  for (int i = 0; i < NYV; ++i) yv[i] = y[(size_t)i * B + b];
-#pragma unroll
-  for (int i = 0; i < NUV; ++i) uv[i] = u[(size_t)i * B + b];
-  auto vf = [&](const T (&ys)[NYV], T (&k)[NYV]) {
-    if constexpr (MODEL == 0) {
-      T w[6], h[6];
-      umpc::ca6_vf(ys, uv, k, w, h);
-    } else {
-      umpc::tsd_vf(ys, uv, k);
-    }
-  };
-  if (nsub == 0) {
-    T k[NYV];
-    vf(yv, k);
-#pragma unroll
-    for (int i = 0; i < NYV; ++i) aux[(size_t)i * B + b] = k[i];
-    if constexpr (MODEL == 0) {
-      T w[6], h[6], kk[NYV];
-      umpc::ca6_vf(yv, uv, kk, w, h);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) { aux[(size_t)(18 + i) * B + b] = w[i]; aux[(size_t)(24 + i) * B + b] = h[i]; }
-    }
-    return;
-  }
-#pragma nounroll
-  for (int s = 0; s < nsub; ++s) umpc::rk4_step<T, NYV>(yv, dt, vf);
-#pragma unroll
-  for (int i = 0; i < NYV; ++i) y[(size_t)i * B + b] = yv[i];
-}
-
-WLDev make_wl(const WLCon_t *wl) {
-  WLDev d;
-  for (int j = 0; j < 4; ++j) { d.umin[j] = wl->umin[j]; d.umax[j] = wl->umax[j]; d.dumax[j] = wl->dumax[j]; }
-  for (int i = 0; i < 6; ++i) {
-    d.Qw[i] = wl->Qw[i + 6 * i];
-    d.a0[i] = wl->fa[i].a0;
-    for (int j = 0; j < 4; ++j) d.a1[i][j] = wl->fa[i].a1[j];
-    for (int j = 0; j < 16; ++j) d.A2[i][j] = wl->fa[i].A2[j];
-    d.Md[i] = 0.f;
-  }
-  return d;
-}
-float *g_wl_dev = nullptr;  // 4 + 6 + 6 + 6 floats for the B = 1 entry point
-}  // namespace
-
-extern "C" {
-
-int umpcBatchWLUpdate(const WLCon_t *wl, int B, int dtype, void *u, const void *h0, const void *pdotdes, void *w0,
-                      void *stream) {
-  if (!wl || B <= 0 || !u || !h0 || !pdotdes || !w0) { g_err = "umpcBatchWLUpdate: bad argument"; return -1; }
-  const WLDev d = make_wl(wl);
-  const int grid = (B + 255) / 256;
-  if (dtype == UMPC_F32)
-    hipLaunchKernelGGL(umpc_wl_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, d, B, (float *)u,
-                       (const float *)h0, (const float *)pdotdes, (float *)w0);
-  else
-    hipLaunchKernelGGL(umpc_wl_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, d, B, (double *)u,
-                       (const double *)h0, (const double *)pdotdes, (double *)w0);
-  return launch_status("umpcBatchWLUpdate");
-}
-
-int umpcBatchSetWL(umpc_batch_t *h, const WLCon_t *wl, const double Mdiag[6], void *u4, void *w0) {
-  if (!h) return -1;
-  if (!wl) {
-    h->wlu = h->wlw = nullptr;
-    if (h->wl) { (void)hipDeviceSynchronize(); (void)hipFree(h->wl); h->wl = nullptr; }
-    return 0;
-  }
-  if (!Mdiag || !u4 || !(Mdiag[2] > 0)) { g_err = "umpcBatchSetWL: bad argument"; return -1; }
-  WLDev d = make_wl(wl);
-  for (int i = 0; i < 6; ++i) d.Md[i] = (float)Mdiag[i];
-  h->wl_md2 = d.Md[2];
-  hipError_t e = hipSuccess;
-  if (!h->wl) e = hipMalloc((void **)&h->wl, sizeof(WLDev));
-  if (e == hipSuccess) e = hipMemcpy(h->wl, &d, sizeof(WLDev), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail(e, "umpcBatchSetWL");
-  h->wlu = u4; h->wlw = w0;
-  return 0;
-}
-
-int umpcBatchModel(int model, int B, int dtype, int nsub, double dt, void *y, const void *u, void *aux, void *stream) {
-  if ((model != UMPC_MODEL_CA6 && model != UMPC_MODEL_TSD) || B <= 0 || nsub < 0 || !y || !u || (nsub == 0 && !aux)) {
-    g_err = "umpcBatchModel: bad argument";
-    return -1;
-  }
-  const dim3 grid((B + 255) / 256), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == UMPC_F32) {
-    if (model == UMPC_MODEL_CA6)
-      hipLaunchKernelGGL((umpc_model_kernel<float, 0>), grid, blk, 0, s, B, nsub, (float)dt, (float *)y, (const float *)u, (float *)aux);
-    else
-      hipLaunchKernelGGL((umpc_model_kernel<float, 1>), grid, blk, 0, s, B, nsub, (float)dt, (float *)y, (const float *)u, (float *)aux);
-  } else {
-    if (model == UMPC_MODEL_CA6)
-      hipLaunchKernelGGL((umpc_model_kernel<double, 0>), grid, blk, 0, s, B, nsub, dt, (double *)y, (const double *)u, (double *)aux);
-    else
-      hipLaunchKernelGGL((umpc_model_kernel<double, 1>), grid, blk, 0, s, B, nsub, dt, (double *)y, (const double *)u, (double *)aux);
-  }
-  return launch_status("umpcBatchModel");
-}
-
-void wlConInit(WLCon_t *wl, const float u0[4], const float umin[4], const float umax[4], const float dumax[4],
-               const float Qw[6], float controlRate, const float popts[90]) {
-  // funapprox.c:102-116 + funApproxInit :35-51 (host-side unpacking; the struct carries all state)
-  memset(wl, 0, sizeof(*wl));
-  for (int i = 0; i < 4; ++i) {
-    wl->u0[i] = u0[i]; wl->umin[i] = umin[i]; wl->umax[i] = umax[i];
-    wl->dumax[i] = dumax[i] / controlRate;
-  }
-  for (int i = 0; i < 6; ++i) {
-    const float *p = &popts[15 * i];
-    wl->fa[i].k = NDELU;
-    wl->fa[i].a0 = p[0];
-    memcpy(wl->fa[i].a1, &p[1], 4 * sizeof(float));
-    int kk = 0;
-    for (int r = 0; r < 4; ++r)
-      for (int c = r; c < 4; ++c) wl->fa[i].A2[r + 4 * c] = wl->fa[i].A2[c + 4 * r] = p[5 + kk++];
-    wl->Qw[i + 6 * i] = Qw[i];
-  }
-}
-
-void wlConUpdate(WLCon_t *wl, float u1[4], float w0[6], const float h0[6], const float pdotdes[6]) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  if (!g_wl_dev && hipMalloc((void **)&g_wl_dev, 22 * sizeof(float)) != hipSuccess) {
-    fprintf(stderr, "wlConUpdate: no GPU (no CPU path exists)\n");
-    return;
-  }
-  float hin[16];
-  memcpy(hin, wl->u0, 16); memcpy(hin + 4, h0, 24); memcpy(hin + 10, pdotdes, 24);
-  (void)hipMemcpy(g_wl_dev, hin, sizeof(hin), hipMemcpyHostToDevice);
-  if (umpcBatchWLUpdate(wl, 1, UMPC_F32, g_wl_dev, g_wl_dev + 4, g_wl_dev + 10, g_wl_dev + 16, nullptr)) return;
-  float hout[22];
-  if (hipMemcpy(hout, g_wl_dev, sizeof(hout), hipMemcpyDeviceToHost) != hipSuccess) return;
-  memcpy(wl->u0, hout, 16); memcpy(u1, hout, 16); memcpy(w0, hout + 16, 24);
-}
-
-namespace { WLCon_t g_wl; int g_wl_inited = 0; }
-void wlconS(float u1[4], float w0[6], const float u0init[4], const float umin[4], const float umax[4],
-            const float dumax[4], const float Qw[6], float controlRate, const float popts[90], const float h0[6],
-            const float pdotdes[6]) {
-  if (!g_wl_inited) {  // funapprox.c:172-175
-    wlConInit(&g_wl, u0init, umin, umax, dumax, Qw, controlRate, popts);
-    g_wl_inited = 1;
-  }
-  wlConUpdate(&g_wl, u1, w0, h0, pdotdes);
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 //      d(rotvec)/dt = omega and omegadot = R' omegadot_b (sic); m = 0.5, Ib = diag(5e-4,5e-4,1e-3), ycp = 0.5,
 //      g = 9.81.
 #pragma once
-#include "umpc_step.h"
+#include "umpc_scalar.h"
 
 namespace umpc {
 

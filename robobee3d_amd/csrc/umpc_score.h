@@ -33,7 +33,7 @@
 
 #include <cstdint>
 
-#include "umpc_step.h"
+#include "umpc_scalar.h"
 
 namespace umpc {
 

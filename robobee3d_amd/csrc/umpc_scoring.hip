@@ -1,0 +1,299 @@
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchScoreBootstrap) and their
+// host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h and umpc_bootstrap.h:
+// nothing here reads the step path or a generated header.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdlib>
+
+#include "umpc_handle.h"
+#include "umpc_score.h"    // scoring of recorded rollouts (umpcBatchScore / umpcBatchScoreGroups)
+#include "umpc_ensemble.h" // per-step, per-group statistics of recorded rollouts (umpcBatchEnsemble)
+#include "umpc_quantile.h" // per-step, per-group order statistics (umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles)
+#include "umpc_bootstrap.h" // bootstrap intervals of a per-group cost table (umpcBatchScoreBootstrap)
+
+// UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
+static bool score_nt() {
+  static const bool v = [] { const char *e_ = getenv("UMPC_SCORE_NT"); return e_ && atoi(e_) != 0; }();
+  return v;
+}
+
+// ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchScoreBootstrap) ----------------------
+// the recorded tables and the window of a call, as the C ABI passes them
+struct ScoreWindow {
+  const void *state_hist, *out_hist;
+  const int32_t *status_hist;
+  const void *ref_tab, *ref;
+  long long first, count, ref_first;
+  int after;
+};
+
+// the tables as the kernels read them: the pointers moved to the first slice of the call (state: slice first + after)
+template <typename T>
+static umpc::ScoreArgs<T> score_args(const umpc_batch_t *h, const ScoreWindow &w, double tol_p, long long step0, void *score) {
+  const size_t B = (size_t)h->B;
+  umpc::ScoreArgs<T> a;
+  a.state = (const T *)w.state_hist + (size_t)(w.first + (w.after ? 1 : 0)) * 18 * B;
+  a.out = w.out_hist ? (const T *)w.out_hist + (size_t)w.first * 9 * B : nullptr;
+  a.status = w.status_hist ? w.status_hist + (size_t)w.first * B : nullptr;
+  a.reftab = w.ref_tab ? (const T *)w.ref_tab + (size_t)w.ref_first * 9 * B : nullptr;
+  a.ref = (const T *)w.ref;
+  a.score = (T *)score;
+  a.B = h->B; a.count = (int)w.count; a.step0 = step0;
+  a.tol2 = (T)(tol_p * tol_p); a.taulim = (T)h->prm.taulim;
+  return a;
+}
+
+// slices of the step range on a grid (group, slice) of blocks of `waves` wavefronts: enough blocks to fill the device when G
+// is small, never fewer than two steps per wavefront while there are that many (which wavefront or block takes a step does
+// not enter its row)
+static unsigned step_slices(int G, long long count, int waves) {
+  long long gy = (4096 + G - 1) / G;
+  const long long most = (count + 2 * waves - 1) / (2 * waves);
+  if (gy > most) gy = most;
+  if (gy > 65535) gy = 65535;
+  return (unsigned)gy;
+}
+
+// the probabilities travel in the launch arguments
+static umpc::QuantProbs quant_probs(const double *probs, int nq) {
+  umpc::QuantProbs q;
+  for (int j = 0; j < umpc::kQuantMaxProbs; ++j) q.p[j] = j < nq ? probs[j] : 0.0;
+  q.nq = nq;
+  return q;
+}
+
+// The checks below return a refusal (refuse, umpc_handle.h) as it is.
+static int check_one_reference(const char *fn, const ScoreWindow &w) {
+  return (w.ref_tab != nullptr) == (w.ref != nullptr)
+             ? refuse(fn, "exactly one of ref_tab (a reference per step) and ref (a constant reference) must be given") : 0;
+}
+// (umpcBatchScore has a step0 and a count limit of its own next to these)
+static int check_window(const char *fn, const ScoreWindow &w) {
+  if (check_one_reference(fn, w)) return -1;
+  if (w.count < 0 || w.first < 0 || w.ref_first < 0) return refuse(fn, "bad argument (count, first, ref_first >= 0)");
+  return w.count > 0x7fffffffLL ? refuse(fn, "count too large for one call (2^31 - 1 steps at the most)") : 0;
+}
+static int check_tol(const char *fn, double tol_p) {
+  return !(tol_p >= 0) || !(tol_p <= 1.79769313486231570815e308) ? refuse(fn, "bad argument (tol_p must be finite and >= 0)") : 0;
+}
+static int check_groups(const char *fn, int G) { return G < 1 ? refuse(fn, "bad argument (G >= 1)") : 0; }
+// nq in 1 .. UMPC_QUANT_MAX_PROBS and every probability in [0, 1] (a NaN fails both comparisons)
+static int check_probs(const char *fn, const double *probs, int nq) {
+  bool ok = nq >= 1 && nq <= UMPC_QUANT_MAX_PROBS;
+  for (int j = 0; ok && j < nq; ++j) ok = probs[j] >= 0.0 && probs[j] <= 1.0;
+  return ok ? 0 : refuse(fn, "bad argument (1 to 8 probabilities, each in [0, 1])");
+}
+static int check_rows(const char *fn, int num, int den) {
+  return num < 0 || num >= UMPC_SCORE_ROWS || den < -1 || den >= UMPC_SCORE_ROWS ? refuse(fn, "bad argument (num in 0..11, den in -1..11)") : 0;
+}
+
+// the entry points have checked the arguments
+template <typename T>
+static int launch_score(umpc_batch_t *h, const ScoreWindow &w, long long step0, double tol_p, void *score, void *stream) {
+  const umpc::ScoreArgs<T> a = score_args<T>(h, w, tol_p, step0, score);
+  const dim3 grid((unsigned)((h->B + 63) / 64)), block(64, umpc::kScoreSlices);
+  // which tables there are is decided HERE, once: each combination is a kernel of its own whose loop has no branch
+  const int form = (score_nt() ? 8 : 0) | (a.reftab ? 4 : 0) | (a.out ? 2 : 0) | (a.status ? 1 : 0);
+#define UMPC_SCORE_FORM(f)                                                                                              \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_score_kernel<T, ((f) & 8) != 0, ((f) & 4) != 0, ((f) & 2) != 0, ((f) & 1) != 0>), grid, \
+                       block, 0, (hipStream_t)stream, a);                                                               \
+    break;
+  switch (form) {
+    UMPC_SCORE_FORM(0) UMPC_SCORE_FORM(1) UMPC_SCORE_FORM(2) UMPC_SCORE_FORM(3) UMPC_SCORE_FORM(4) UMPC_SCORE_FORM(5)
+    UMPC_SCORE_FORM(6) UMPC_SCORE_FORM(7) UMPC_SCORE_FORM(8) UMPC_SCORE_FORM(9) UMPC_SCORE_FORM(10) UMPC_SCORE_FORM(11)
+    UMPC_SCORE_FORM(12) UMPC_SCORE_FORM(13) UMPC_SCORE_FORM(14) UMPC_SCORE_FORM(15)
+  }
+#undef UMPC_SCORE_FORM
+  return launch_status("umpcBatchScore");
+}
+
+template <typename T>
+static int launch_ensemble(umpc_batch_t *h, const ScoreWindow &w, double tol_p, const int32_t *order, const int32_t *offset, int G,
+                           double *ens, void *stream) {
+  umpc::EnsArgs<T> e;
+  e.t = score_args<T>(h, w, tol_p, 0, nullptr);
+  e.order = order; e.offset = offset; e.ens = ens; e.G = G;
+  const dim3 grid((unsigned)G, step_slices(G, w.count, umpc::kEnsWaves)), block(64, umpc::kEnsWaves);
+  const int form = (w.ref_tab ? 4 : 0) | (w.out_hist ? 2 : 0) | (w.status_hist ? 1 : 0);
+#define UMPC_ENS_FORM(f)                                                                                                \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_ensemble_kernel<T, ((f) & 4) != 0, ((f) & 2) != 0, ((f) & 1) != 0>), grid, block, 0,   \
+                       (hipStream_t)stream, e);                                                                         \
+    break;
+  switch (form) {
+    UMPC_ENS_FORM(0) UMPC_ENS_FORM(1) UMPC_ENS_FORM(2) UMPC_ENS_FORM(3) UMPC_ENS_FORM(4) UMPC_ENS_FORM(5)
+    UMPC_ENS_FORM(6) UMPC_ENS_FORM(7)
+  }
+#undef UMPC_ENS_FORM
+  return launch_status("umpcBatchEnsemble");
+}
+
+// (w carries no status record and there is no tube: the kernels read neither)
+template <typename T>
+static int launch_ens_quantiles(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G, int term,
+                                const double *probs, int nq, double *quant, void *stream) {
+  umpc::QuantArgs<T> e;
+  e.t = score_args<T>(h, w, 0.0, 0, nullptr);
+  e.order = order; e.offset = offset; e.quant = quant; e.G = G;
+  e.q = quant_probs(probs, nq);
+  const dim3 grid((unsigned)G, step_slices(G, w.count, umpc::kQuantWaves)), block(64, umpc::kQuantWaves);
+  const int form = term * 4 + (w.ref_tab ? 2 : 0) + (w.out_hist ? 1 : 0);
+#define UMPC_QUANT_FORM(f)                                                                                              \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_ens_quantile_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, (f) / 4>), grid, block, 0,      \
+                       (hipStream_t)stream, e);                                                                         \
+    hipLaunchKernelGGL((umpc::umpc_ens_quantile_block_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, (f) / 4>), grid, block, 0, \
+                       (hipStream_t)stream, e);                                                                         \
+    break;
+  switch (form) {
+    UMPC_QUANT_FORM(0) UMPC_QUANT_FORM(1) UMPC_QUANT_FORM(2) UMPC_QUANT_FORM(3) UMPC_QUANT_FORM(4) UMPC_QUANT_FORM(5)
+    UMPC_QUANT_FORM(6) UMPC_QUANT_FORM(7) UMPC_QUANT_FORM(9) UMPC_QUANT_FORM(11)       // (term 2 needs out: forms 8 and 10 do not exist)
+  }
+#undef UMPC_QUANT_FORM
+  return launch_status("umpcBatchEnsembleQuantiles");
+}
+
+template <typename T>
+static int launch_score_quantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order, const int32_t *offset,
+                                  int G, const double *probs, int nq, double *quant, void *stream) {
+  umpc::ScoreQuantArgs<T> e;
+  e.score = (const T *)score; e.order = order; e.offset = offset; e.quant = quant;
+  e.B = h->B; e.num = num; e.den = den;
+  e.q = quant_probs(probs, nq);
+  hipLaunchKernelGGL(umpc::umpc_score_quantile_kernel<T>, dim3((unsigned)G), dim3(64, umpc::kQuantWaves), 0, (hipStream_t)stream, e);
+  return launch_status("umpcBatchScoreQuantiles");
+}
+
+// compaction, the replicates of the small and of the large cells, the rows
+template <typename T>
+static int launch_score_bootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den, const int32_t *order,
+                                  const int32_t *offset, int G, int stat, double stat_p, int R, unsigned long long seed,
+                                  const double *probs, int nq, double *boot, double *reps, double *work, void *stream) {
+  umpc::BootCompactArgs<T> c;
+  c.score = (const T *)score; c.other = (const T *)other; c.order = order; c.offset = offset; c.work = work;
+  c.B = h->B; c.num = num; c.den = den;
+  umpc::BootArgs e;
+  e.offset = offset; e.work = work; e.boot = boot; e.reps = reps;
+  e.c0 = seed * 0x9E3779B97F4A7C15ull + umpc::kBootSalt;      // (wraps: the hash is arithmetic modulo 2^64)
+  e.stat_p = stat_p; e.B = h->B; e.R = R;
+  e.q = quant_probs(probs, nq);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 block(64, umpc::kBootWaves);
+  if (other) hipLaunchKernelGGL((umpc::umpc_boot_compact_kernel<T, true>), dim3((unsigned)G), dim3(64), 0, s, c);
+  else hipLaunchKernelGGL((umpc::umpc_boot_compact_kernel<T, false>), dim3((unsigned)G), dim3(64), 0, s, c);
+  // a wavefront of the small-cell kernel takes chunks of 64 replicates; a block of the large-cell kernels one replicate
+  const int chunks = (R + 63) / 64;
+  const dim3 grid_a((unsigned)G, (unsigned)((chunks + umpc::kBootWaves - 1) / umpc::kBootWaves));
+  int gy = (4096 + G - 1) / G;
+  if (gy > R) gy = R;
+  const dim3 grid_b((unsigned)G, (unsigned)gy);
+  if (stat == UMPC_BOOT_MEAN) {
+    hipLaunchKernelGGL(umpc::umpc_boot_rep_kernel<umpc::kBootMean>, grid_a, block, 0, s, e);
+    hipLaunchKernelGGL(umpc::umpc_boot_mean_block_kernel, grid_b, block, 0, s, e);
+  } else {
+    hipLaunchKernelGGL(umpc::umpc_boot_rep_kernel<umpc::kBootQuantile>, grid_a, block, 0, s, e);
+    hipLaunchKernelGGL(umpc::umpc_boot_quantile_block_kernel, grid_b, block, 0, s, e);
+  }
+  hipLaunchKernelGGL(umpc::umpc_boot_row_kernel, dim3((unsigned)G), block, 0, s, e);
+  return launch_status("umpcBatchScoreBootstrap");
+}
+
+extern "C" {
+
+int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
+  if (!h || !score) { umpc_set_error("umpcBatchScoreInit: bad argument"); return -1; }
+  const dim3 grid((unsigned)((h->B + 255) / 256));
+  if (h->dtype == UMPC_F32) hipLaunchKernelGGL(umpc::umpc_score_init_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (float *)score, h->B);
+  else hipLaunchKernelGGL(umpc::umpc_score_init_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (double *)score, h->B);
+  return launch_status("umpcBatchScoreInit");
+}
+int umpcBatchScore(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                   const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                   long long step0, double tol_p, int after, void *score, void *stream) {
+  const char *fn = "umpcBatchScore";
+  const ScoreWindow w = {state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!score || !state_hist) return refuse(fn, "bad argument (score and state_hist must be given)");
+  if (check_one_reference(fn, w)) return -1;
+  if (count < 0 || first < 0 || ref_first < 0 || step0 < 0) return refuse(fn, "bad argument (count, first, ref_first, step0 >= 0)");
+  if (check_tol(fn, tol_p)) return -1;
+  if (count > 0x7fffffffLL - 2 * umpc::kScoreSlices) return refuse(fn, "count too large for one call (2^31 - 17 steps at the most)");
+  // counts and step numbers are scalars of the dtype: fp32 holds integers exactly up to 2^24. Row 0 never exceeds the
+  // number of steps scored, which is at most step0 + count when step0 counts the steps from the start of the run.
+  if (h->dtype == UMPC_F32 && step0 + count > (1LL << 24))
+    return refuse(fn, "step0 + count passes 2^24, the largest step number and count an fp32 score holds exactly (score in fp64, or in parts)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_score<float>(h, w, step0, tol_p, score, stream)
+                              : launch_score<double>(h, w, step0, tol_p, score, stream);
+}
+int umpcBatchScoreGroups(umpc_batch_t *h, const void *score, const int32_t *group, int G, double *gstat, void *stream) {
+  if (!h || !score || !group || !gstat || G < 1) return refuse("umpcBatchScoreGroups", "bad argument (score, group, gstat and G >= 1 must be given)");
+  if (h->dtype == UMPC_F32)
+    hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<float>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const float *)score, group, h->B, gstat);
+  else
+    hipLaunchKernelGGL(umpc::umpc_score_groups_kernel<double>, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, (const double *)score, group, h->B, gstat);
+  return launch_status("umpcBatchScoreGroups");
+}
+int umpcBatchGroupIndex(umpc_batch_t *h, const int32_t *group, int G, int32_t *order, int32_t *offset, void *stream) {
+  if (!h || !group || !order || !offset || G < 1) return refuse("umpcBatchGroupIndex", "bad argument (group, order, offset and G >= 1 must be given)");
+  hipLaunchKernelGGL(umpc::umpc_group_index_kernel, dim3((unsigned)G + 1u), dim3(64), 0, (hipStream_t)stream, group, h->B, G, order, offset);
+  return launch_status("umpcBatchGroupIndex");
+}
+int umpcBatchEnsemble(umpc_batch_t *h, const void *state_hist, const void *out_hist, const int32_t *status_hist,
+                      const void *ref_tab, const void *ref, long long first, long long count, long long ref_first,
+                      double tol_p, int after, const int32_t *order, const int32_t *offset, int G,
+                      double *ens, void *stream) {
+  const char *fn = "umpcBatchEnsemble";
+  const ScoreWindow w = {state_hist, out_hist, status_hist, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !ens) return refuse(fn, "bad argument (state_hist, order, offset and ens must be given)");
+  if (check_window(fn, w) || check_tol(fn, tol_p) || check_groups(fn, G)) return -1;
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_ensemble<float>(h, w, tol_p, order, offset, G, ens, stream)
+                              : launch_ensemble<double>(h, w, tol_p, order, offset, G, ens, stream);
+}
+int umpcBatchEnsembleQuantiles(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab,
+                               const void *ref, long long first, long long count, long long ref_first, int after,
+                               const int32_t *order, const int32_t *offset, int G, int term, const double *probs,
+                               int nq, double *quant, void *stream) {
+  const char *fn = "umpcBatchEnsembleQuantiles";
+  const ScoreWindow w = {state_hist, out_hist, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !probs || !quant) return refuse(fn, "bad argument (state_hist, order, offset, probs and quant must be given)");
+  if (check_window(fn, w) || check_groups(fn, G) || check_probs(fn, probs, nq)) return -1;
+  if (term < UMPC_TERM_EP || term > UMPC_TERM_TAU) return refuse(fn, "bad argument (term is UMPC_TERM_EP, UMPC_TERM_ES or UMPC_TERM_TAU)");
+  if (term == UMPC_TERM_TAU && !out_hist) return refuse(fn, "UMPC_TERM_TAU needs out_hist (the moments are read from it)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_ens_quantiles<float>(h, w, order, offset, G, term, probs, nq, quant, stream)
+                              : launch_ens_quantiles<double>(h, w, order, offset, G, term, probs, nq, quant, stream);
+}
+int umpcBatchScoreQuantiles(umpc_batch_t *h, const void *score, int num, int den, const int32_t *order,
+                            const int32_t *offset, int G, const double *probs, int nq, double *quant, void *stream) {
+  const char *fn = "umpcBatchScoreQuantiles";
+  if (!h || !score || !order || !offset || !probs || !quant) return refuse(fn, "bad argument (h, score, order, offset, probs and quant must be given)");
+  if (check_groups(fn, G) || check_probs(fn, probs, nq) || check_rows(fn, num, den)) return -1;
+  return h->dtype == UMPC_F32 ? launch_score_quantiles<float>(h, score, num, den, order, offset, G, probs, nq, quant, stream)
+                              : launch_score_quantiles<double>(h, score, num, den, order, offset, G, probs, nq, quant, stream);
+}
+int umpcBatchScoreBootstrap(umpc_batch_t *h, const void *score, const void *other, int num, int den,
+                            const int32_t *order, const int32_t *offset, int G, int stat, double stat_p,
+                            int R, unsigned long long seed, const double *probs, int nq,
+                            double *boot, double *reps, double *work, void *stream) {
+  const char *fn = "umpcBatchScoreBootstrap";
+  if (!score || !order || !offset || !probs) return refuse(fn, "bad argument (score, order, offset and probs must be given)");
+  if (!boot || !reps || !work) return refuse(fn, "bad argument (boot [G][5 + nq], reps [G][R] and work [B + G] must be given)");
+  if (check_groups(fn, G)) return -1;
+  if (R < 2 || R > UMPC_BOOT_MAX_REPS) return refuse(fn, "bad argument (2 <= R <= 1048576 replicates)");
+  if (stat != UMPC_BOOT_MEAN && stat != UMPC_BOOT_QUANTILE) return refuse(fn, "bad argument (stat is UMPC_BOOT_MEAN or UMPC_BOOT_QUANTILE)");
+  if (!(stat_p >= 0.0 && stat_p <= 1.0)) return refuse(fn, "bad argument (stat_p in [0, 1])");
+  if (check_probs(fn, probs, nq) || check_rows(fn, num, den)) return -1;
+  // (the handle last: every other refusal can be met without one; nothing above reads it)
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  return h->dtype == UMPC_F32
+             ? launch_score_bootstrap<float>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream)
+             : launch_score_bootstrap<double>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream);
+}
+
+}  // extern "C"
