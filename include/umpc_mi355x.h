@@ -489,6 +489,52 @@ int umpcBatchScoreBootstrap(umpc_batch_t *h, const void *score, const void *othe
                             int R, unsigned long long seed, const double *probs, int nq,
                             double *boot, double *reps, double *work, void *stream);
 
+/* Bootstrap confidence bands of ensemble curves: the error bar of the per-step curve of a group (the mean or a quantile of a
+ * term over the draws of a grid cell, or of MPC minus reactive), pointwise and SIMULTANEOUS over the window. A pure function
+ * of its arguments like umpcBatchEnsembleQuantiles, whose tables, window (first, count, ref_first, after), reference
+ * (exactly one of ref_tab, ref), group index and term it takes: it reads no cursor of the handle, takes only B, the dtype
+ * and taulim from it, is asynchronous on `stream` and allocates nothing; probs and levels are HOST arrays.
+ * Step i of the window, group g: v_i[0 .. nsc_i) is the term of the members scored at that step -- the rule of
+ * umpcBatchEnsembleQuantiles with the same out_hist -- in member-list order, as a double. With other_state (a second
+ * history of the same shape and dtype, e.g. the reactive run of the same sweep; other_out given exactly when out_hist is)
+ * a member enters when BOTH histories score it against the SAME reference and x - x_other, subtracted in double, is finite:
+ * that difference is the value, a comparison paired by draw. Replicate r of the step is the statistic (stat, stat_p: those
+ * of umpcBatchScoreBootstrap) of v_i resampled with the indices of that call for (seed, r, slot, nsc_i): they do not depend
+ * on the step, so while nsc does not change replicate r draws the same members at every step -- it resamples whole
+ * trajectories. When a draw drops out mid-window its later steps are resampled with the indices of the new count.
+ * band [count][G][UMPC_BAND_ROWS + nq], DOUBLE, overwritten:
+ *   0  members scored (nsc)     1  members skipped     2  the statistic of v_i itself (the point estimate)
+ *   3  mean of the R replicates     4  their standard error, two passes, R - 1 in the divisor
+ *   5  1.0 when the step ENTERS the simultaneous statistic -- nsc >= 2 and the R replicates are not all the same double
+ *      (a test on the replicates, not on se > 0) --, else 0.0
+ *   6 + k  the nearest-rank element of the R replicates at probs[k]: the pointwise percentile band
+ * nsc = 0 gives NaN from column 2 on and 0 in column 5.
+ * sup [G][R], DOUBLE: sup[g][r] = the largest |t_{i,r} - point_i| / se_i over the entering steps i (a comparison that a NaN
+ * never wins), a NaN row when no step enters. crit [G][1 + nl], DOUBLE: column 0 = the number of entering steps, column
+ * 1 + j = the nearest-rank element of sup[g] at levels[j], NaN when no step enters. The simultaneous band of group g at
+ * level j is point_i +- crit[g][1 + j] * se_i over its entering steps: it contains the whole curve with about that
+ * probability, which a pointwise band does not. crit == NULL && sup == NULL (with nl == 0) asks for band alone.
+ * work: DOUBLE [B + G], scratch of the call (the compacted values of groups above 64 members); the caller owns it, and two
+ * calls in flight need two. One launch, one pass over the tables; the replicates are never stored (nothing of size R * B
+ * or count * G * R exists). Bit-reproducible: no atomics, every order of summation fixed and that of
+ * umpcBatchScoreBootstrap: a step equals umpcBatchScore(count = 1) + umpcBatchScoreBootstrap on it bit for bit. A group of
+ * up to 64 scored values is resampled in the registers of a wavefront; a larger one through L2, correct and not tuned.
+ * Rows of the blocks of a sharded job do NOT combine: keep a cell inside one block.
+ * Refused (-1, umpcLastError) BEFORE any HIP call: state_hist, order, offset, probs, band or work NULL; one of crit and sup
+ * without the other; both or neither of ref_tab and ref; count, first or ref_first < 0; count > 2^31 - 1; G < 1; R outside
+ * 2..UMPC_BAND_MAX_REPS; stat neither of the two; stat_p outside [0, 1] or NaN; nq outside 1..8 or a probability outside
+ * [0, 1] or NaN; with crit, nl outside 1..8 or a level outside [0, 1] or NaN or levels NULL; without crit, nl != 0; term
+ * outside 0..2; UMPC_TERM_TAU without out_hist; other_out without other_state, or other_state with other_out given and
+ * out_hist not (or the reverse); h NULL. count == 0 is a successful no-op. */
+#define UMPC_BAND_ROWS 6   /* columns ahead of the percentile columns */
+#define UMPC_BAND_MAX_REPS 4096
+int umpcBatchEnsembleBootstrap(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *other_state,
+                               const void *other_out, const void *ref_tab, const void *ref, long long first,
+                               long long count, long long ref_first, int after, const int32_t *order,
+                               const int32_t *offset, int G, int term, int stat, double stat_p, int R,
+                               unsigned long long seed, const double *probs, int nq, const double *levels, int nl,
+                               double *band, double *crit, double *sup, double *work, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

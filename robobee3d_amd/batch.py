@@ -615,6 +615,67 @@ class BatchUprightMPC:
                                                        _ptr(work), self._stream()))
         return (boot, rep) if return_reps else boot
 
+    def ensemble_bootstrap(self, index, term="ep", stat="mean", p=0.5, reps=1000, seed=0, probs=(0.025, 0.975), levels=(0.95,),
+                           other=None, first=0, count=None, after=False, ref_table=None, ref_first=0, simultaneous=True, out=None):
+        """Bootstrap confidence bands of the per-step curve of each group over the recorded steps first .. first + count - 1
+        (umpcBatchEnsembleBootstrap; columns: robobee3d_amd/score.py BAND_N scored, BAND_SKIPPED, BAND_POINT the statistic of
+        the cell at that step, BAND_MEAN and BAND_SE of its replicates, BAND_ENTERS, then the nearest-rank element of the
+        replicates for each of `probs`: the POINTWISE percentile band): band [count, G, 6 + len(probs)] float64, in ONE launch
+        and one pass over the tables, the replicates never stored. term, first, count, after, ref_table, ref_first and out are
+        those of ensemble_quantiles() and the reference is resolved as there; stat, p, reps (2 .. 4096) and seed those of
+        score_bootstrap(). other: another handle of the same B, dtype and device whose recorded history is read at the same
+        window against the SAME reference -- in practice the reactive run of the same sweep: the value of a draw is then its
+        term minus the other run's, a comparison paired by draw, and a draw missing in either run is skipped.
+        The resample indices depend on (seed, replicate, slot, members scored) alone, so a replicate draws the same members at
+        every step: it resamples whole trajectories. simultaneous=True returns (band, crit, sup): sup [G, reps] is every
+        replicate's largest |t - point| / se over the steps that enter (BAND_ENTERS: at least two members scored and
+        replicates that are not all the same double), crit [G, 1 + len(levels)] the number of entering steps and the
+        nearest-rank element of sup[g] at each level. The simultaneous band of group g at levels[j] is
+            band[:, g, BAND_POINT, None] + crit[g, 1 + j] * band[:, g, BAND_SE, None] * torch.tensor([-1.0, 1.0])
+        -- one expression, left to the caller: it contains the whole curve with about that probability, which the pointwise
+        band does not (a 90 % pointwise band around 20 steps holds the whole curve 15-20 % of the time). When a draw drops
+        out mid-window its later steps are resampled with the indices of the new count. No host synchronisation;
+        bit-reproducible. Rows of the blocks of a sharded job do not combine: keep a cell inside one block."""
+        from .score import BAND_FIRST, BAND_MAX_REPS, BOOT_STATS, TERM_NAMES
+        hist, first, count = self._history_window("ensemble_bootstrap", first, count)
+        order, offset, G = self._group_index_arg("ensemble_bootstrap", index)
+        if term not in TERM_NAMES:
+            raise ValueError("ensemble_bootstrap: term is one of %s" % (TERM_NAMES,))
+        if term == "tau" and hist["out"] is None:
+            raise RuntimeError("ensemble_bootstrap: term 'tau' needs the out record of the step history")
+        if stat not in BOOT_STATS or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("ensemble_bootstrap: stat is one of %s, p in [0, 1]" % (BOOT_STATS,))
+        R = int(reps)
+        if not 2 <= R <= BAND_MAX_REPS:
+            raise ValueError("ensemble_bootstrap: 2 <= reps <= %d" % BAND_MAX_REPS)
+        cprobs, nq = self._probs_arg("ensemble_bootstrap", probs)
+        clevels, nl = self._probs_arg("ensemble_bootstrap", levels) if simultaneous else (None, 0)
+        ostate = oout = None
+        if other is not None:
+            if not isinstance(other, BatchUprightMPC) or other.B != self.B or other.dtype != self.dtype or other.state.device != self.state.device:
+                raise ValueError("ensemble_bootstrap: other must be a handle of the same B, dtype and device")
+            ohist, _, _ = other._history_window("ensemble_bootstrap (other)", first, count)
+            if (ohist["out"] is None) != (hist["out"] is None):
+                raise ValueError("ensemble_bootstrap: both histories must have the out record, or neither")
+            ostate, oout = ohist["state"], ohist["out"]
+        reftab, rfirst = self._scoring_reference("ensemble_bootstrap", first, count, ref_table, ref_first)
+        band = self._out_arg(out, (count, G, BAND_FIRST + nq))
+        crit = sup = None
+        if simultaneous:
+            crit = torch.empty((G, 1 + nl), dtype=torch.float64, device=self.device)
+            sup = torch.empty((G, R), dtype=torch.float64, device=self.device)
+        work = torch.empty((self.B + G,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchEnsembleBootstrap(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(ostate), _ptr(oout),
+                                                          _ptr(reftab), None if reftab is not None else _ptr(self.ref), first,
+                                                          count, rfirst, int(bool(after)), _ptr(order), _ptr(offset), G,
+                                                          TERM_NAMES.index(term), BOOT_STATS.index(stat), float(p), R,
+                                                          int(seed) & 0xFFFFFFFFFFFFFFFF, cprobs, nq, clevels, nl, _ptr(band),
+                                                          _ptr(crit), _ptr(sup), _ptr(work), self._stream()))
+        if simultaneous and count == 0:
+            crit.fill_(float("nan")); sup.fill_(float("nan")); crit[:, 0] = 0.0      # (a no-op of the library: no step enters)
+        return (band, crit, sup) if simultaneous else band
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

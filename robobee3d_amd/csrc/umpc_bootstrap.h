@@ -33,7 +33,7 @@
 //    writes it to boot[g][2].
 // 3. umpc_boot_row_kernel, one block per cell over reps[g][0 .. R): the percentile columns by quant_block_row, the mean of
 //    the replicates accumulated in double-double (TwoSum per addend, thread-strided, a fixed LDS tree), then a second pass
-//    for sum (t_r - mean)^2 in plain doubles in the same order.
+//    for sum (t_r - mean)^2 in plain doubles in the same order (boot_row_moments).
 // Orders of summation. A replicate's sum: path A the butterfly above, path B thread-strided then the tree: functions of nsc
 // alone. The row's: thread-strided then the tree: functions of R alone. Nothing is atomic; two calls give the same bits.
 #pragma once
@@ -276,25 +276,9 @@ struct BootRowLds {
   double hi[kBootThreads], lo[kBootThreads];
 };
 
-__global__ __launch_bounds__(kBootThreads) void umpc_boot_row_kernel(const BootArgs e) {
-  __shared__ BootRowLds lds;
-  const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y), tid = wave * 64 + lane;
-  const int g = blockIdx.x;
-  const int n = group_window(e.offset, g).n;
-  const int nsc = __builtin_amdgcn_readfirstlane((int)e.work[(size_t)e.B + g]);
-  const int R = e.R, nq = e.q.nq;
-  double *boot = e.boot + (size_t)g * (kBootRows + nq);
-  const double *t = e.reps + (size_t)g * R;
-  if (tid < 2) boot[tid] = (double)(tid == 0 ? nsc : n - nsc);
-  if (nsc == 0) {                                       // (column 2 is the replicate kernel's)
-    if (tid >= 3 && tid < kBootRows + nq) boot[tid] = __builtin_nan("");
-    return;
-  }
-  // the percentile interval: nearest-rank elements of the R replicates
-  quant_block_init(e.q, tid, lds.q);
-  quant_block_row<uint64_t>([&](int r, bool &ok) { ok = true; return quant_image(t[r]); }, R, nq, lane, wave, lds.q, lds.row);
-  if (tid < nq) boot[kBootRows + tid] = lds.row[2 + tid];
-  // their mean: double-double partial sums, thread-strided, then a fixed tree
+// the mean of t[0 .. R) and the sum of the squares about it, by the block (also the band kernel's, umpc_band.h, on a row in LDS):
+// double-double partial sums, thread-strided, then a fixed tree; then a second pass in plain doubles in the same order
+__device__ __forceinline__ void boot_row_moments(const double *t, int R, int tid, BootRowLds &lds, double &mean, double &ss) {
   double hi = 0.0, lo = 0.0;
   for (int r = tid; r < R; r += kBootThreads) {
     double s, err;
@@ -314,13 +298,36 @@ __global__ __launch_bounds__(kBootThreads) void umpc_boot_row_kernel(const BootA
     }
   }
   __syncthreads();
-  const double mean = lds.hi[0] / (double)R;
+  mean = lds.hi[0] / (double)R;
   __syncthreads();
   // their spread about that mean, second pass
   double acc = 0.0;
   for (int r = tid; r < R; r += kBootThreads) { const double d = t[r] - mean; acc += d * d; }
   lds.hi[tid] = acc;
-  const double ss = boot_block_sum(lds.hi, tid);
+  ss = boot_block_sum(lds.hi, tid);
+}
+
+__global__ __launch_bounds__(kBootThreads) void umpc_boot_row_kernel(const BootArgs e) {
+  __shared__ BootRowLds lds;
+  const int lane = threadIdx.x, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y), tid = wave * 64 + lane;
+  const int g = blockIdx.x;
+  const int n = group_window(e.offset, g).n;
+  const int nsc = __builtin_amdgcn_readfirstlane((int)e.work[(size_t)e.B + g]);
+  const int R = e.R, nq = e.q.nq;
+  double *boot = e.boot + (size_t)g * (kBootRows + nq);
+  const double *t = e.reps + (size_t)g * R;
+  if (tid < 2) boot[tid] = (double)(tid == 0 ? nsc : n - nsc);
+  if (nsc == 0) {                                       // (column 2 is the replicate kernel's)
+    if (tid >= 3 && tid < kBootRows + nq) boot[tid] = __builtin_nan("");
+    return;
+  }
+  // the percentile interval: nearest-rank elements of the R replicates
+  quant_block_init(e.q, tid, lds.q);
+  quant_block_row<uint64_t>([&](int r, bool &ok) { ok = true; return quant_image(t[r]); }, R, nq, lane, wave, lds.q, lds.row);
+  if (tid < nq) boot[kBootRows + tid] = lds.row[2 + tid];
+  // their mean and their spread about it
+  double mean, ss;
+  boot_row_moments(t, R, tid, lds, mean, ss);
   if (tid == 0) { boot[3] = mean; boot[4] = __builtin_sqrt(ss / (double)(R - 1)); }
 }
 

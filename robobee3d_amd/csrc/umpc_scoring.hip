@@ -1,6 +1,6 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchScoreBootstrap) and their
-// host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h and umpc_bootstrap.h:
-// nothing here reads the step path or a generated header.
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchEnsembleBootstrap) and their
+// host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h and
+// umpc_band.h: nothing here reads the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -11,6 +11,7 @@
 #include "umpc_ensemble.h" // per-step, per-group statistics of recorded rollouts (umpcBatchEnsemble)
 #include "umpc_quantile.h" // per-step, per-group order statistics (umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles)
 #include "umpc_bootstrap.h" // bootstrap intervals of a per-group cost table (umpcBatchScoreBootstrap)
+#include "umpc_band.h"     // bootstrap bands of per-step, per-group curves (umpcBatchEnsembleBootstrap)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -18,7 +19,7 @@ static bool score_nt() {
   return v;
 }
 
-// ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchScoreBootstrap) ----------------------
+// ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchEnsembleBootstrap) -------------------
 // the recorded tables and the window of a call, as the C ABI passes them
 struct ScoreWindow {
   const void *state_hist, *out_hist;
@@ -200,6 +201,37 @@ static int launch_score_bootstrap(umpc_batch_t *h, const void *score, const void
   return launch_status("umpcBatchScoreBootstrap");
 }
 
+// one block per cell walks the window; the replicates of the step in hand are its dynamic LDS
+template <typename T>
+static int launch_ens_bootstrap(umpc_batch_t *h, const ScoreWindow &w, const void *other_state, const void *other_out,
+                                const int32_t *order, const int32_t *offset, int G, int term, int stat, double stat_p, int R,
+                                unsigned long long seed, const double *probs, int nq, const double *levels, int nl, double *band,
+                                double *crit, double *sup, double *work, void *stream) {
+  umpc::BandArgs<T> e;
+  e.t = score_args<T>(h, w, 0.0, 0, nullptr);
+  ScoreWindow wo = w;
+  wo.state_hist = other_state; wo.out_hist = other_out;
+  const umpc::ScoreArgs<T> o = score_args<T>(h, wo, 0.0, 0, nullptr);
+  e.ostate = other_state ? o.state : nullptr; e.oout = o.out;
+  e.order = order; e.offset = offset; e.band = band; e.crit = crit; e.sup = sup; e.work = work;
+  e.c0 = seed * 0x9E3779B97F4A7C15ull + umpc::kBootSalt;      // (wraps: the hash is arithmetic modulo 2^64)
+  e.stat_p = stat_p; e.G = G; e.R = R; e.term = term;
+  e.q = quant_probs(probs, nq);
+  e.lv = quant_probs(levels, nl);
+  const dim3 grid((unsigned)G), block(64, umpc::kBootWaves);
+  const size_t lds = (size_t)R * sizeof(double);
+  const hipStream_t s = (hipStream_t)stream;
+  // the cells of up to 64 members (in the form that holds R / 256 running maxima per thread), then the larger ones
+  const bool few = R <= umpc::kBandHoldFew * umpc::kBootThreads;
+#define UMPC_BAND_FORM(STAT)                                                                                             \
+  if (few) hipLaunchKernelGGL((umpc::umpc_band_kernel<T, STAT, false, umpc::kBandHoldFew>), grid, block, lds, s, e);      \
+  else hipLaunchKernelGGL((umpc::umpc_band_kernel<T, STAT, false, umpc::kBandHold>), grid, block, lds, s, e);             \
+  hipLaunchKernelGGL((umpc::umpc_band_kernel<T, STAT, true, umpc::kBandHold>), grid, block, lds, s, e);
+  if (stat == UMPC_BOOT_MEAN) { UMPC_BAND_FORM(umpc::kBootMean) } else { UMPC_BAND_FORM(umpc::kBootQuantile) }
+#undef UMPC_BAND_FORM
+  return launch_status("umpcBatchEnsembleBootstrap");
+}
+
 extern "C" {
 
 int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
@@ -294,6 +326,41 @@ int umpcBatchScoreBootstrap(umpc_batch_t *h, const void *score, const void *othe
   return h->dtype == UMPC_F32
              ? launch_score_bootstrap<float>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream)
              : launch_score_bootstrap<double>(h, score, other, num, den, order, offset, G, stat, stat_p, R, seed, probs, nq, boot, reps, work, stream);
+}
+int umpcBatchEnsembleBootstrap(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *other_state,
+                               const void *other_out, const void *ref_tab, const void *ref, long long first, long long count,
+                               long long ref_first, int after, const int32_t *order, const int32_t *offset, int G, int term,
+                               int stat, double stat_p, int R, unsigned long long seed, const double *probs, int nq,
+                               const double *levels, int nl, double *band, double *crit, double *sup, double *work,
+                               void *stream) {
+  const char *fn = "umpcBatchEnsembleBootstrap";
+  const ScoreWindow w = {state_hist, out_hist, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!state_hist || !order || !offset || !probs) return refuse(fn, "bad argument (state_hist, order, offset and probs must be given)");
+  if (!band || !work) return refuse(fn, "bad argument (band [count][G][6 + nq] and work [B + G] must be given)");
+  if ((crit != nullptr) != (sup != nullptr)) return refuse(fn, "bad argument (crit [G][1 + nl] and sup [G][R] are given together or not at all)");
+  if (check_window(fn, w) || check_groups(fn, G)) return -1;
+  if (R < 2 || R > UMPC_BAND_MAX_REPS) return refuse(fn, "bad argument (2 <= R <= 4096 replicates)");
+  if (stat != UMPC_BOOT_MEAN && stat != UMPC_BOOT_QUANTILE) return refuse(fn, "bad argument (stat is UMPC_BOOT_MEAN or UMPC_BOOT_QUANTILE)");
+  if (!(stat_p >= 0.0 && stat_p <= 1.0)) return refuse(fn, "bad argument (stat_p in [0, 1])");
+  if (check_probs(fn, probs, nq)) return -1;
+  if (crit) {
+    bool ok = levels != nullptr && nl >= 1 && nl <= UMPC_QUANT_MAX_PROBS;
+    for (int j = 0; ok && j < nl; ++j) ok = levels[j] >= 0.0 && levels[j] <= 1.0;
+    if (!ok) return refuse(fn, "bad argument (1 to 8 levels, each in [0, 1], with crit and sup)");
+  } else if (nl != 0) {
+    return refuse(fn, "bad argument (levels without crit and sup: nl must be 0)");
+  }
+  if (term < UMPC_TERM_EP || term > UMPC_TERM_TAU) return refuse(fn, "bad argument (term is UMPC_TERM_EP, UMPC_TERM_ES or UMPC_TERM_TAU)");
+  if (term == UMPC_TERM_TAU && !out_hist) return refuse(fn, "UMPC_TERM_TAU needs out_hist (the moments are read from it)");
+  if (other_out && !other_state) return refuse(fn, "bad argument (other_out without other_state)");
+  if (other_state && (other_out != nullptr) != (out_hist != nullptr))
+    return refuse(fn, "other_state needs other_out exactly when out_hist is given (both runs are scored by the same rule)");
+  // (the handle last: every other refusal can be met without one; nothing above reads it)
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32
+             ? launch_ens_bootstrap<float>(h, w, other_state, other_out, order, offset, G, term, stat, stat_p, R, seed, probs, nq, levels, nl, band, crit, sup, work, stream)
+             : launch_ens_bootstrap<double>(h, w, other_state, other_out, order, offset, G, term, stat, stat_p, R, seed, probs, nq, levels, nl, band, crit, sup, work, stream);
 }
 
 }  // extern "C"

@@ -2,8 +2,8 @@
 numpy fp64 mirrors. The device path is BatchUprightMPC.score / score_groups (batch.py); nothing here touches a device, and
 the mirrors are the definition the kernels are tested against, not a fallback. The same holds for the ensemble rows of
 umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble) and for the order statistics of
-umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles) and the bootstrap of
-umpcBatchScoreBootstrap (score_bootstrap) further down.
+umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles), the bootstrap of
+umpcBatchScoreBootstrap (score_bootstrap) and the bootstrap bands of umpcBatchEnsembleBootstrap (ensemble_bootstrap) further down.
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -421,3 +421,132 @@ def score_bootstrap_reference(score, order, offset, num, den=None, other=None, s
         for k, q in enumerate(probs):
             boot[g, BOOT_FIRST + k] = ts[quantile_rank(q, R)]
     return boot, out
+
+
+def _boot_replicates(v, J, stat, p):
+    """[R]: _boot_statistic of every resample v[J[r]], J [R, nsc] from bootstrap_indices -- the same values row by row, formed
+    once for all rows: an fsum per row, or one sort of the total-order images along the rows (equal images are equal doubles)"""
+    S = v[J]
+    n = S.shape[1]
+    if stat == 0:
+        return np.array([math.fsum(row) / n for row in S.tolist()])
+    img = np.sort(_total_order_image(S), axis=1)[:, quantile_rank(p, n)]
+    return np.where(img >> np.uint64(63) != 0, img & np.uint64((1 << 63) - 1), ~img).view(np.float64)
+
+
+def band_rows(t, point, nsc, probs, levels):
+    """The band of ONE group from its replicates, the second half of ensemble_bootstrap_reference: t [K, R] the replicates of
+    every step (rows with nsc = 0 are not read), point [K], nsc [K]. Returns (rows [K, 3 + nq] = mean, standard error, enters,
+    the percentile columns; NaN and enters = 0 where nsc = 0), sup [R], crit [1 + nl]. A step enters when nsc >= 2 and its R
+    replicates are not all the same double (total-order images: -0 is not +0); sup[r] is the largest |t[i, r] - point[i]| /
+    se[i] over the entering steps, found by comparisons that a NaN never wins, from 0; crit[0] the number of entering steps,
+    crit[1 + j] the element at quantile_rank(levels[j], R) of sup sorted; NaN when no step enters. Every sum is an fsum."""
+    t = np.asarray(t, np.float64)
+    K, R = t.shape
+    rows = np.full((K, 3 + len(probs)), np.nan)
+    rows[:, 2] = 0.0
+    sup, entered = np.zeros(R), 0
+    for i in range(K):
+        if nsc[i] == 0:
+            continue
+        ti = t[i]
+        mean = math.fsum(ti.tolist()) / R
+        se = math.sqrt(math.fsum(((ti - mean) ** 2).tolist()) / (R - 1))
+        img = _total_order_image(ti)
+        ts = ti[np.argsort(img, kind="stable")]
+        rows[i, 0], rows[i, 1] = mean, se
+        rows[i, 3:] = [ts[quantile_rank(q, R)] for q in probs]
+        if nsc[i] >= 2 and img.min() != img.max():
+            rows[i, 2] = 1.0
+            entered += 1
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                d = np.abs(ti - point[i]) / se
+                sup = np.where(d > sup, d, sup)
+    crit = np.full(1 + len(levels), np.nan)
+    crit[0] = entered
+    if entered == 0:
+        return rows, np.full(R, np.nan), crit
+    ss = np.sort(sup)
+    crit[1:] = [ss[quantile_rank(q, R)] for q in levels]
+    return rows, sup, crit
+
+
+BAND_N, BAND_SKIPPED, BAND_POINT, BAND_MEAN, BAND_SE, BAND_ENTERS, BAND_FIRST = 0, 1, 2, 3, 4, 5, 6
+BAND_MAX_REPS = 4096
+
+
+def ensemble_bootstrap_reference(state_hist, out_hist, ref, first, count, ref_first, after, taulim, order, offset, term=TERM_EP,
+                                 other=None, stat="mean", p=0.5, reps=1000, seed=0, probs=(0.025, 0.975), levels=(0.95,),
+                                 dtype=np.float64):
+    """umpcBatchEnsembleBootstrap in numpy, group by group, step by step and replicate by replicate: (band [count, G, 6 + nq],
+    crit [G, 1 + nl], sup [G, R]). The tables, first, count, ref_first, after, order, offset and term are those of
+    ensemble_quantiles_reference. At step i of the window the values of group g are the terms of its members scored at
+    that step (the rule of ensemble_quantiles_reference with the same out_hist) in member-list order, v_i[0 .. nsc_i). With
+    other = (state_hist, out_hist or None) of a second run of the same shape, read against the SAME reference, a member
+    enters when both runs score it and x - x_other, subtracted in double, is finite; that difference is the value.
+    Replicate t[i, r] = the statistic of v_i[bootstrap_indices(nsc_i, R, seed)[r]]: its fsum / nsc_i (stat "mean") or its
+    element at quantile_rank(p, nsc_i) in the total order (stat "quantile"), exactly as score_bootstrap_reference. The
+    indices do not depend on the step: while nsc does not change, replicate r resamples the same members at every step --
+    whole trajectories. When a draw drops out mid-window its steps are resampled with the indices of the new count.
+    band columns: BAND_N scored, BAND_SKIPPED, BAND_POINT the statistic of v_i, BAND_MEAN fsum(t_i) / R, BAND_SE
+    sqrt(fsum((t_i - mean)^2) / (R - 1)), BAND_ENTERS 1.0 when the step enters the simultaneous statistic (nsc_i >= 2 and the
+    R replicates are not all the same double -- a test on replicates, not on se > 0), BAND_FIRST + k the element at
+    quantile_rank(probs[k], R) of the sorted replicates: the pointwise percentile band. nsc_i = 0: NaN from BAND_POINT on and
+    BAND_ENTERS = 0. sup[g, r] = max over the entering steps of |t[i, r] - point_i| / se_i, crit[g, 0] = the number of entering
+    steps, crit[g, 1 + j] = the element at quantile_rank(levels[j], R) of sup[g] sorted; NaN when no step enters (band_rows).
+    The simultaneous band of group g is band[:, g, BAND_POINT] +- crit[g, 1 + j] * band[:, g, BAND_SE].
+    dtype: the terms are evaluated in it (the same operations in the same order as the kernels' score_terms) and then widened
+    to double: np.float32 gives the values the device forms from fp32 tables bit for bit, so that what is left between the
+    mirror and the device is the rounding of the sums alone. Everything behind the values is fp64 either way.
+    Like quantiles, the rows of the blocks of a sharded job do not combine: keep a cell inside one block."""
+    dtype = np.dtype(dtype)
+    st = np.asarray(state_hist).astype(dtype)
+    out = None if out_hist is None else np.asarray(out_hist).astype(dtype)
+    ref = np.asarray(ref).astype(dtype)
+    order, offset = np.asarray(order), np.asarray(offset)
+    first, count, ref_first, after, term = int(first), int(count), int(ref_first), int(bool(after)), int(term)
+    G, R = len(offset) - 1, int(reps)
+    probs = _check_probs(probs, "ensemble_bootstrap_reference")
+    levels = _check_probs(levels, "ensemble_bootstrap_reference")
+    if (count < 0 or first < 0 or ref_first < 0 or G < 1 or term not in (TERM_EP, TERM_ES, TERM_TAU)
+            or (term == TERM_TAU and out is None) or stat not in BOOT_STATS or not 0.0 <= float(p) <= 1.0
+            or not 2 <= R <= BAND_MAX_REPS):
+        raise ValueError("ensemble_bootstrap_reference: bad argument (term, stat 'mean' or 'quantile', p in [0, 1], 2 <= reps <= 4096)")
+    ost = oout = None
+    if other is not None:
+        ost = np.asarray(other[0]).astype(dtype)
+        oout = None if other[1] is None else np.asarray(other[1]).astype(dtype)
+        if ost.shape != st.shape or (oout is None) != (out is None):
+            raise ValueError("ensemble_bootstrap_reference: other must be (state_hist, out_hist) of the shape of the first run")
+    sti, p, tl = BOOT_STATS.index(stat), float(p), dtype.type(taulim)
+    x, ok = np.zeros((count, st.shape[-1])), np.zeros((count, st.shape[-1]), bool)
+    for i in range(count):
+        c = first + i
+        r = ref[ref_first + i] if ref.ndim == 3 else ref
+        terms = _step_terms(st[c + after], None if out is None else out[c], r, tl)
+        x[i], ok[i] = (terms[2 + term] if term < 2 else terms[5]).astype(np.float64), terms[0]
+        if ost is not None:
+            oterms = _step_terms(ost[c + after], None if oout is None else oout[c], r, tl)
+            with np.errstate(invalid="ignore", over="ignore"):
+                x[i] = x[i] - (oterms[2 + term] if term < 2 else oterms[5]).astype(np.float64)
+            ok[i] &= oterms[0] & np.isfinite(x[i])
+    nq = len(probs)
+    band = np.full((count, G, BAND_FIRST + nq), np.nan)
+    crit, sup = np.full((G, 1 + len(levels)), np.nan), np.full((G, R), np.nan)
+    tables = {}
+    for g in range(G):
+        mem = order[offset[g]:offset[g + 1]]
+        t, point, nsc = np.full((count, R), np.nan), np.full(count, np.nan), np.zeros(count, np.int64)
+        for i in range(count):
+            v = x[i, mem[ok[i, mem]]]
+            nsc[i] = len(v)
+            if len(v) == 0:
+                continue
+            if len(v) not in tables:
+                tables[len(v)] = bootstrap_indices(len(v), R, seed)
+            t[i] = _boot_replicates(v, tables[len(v)], sti, p)
+            point[i] = _boot_statistic(v, sti, p)
+        rows, sup[g], crit[g] = band_rows(t, point, nsc, probs, levels)
+        band[:, g, BAND_N], band[:, g, BAND_SKIPPED], band[:, g, BAND_POINT] = nsc, len(mem) - nsc, point
+        band[:, g, BAND_MEAN:] = rows
+    return band, crit, sup
