@@ -535,6 +535,66 @@ int umpcBatchEnsembleBootstrap(umpc_batch_t *h, const void *state_hist, const vo
                                unsigned long long seed, const double *probs, int nq, const double *levels, int nl,
                                double *band, double *crit, double *sup, double *work, void *stream);
 
+/* Frequency response: how fast a reference the controller still follows. Scores, ensembles and their bootstraps measure how
+ * LARGE the tracking error is; this block gives the Bode point of every robot of a (trajFreq x draws) sweep -- gain and
+ * phase of p against pdes at the robot's own task frequency, the amplitude of the tracking error there, and how much of
+ * the motion is not at that frequency at all -- by a three-parameter least-squares sine fit (IEEE 1057 style)
+ *   y_k ~ a0 + a1 cos(phi_k) + a2 sin(phi_k),   phi_k = 2 pi k nu[b]
+ * per robot and per position axis j = 0..2, of y = p_j (state row j) and of r = pdes_j (reference row j). A least-squares
+ * fit and not a DFT bin: it is exact for a window that is not a whole number of periods, and indifferent to the constant
+ * offset (initialPos, the 1 - cos of useY). Two stages, as a score holds raw sums before means: umpcBatchResponse adds the
+ * sums of the normal equations in one pass over the step history, once per chunk of a chunked run; umpcBatchResponseFit
+ * solves them once. Array expressions over the history would need [steps][B] sine and cosine tables.
+ * umpcBatchResponse is a pure function of its arguments, as umpcBatchScore is: it reads none of the handle's cursors and
+ * takes only B and the dtype from the handle. state_hist, ref_tab / ref (exactly ONE of the two), first, count, ref_first
+ * and after are those of umpcBatchScore; there is no out or status record. nu [B] DOUBLE on the device: the robot's
+ * frequency in revolutions per closed-loop step (f [Hz] x 1e-3 x nsub x dtsim). Step i of the call (c = first + i) carries
+ * k = step0 + i. Its phase is u = k nu - floor(k nu) with ONE IEEE double multiply of (double)k and nu, and c = cos(2 pi u),
+ * s = sin(2 pi u) in fp64 to a few ulp (sincospi(2 u): exactly 0 and +-1 at the quarter points): the phase of a step does
+ * not depend on how the run is cut into calls, and stays accurate at a step0 of 10^6.
+ * A step reads 6 words per robot: state rows 0..2 of slice c + after, reference rows 0..2 of table slice ref_first + i or of
+ * the constant ref. A step where any of the six, or the phase (a nu that is not finite), is not finite is counted in
+ * `skipped` and adds nothing else. The words are widened exactly; every product and every sum is fp64.
+ * sums [UMPC_RSUM_ROWS][B] DOUBLE, in/out: the call ADDS into it; umpcBatchResponseInit writes zeros. Per robot:
+ *   0  n, steps that entered        1  skipped steps
+ *   2  sum c      3  sum s      4  sum c c      5  sum c s          (sum s s = n - sum c c)
+ *   6 + 9 j + 0..8, axis j:  sum y,  sum y c,  sum y s,  sum y y,  sum r,  sum r c,  sum r s,  sum r r,  sum y r
+ * Order of summation: a block of 64 robots is 4 wavefronts; wavefront w folds steps w, w + 4, w + 8, .. of the call in
+ * order, the four partial sums are added in the order 0, 1, 2, 3 and the total is added to `sums`. Nothing crosses robots:
+ * bit-equal from run to run, and between a column block on a handle of its own and the same columns of the whole batch; no
+ * atomics, no temporaries. Rows 0 and 1 do not depend on how a step range is cut into calls; the other rows to rounding
+ * (each within (n + 16) u times the sum of its terms' magnitudes of the exact sum).
+ * umpcBatchResponseFit: one lane per robot, fp64 throughout, rounded to the handle's dtype at the store. Normal matrix
+ * M = [[n, sum c, sum s], [sum c, sum cc, sum cs], [sum s, sum cs, sum ss]], Cholesky in that variable order with the
+ * pivots d1 = n, d2, d3 (the squares of the factor's diagonal). The fit is REFUSED when n < 3 or a pivot is <= 1e-9 n (or
+ * NaN): nu = 0 and nu = 0.5, where s = 0 at every step, and windows of fewer than three steps. With Y = a1 - i a2 of y
+ * and R likewise of r, resp [3][UMPC_RESP_ROWS][B] in the handle's dtype, overwritten; per axis:
+ *   0  n, or 0 when the fit is refused (rows 2..11 are then NaN)        1  skipped steps
+ *   2  |Y|^2                        3  |R|^2
+ *   4  gain sqrt(row 2 / row 3), NaN when row 3 is 0
+ *   5  phase arg Y - arg R in (-pi, pi], negative = p lags pdes; NaN when row 3 is 0
+ *   6  Re (Y / R)                   7  Im (Y / R); both NaN when row 3 is 0
+ *   8  a0 of y                      9  a0 of r
+ *  10  mean squared residual of y's fit, max(0, (sum y y - a . rhs) / n): distortion and everything off the fundamental
+ *  11  |Y - R|^2, the squared amplitude of the tracking error at the fundamental; sqrt(row 11 / row 3) is |S|
+ * A constant reference has |R|^2 = 0 only to rounding unless it is zero: rows 4..7 then mean nothing; rows 2, 8, 10 stand.
+ * resp[axis] is shaped as a score on purpose -- [12][B], contiguous, row 0 > 0 meaning "enters" -- so
+ * umpcBatchScoreQuantiles(resp[0], num = 2, den = 3) is a cell's median gain^2 and umpcBatchScoreBootstrap(.., other = the
+ * reactive run's resp[0]) its interval and MPC minus reactive paired by draw, unchanged. Rows 0 and 1 are exact in fp32 up
+ * to 2^24 steps.
+ * Not built: more than one frequency per call (a harmonic is a second call with 2 nu); the attitude and effort signals;
+ * a per-cell reduction of the complex H beyond what the quantile and bootstrap calls give.
+ * Refused (-1, umpcLastError) BEFORE any HIP call: h NULL; state_hist, nu, sums or resp NULL; both or neither of ref_tab and
+ * ref; count, first, ref_first or step0 < 0; count > 2^31 - 9; step0 + count > 2^53. count == 0 is a successful no-op.
+ * Asynchronous on `stream`. */
+#define UMPC_RSUM_ROWS 33
+#define UMPC_RESP_ROWS 12
+int umpcBatchResponseInit(umpc_batch_t *h, double *sums, void *stream);
+int umpcBatchResponse(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, const double *nu,
+                      long long first, long long count, long long ref_first, long long step0, int after, double *sums,
+                      void *stream);
+int umpcBatchResponseFit(umpc_batch_t *h, const double *sums, void *resp, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

@@ -26,6 +26,7 @@ QUANT_MAX_PROBS = 8
 TERM_EP, TERM_ES, TERM_TAU = 0, 1, 2
 BOOT_MEAN, BOOT_QUANTILE, BOOT_ROWS, BOOT_MAX_REPS = 0, 1, 5, 1 << 20
 BAND_ROWS, BAND_MAX_REPS = 6, 4096
+RSUM_ROWS, RESP_ROWS = 33, 12
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -37,7 +38,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchSetRefTrajectory", "umpcBatchRefCursor", "umpcBatchTaskTable", "umpcBatchSetHistory", "umpcBatchHistoryCursor",
            "umpcBatchSetImpulses", "umpcBatchImpulseCursor", "umpcBatchScoreInit", "umpcBatchScore", "umpcBatchScoreGroups",
            "umpcBatchGroupIndex", "umpcBatchEnsemble", "umpcBatchEnsembleQuantiles", "umpcBatchScoreQuantiles", "umpcBatchScoreBootstrap",
-           "umpcBatchEnsembleBootstrap",
+           "umpcBatchEnsembleBootstrap", "umpcBatchResponseInit", "umpcBatchResponse", "umpcBatchResponseFit",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -290,6 +291,9 @@ def lib():
                                                  C.c_int, C.c_double, C.c_int, C.c_ulonglong, C.POINTER(C.c_double), C.c_int,
                                                  C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
+        L.umpcBatchResponseInit.argtypes = [C.c_void_p] * 3
+        L.umpcBatchResponse.argtypes = [C.c_void_p] * 5 + [C.c_longlong] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchResponseFit.argtypes = [C.c_void_p] * 4
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

@@ -676,6 +676,47 @@ class BatchUprightMPC:
             crit.fill_(float("nan")); sup.fill_(float("nan")); crit[:, 0] = 0.0      # (a no-op of the library: no step enters)
         return (band, crit, sup) if simultaneous else band
 
+    def frequency_response(self, freq_hz, first=0, count=None, after=False, ref_table=None, ref_first=0, step0=None, sums=None,
+                           fit=True):
+        """The Bode point of every robot from the recorded steps first .. first + count - 1 of the step history
+        (umpcBatchResponse / umpcBatchResponseFit; rows: robobee3d_amd/score.py RESP_* and RSUM_*): a three-parameter
+        least-squares sine fit a0 + a1 cos + a2 sin of p and of pdes, per position axis, at the robot's own frequency, in
+        ONE pass over the tables on the device -- no sine or cosine table, nothing of the tables' size allocated. freq_hz: a
+        scalar or [B], the trajFreq a robot's task was built with; nu = freq_hz * 1e-3 * nsub * dtsim revolutions per step
+        in float64 (score.response_nu). Returns (resp, sums): resp [3, 12, B] in the handle's dtype -- per axis the steps
+        that entered (0 when the fit is refused: fewer than three steps, or nu = 0 or 0.5 where the sine is zero at every
+        step; the rows behind are then NaN), the steps skipped as not finite, |Y|^2, |R|^2, gain, phase (negative = p
+        lags pdes), Re and Im of Y / R, the two offsets, the mean squared residual of p's fit (distortion and everything
+        off the fundamental) and |Y - R|^2, the squared amplitude of the tracking error at the fundamental; sums [33, B]
+        float64, the raw sums of the normal equations. first, count, after, ref_table and ref_first are those of score()
+        and the reference is resolved as there. step0 (default `first`) is the step number of step `first`: it sets the
+        phase origin. Passing `sums` back in accumulates, and fit=False accumulates only (resp is None): a chunked run
+        calls this once per chunk with rewind_history() in between, step0 = the steps already run, and fits at the end.
+        resp[axis] is shaped as a score: score_quantiles(resp[0], index, [0.5], num=RESP_Y_AMP2, den=RESP_R_AMP2) is a cell's
+        median gain^2, score_bootstrap(..., other=resp_reactive[0]) its interval and MPC minus reactive paired by draw.
+        One frequency per call: a harmonic is a second call with 2 * freq_hz."""
+        from .score import response_nu
+        hist, first, count = self._history_window("frequency_response", first, count)
+        reftab, rfirst = self._scoring_reference("frequency_response", first, count, ref_table, ref_first)
+        nu = np.broadcast_to(response_nu(freq_hz, int(self.prm.nsub), float(self.prm.dtsim)), (self.B,))
+        nu = torch.as_tensor(np.array(nu)).to(self.device)
+        with torch.cuda.device(self.device):
+            if sums is None:
+                sums = torch.empty((_lib.RSUM_ROWS, self.B), dtype=torch.float64, device=self.device)
+                self._check(self.L.umpcBatchResponseInit(self.h, _ptr(sums), self._stream()))
+            elif (tuple(sums.shape) != (_lib.RSUM_ROWS, self.B) or sums.dtype != torch.float64 or sums.device != self.state.device
+                  or not sums.is_contiguous()):
+                raise ValueError("sums must be a contiguous [33, %d] float64 tensor on the handle's device" % self.B)
+            self._check(self.L.umpcBatchResponse(self.h, _ptr(hist["state"]), _ptr(reftab),
+                                                 None if reftab is not None else _ptr(self.ref), _ptr(nu), first, count, rfirst,
+                                                 first if step0 is None else int(step0), int(bool(after)), _ptr(sums),
+                                                 self._stream()))
+            resp = None
+            if fit:
+                resp = torch.empty((3, _lib.RESP_ROWS, self.B), dtype=self.dtype, device=self.device)
+                self._check(self.L.umpcBatchResponseFit(self.h, _ptr(sums), _ptr(resp), self._stream()))
+        return resp, sums
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

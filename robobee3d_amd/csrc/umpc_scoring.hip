@@ -1,6 +1,6 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchEnsembleBootstrap) and their
-// host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h and
-// umpc_band.h: nothing here reads the step path or a generated header.
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchResponseFit) and their
+// host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
+// umpc_band.h and umpc_response.h: nothing here reads the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -12,6 +12,7 @@
 #include "umpc_quantile.h" // per-step, per-group order statistics (umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles)
 #include "umpc_bootstrap.h" // bootstrap intervals of a per-group cost table (umpcBatchScoreBootstrap)
 #include "umpc_band.h"     // bootstrap bands of per-step, per-group curves (umpcBatchEnsembleBootstrap)
+#include "umpc_response.h" // per-robot sine fit at the robot's own frequency (umpcBatchResponse / umpcBatchResponseFit)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -19,7 +20,7 @@ static bool score_nt() {
   return v;
 }
 
-// ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchEnsembleBootstrap) -------------------
+// ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchResponse) ----------------------------
 // the recorded tables and the window of a call, as the C ABI passes them
 struct ScoreWindow {
   const void *state_hist, *out_hist;
@@ -232,6 +233,25 @@ static int launch_ens_bootstrap(umpc_batch_t *h, const ScoreWindow &w, const voi
   return launch_status("umpcBatchEnsembleBootstrap");
 }
 
+// (w carries neither an out nor a status record: the kernel reads state rows 0..2 and reference rows 0..2)
+template <typename T>
+static int launch_response(umpc_batch_t *h, const ScoreWindow &w, const double *nu, long long step0, double *sums, void *stream) {
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, step0, nullptr);
+  umpc::RespArgs<T> a;
+  a.state = t.state; a.reftab = t.reftab; a.ref = t.ref; a.nu = nu; a.sums = sums;
+  a.B = t.B; a.count = t.count; a.step0 = step0;
+  const dim3 grid((unsigned)((h->B + 63) / 64)), block(64, umpc::kRespSlices);
+  const hipStream_t s = (hipStream_t)stream;
+  const int form = (score_nt() ? 2 : 0) | (a.reftab ? 1 : 0);
+  switch (form) {
+    case 0: hipLaunchKernelGGL((umpc::umpc_response_kernel<T, false, false>), grid, block, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((umpc::umpc_response_kernel<T, false, true>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((umpc::umpc_response_kernel<T, true, false>), grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((umpc::umpc_response_kernel<T, true, true>), grid, block, 0, s, a); break;
+  }
+  return launch_status("umpcBatchResponse");
+}
+
 extern "C" {
 
 int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
@@ -361,6 +381,37 @@ int umpcBatchEnsembleBootstrap(umpc_batch_t *h, const void *state_hist, const vo
   return h->dtype == UMPC_F32
              ? launch_ens_bootstrap<float>(h, w, other_state, other_out, order, offset, G, term, stat, stat_p, R, seed, probs, nq, levels, nl, band, crit, sup, work, stream)
              : launch_ens_bootstrap<double>(h, w, other_state, other_out, order, offset, G, term, stat, stat_p, R, seed, probs, nq, levels, nl, band, crit, sup, work, stream);
+}
+int umpcBatchResponseInit(umpc_batch_t *h, double *sums, void *stream) {
+  const char *fn = "umpcBatchResponseInit";
+  if (!h || !sums) return refuse(fn, "bad argument (h and sums must be given)");
+  const hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * UMPC_RSUM_ROWS * (size_t)h->B, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail(e, fn);
+}
+int umpcBatchResponse(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, const double *nu,
+                      long long first, long long count, long long ref_first, long long step0, int after, double *sums,
+                      void *stream) {
+  const char *fn = "umpcBatchResponse";
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !nu || !sums) return refuse(fn, "bad argument (state_hist, nu and sums must be given)");
+  if (check_window(fn, w)) return -1;
+  if (count > 0x7fffffffLL - 2 * umpc::kRespSlices) return refuse(fn, "count too large for one call (2^31 - 9 steps at the most)");
+  // k = step0 + i enters the phase as a double: every step number of the call must be one exactly
+  if (step0 < 0 || step0 > (1LL << 53) - count) return refuse(fn, "bad argument (0 <= step0, step0 + count <= 2^53)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_response<float>(h, w, nu, step0, sums, stream)
+                              : launch_response<double>(h, w, nu, step0, sums, stream);
+}
+int umpcBatchResponseFit(umpc_batch_t *h, const double *sums, void *resp, void *stream) {
+  const char *fn = "umpcBatchResponseFit";
+  if (!h || !sums || !resp) return refuse(fn, "bad argument (h, sums and resp must be given)");
+  const dim3 grid((unsigned)((h->B + 255) / 256));
+  if (h->dtype == UMPC_F32)
+    hipLaunchKernelGGL(umpc::umpc_response_fit_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, sums, (float *)resp, h->B);
+  else
+    hipLaunchKernelGGL(umpc::umpc_response_fit_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, sums, (double *)resp, h->B);
+  return launch_status(fn);
 }
 
 }  // extern "C"

@@ -550,3 +550,152 @@ def ensemble_bootstrap_reference(state_hist, out_hist, ref, first, count, ref_fi
         band[:, g, BAND_N], band[:, g, BAND_SKIPPED], band[:, g, BAND_POINT] = nsc, len(mem) - nsc, point
         band[:, g, BAND_MEAN:] = rows
     return band, crit, sup
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Frequency response (umpcBatchResponseInit / umpcBatchResponse / umpcBatchResponseFit): a three-parameter sine fit
+# y_k ~ a0 + a1 cos(phi_k) + a2 sin(phi_k) per robot and position axis, of p and of pdes, at the robot's own frequency
+# ----------------------------------------------------------------------------------------------------------------------
+RSUM_ROWS, RESP_ROWS = 33, 12
+# sum rows: common, then 9 per axis j at RSUM_AXIS + 9 j
+RSUM_N, RSUM_SKIPPED, RSUM_C, RSUM_S, RSUM_CC, RSUM_CS, RSUM_AXIS = 0, 1, 2, 3, 4, 5, 6
+(RSUM_Y, RSUM_YC, RSUM_YS, RSUM_YY, RSUM_R, RSUM_RC, RSUM_RS, RSUM_RR, RSUM_YR) = range(9)
+RSUM_AXIS_ROWS = 9
+# response rows, per axis (row 0 > 0 means "enters", as in a score: score_quantiles / score_bootstrap take resp[axis] as it is)
+(RESP_STEPS, RESP_SKIPPED, RESP_Y_AMP2, RESP_R_AMP2, RESP_GAIN, RESP_PHASE, RESP_H_RE, RESP_H_IM, RESP_Y_DC, RESP_R_DC,
+ RESP_Y_RES, RESP_E_AMP2) = range(12)
+RESP_ROW_NAMES = ("steps", "skipped", "y_amp2", "r_amp2", "gain", "phase", "h_re", "h_im", "y_dc", "r_dc", "y_res", "e_amp2")
+RESP_PIVOT_TOL = 1e-9       # the fit is refused when a Cholesky pivot is <= RESP_PIVOT_TOL * n
+
+
+def response_nu(freq_hz, nsub, dtsim):
+    """The frequency of a task in revolutions per closed-loop step, float64: freq_hz * 1e-3 * nsub * dtsim, multiplied in that
+    order (dtsim in ms: 5 Hz at the default 25 x 0.2 ms step is 0.025)."""
+    return np.asarray(freq_hz, np.float64) * 1e-3 * float(nsub) * float(dtsim)
+
+
+def response_identity(B):
+    """The sums no step has entered (umpcBatchResponseInit): zeros [33, B] float64."""
+    return np.zeros((RSUM_ROWS, int(B)))
+
+
+def response_phase(k, nu):
+    """(c, s) = (cos, sin)(2 pi u), u = k nu - floor(k nu) with ONE double multiply of float(k) and nu [B], and u itself. The
+    quadrant is taken out exactly first (u - j / 4 is exact), so the argument of cos / sin is at most pi / 4 and the results
+    are within ~2 ulp of the true values, exactly 0 and +-1 at the quarter points, whatever k is."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = float(k) * np.asarray(nu, np.float64)
+        u = x - np.floor(x)
+        j = np.rint(4.0 * u)
+        a = (2.0 * np.pi) * (u - 0.25 * j)
+        ca, sa = np.cos(a), np.sin(a)
+        jj = np.where(np.isfinite(j), j, 0).astype(np.int64) & 3
+    c = np.choose(jj, [ca, -sa, -ca, sa])
+    s = np.choose(jj, [sa, ca, -sa, -ca])
+    return c, s, u
+
+
+def response_sums_reference(state_hist, ref, nu, first, count, ref_first, step0, after, sums=None):
+    """umpcBatchResponse in numpy fp64, step by step in order. state_hist [.., 18, B] and ref -- a table [.., 9, B] (slice
+    ref_first + i) or one constant reference [9, B] -- are taken as given and widened; nu [B] float64 is the frequency of each
+    robot in revolutions per step. Step c = first + i reads rows 0..2 of state slice c + after and of its reference slice and
+    carries k = step0 + i, phase response_phase(k, nu). A step where any of the six words, or the phase, is not finite is
+    counted in RSUM_SKIPPED and in no other row. Returns the sums [33, B] (float64); passing one back in accumulates."""
+    st = np.asarray(state_hist, np.float64)
+    ref = np.asarray(ref, np.float64)
+    B = st.shape[-1]
+    nu = np.asarray(nu, np.float64)
+    first, count, ref_first, step0, after = int(first), int(count), int(ref_first), int(step0), int(bool(after))
+    if count < 0 or first < 0 or ref_first < 0 or step0 < 0 or step0 + count > 1 << 53 or nu.shape != (B,):
+        raise ValueError("response_sums_reference: bad argument")
+    sm = response_identity(B) if sums is None else np.array(sums, np.float64)
+    for i in range(count):
+        y = st[first + i + after, 0:3]
+        r = (ref[ref_first + i] if ref.ndim == 3 else ref)[0:3]
+        c, s, u = response_phase(step0 + i, nu)
+        ok = np.isfinite(u) & np.isfinite(y).all(0) & np.isfinite(r).all(0)
+        sm[RSUM_SKIPPED] += ~ok
+        sm[RSUM_N] += ok
+        c, s = c[ok], s[ok]
+        sm[RSUM_C, ok] += c
+        sm[RSUM_S, ok] += s
+        sm[RSUM_CC, ok] += c * c
+        sm[RSUM_CS, ok] += c * s
+        for j in range(3):
+            yj, rj, a = y[j, ok], r[j, ok], RSUM_AXIS + RSUM_AXIS_ROWS * j
+            for row, term in ((RSUM_Y, yj), (RSUM_YC, yj * c), (RSUM_YS, yj * s), (RSUM_YY, yj * yj), (RSUM_R, rj),
+                              (RSUM_RC, rj * c), (RSUM_RS, rj * s), (RSUM_RR, rj * rj), (RSUM_YR, yj * rj)):
+                sm[a + row, ok] += term
+    return sm
+
+
+def _response_factor(sm):
+    """the Cholesky factor of the normal matrix [[n, Sc, Ss], [Sc, Scc, Scs], [Ss, Scs, n - Scc]] in that variable order, in
+    the kernel's operation order: ((l11, l21, l31, l22, l32, l33), pivots [3, B], fit [B] bool)"""
+    n, Sc, Ss, Scc, Scs = sm[RSUM_N], sm[RSUM_C], sm[RSUM_S], sm[RSUM_CC], sm[RSUM_CS]
+    Sss, tol = n - Scc, RESP_PIVOT_TOL * n
+    d1 = n
+    l11 = np.sqrt(d1)
+    l21, l31 = Sc / l11, Ss / l11
+    d2 = Scc - l21 * l21
+    l22 = np.sqrt(d2)
+    l32 = (Scs - l21 * l31) / l22
+    d3 = (Sss - l31 * l31) - l32 * l32
+    l33 = np.sqrt(d3)
+    fit = (n >= 3.0) & (d1 > tol) & (d2 > tol) & (d3 > tol)
+    return (l11, l21, l31, l22, l32, l33), np.stack([d1, d2, d3]), fit
+
+
+def response_pivots(sums):
+    """[3, B]: the Cholesky pivots d1 = n, d2, d3 of every robot's normal matrix (the squares of the factor's diagonal); the
+    fit is refused when n < 3 or one of them is <= 1e-9 n. For a window of whole periods they are n, n / 2, n / 2."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return _response_factor(np.asarray(sums, np.float64))[1]
+
+
+def response_fit_reference(sums):
+    """umpcBatchResponseFit in numpy fp64, in the kernel's operation order: [3, 12, B] float64 from the sums [33, B]. Rows per
+    axis (RESP_*), with Y = a1 - i a2 of y = p_axis and R likewise of r = pdes_axis: STEPS n, or 0 when the fit is refused (n < 3
+    or a pivot <= 1e-9 n: rows 2..11 are then NaN); SKIPPED; Y_AMP2 |Y|^2; R_AMP2 |R|^2; GAIN sqrt(Y_AMP2 / R_AMP2); PHASE arg Y -
+    arg R in (-pi, pi], negative = a lag; H_RE, H_IM the parts of Y / R (GAIN, PHASE, H_RE, H_IM are NaN when R_AMP2 is 0); Y_DC,
+    R_DC the offsets a0; Y_RES = max(0, (sum yy - a . rhs) / n), the mean squared residual of y's fit; E_AMP2 |Y - R|^2."""
+    sm = np.asarray(sums, np.float64)
+    if sm.ndim != 2 or sm.shape[0] != RSUM_ROWS:
+        raise ValueError("response_fit_reference: sums must be [33, B]")
+    B = sm.shape[1]
+    resp = np.full((3, RESP_ROWS, B), np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        (l11, l21, l31, l22, l32, l33), _, fit = _response_factor(sm)
+
+        def solve(b0, b1, b2):
+            z0 = b0 / l11
+            z1 = (b1 - l21 * z0) / l22
+            z2 = ((b2 - l31 * z0) - l32 * z1) / l33
+            a2 = z2 / l33
+            a1 = (z1 - l32 * a2) / l22
+            a0 = ((z0 - l21 * a1) - l31 * a2) / l11
+            return a0, a1, a2
+
+        n = sm[RSUM_N]
+        for j in range(3):
+            x = sm[RSUM_AXIS + RSUM_AXIS_ROWS * j:RSUM_AXIS + RSUM_AXIS_ROWS * (j + 1)]
+            ay, ar = solve(x[RSUM_Y], x[RSUM_YC], x[RSUM_YS]), solve(x[RSUM_R], x[RSUM_RC], x[RSUM_RS])
+            yamp2, ramp2 = ay[1] * ay[1] + ay[2] * ay[2], ar[1] * ar[1] + ar[2] * ar[2]
+            re, im = ay[1] * ar[1] + ay[2] * ar[2], ay[1] * ar[2] - ay[2] * ar[1]
+            href = ramp2 > 0.0
+            res = (x[RSUM_YY] - ((ay[0] * x[RSUM_Y] + ay[1] * x[RSUM_YC]) + ay[2] * x[RSUM_YS])) / n
+            e1, e2 = ay[1] - ar[1], ay[2] - ar[2]
+            at = np.arctan2(im, re)
+            o = resp[j]
+            o[RESP_STEPS] = n
+            o[RESP_Y_AMP2], o[RESP_R_AMP2] = yamp2, ramp2
+            o[RESP_GAIN] = np.where(href, np.sqrt(yamp2 / ramp2), np.nan)
+            o[RESP_PHASE] = np.where(href, np.where(at == -np.pi, np.pi, at), np.nan)
+            o[RESP_H_RE], o[RESP_H_IM] = np.where(href, re / ramp2, np.nan), np.where(href, im / ramp2, np.nan)
+            o[RESP_Y_DC], o[RESP_R_DC] = ay[0], ar[0]
+            o[RESP_Y_RES] = np.where(res > 0.0, res, 0.0)
+            o[RESP_E_AMP2] = e1 * e1 + e2 * e2
+            o[2:, ~fit] = np.nan
+            o[RESP_STEPS, ~fit] = 0.0
+            o[RESP_SKIPPED] = sm[RSUM_SKIPPED]
+    return resp
