@@ -595,6 +595,79 @@ int umpcBatchResponse(umpc_batch_t *h, const void *state_hist, const void *ref_t
                       void *stream);
 int umpcBatchResponseFit(umpc_batch_t *h, const double *sums, void *resp, void *stream);
 
+/* Dispersion ellipsoids: the mean vector, the covariance and the k-sigma ellipsoid of the error state of each group of
+ * robots at every step -- the standard product of a Monte-Carlo dispersion study -- and the Mahalanobis distance of every
+ * robot from its own cell's ellipsoid. Every other table here works on a scalar norm (e_p, e_s, the clipped moments); the
+ * direction of the error and the correlation between axes are kept only here. Array expressions would need a
+ * [steps][B][21] temporary. All four calls are pure functions of their arguments, as umpcBatchScore is: they read no
+ * cursor of the handle, take only B and the dtype from it, are asynchronous on `stream` and allocate nothing.
+ * Error state of robot b at a step: z = (p - pdes, v - dpdes) in R^6; p = state rows 0..2, v = state rows 12..14 (world
+ * frame), pdes = reference rows 0..2, dpdes = reference rows 3..5: 12 words (48 B in fp32) per robot-step, each read once.
+ * Each difference is formed in the handle's dtype with one rounding, then widened to double.
+ * umpcBatchDispersion takes state_hist, ref_tab / ref (exactly ONE of the two), first, count, ref_first, after, order, offset
+ * and G exactly as umpcBatchEnsemble does; there is no out or status record and no tube. A member is scored at a step when
+ * all 12 words it reads there are finite, and skipped otherwise. THIS IS NOT umpcBatchEnsemble's RULE: that call reads s, out
+ * and the status and not v, this one reads v and dpdes and none of them. mom [count][G][UMPC_DISP_ROWS] is DOUBLE whatever
+ * the dtype and is OVERWRITTEN; row i belongs to step first + i. Per (step, group):
+ *   0  members scored               1  members skipped (not finite); they enter no other row
+ *   2..7   S1 = sum z
+ *   8..28  S2 = sum z_i z_j for i <= j, the upper triangle row by row: (0,0) (0,1) .. (0,5) (1,1) .. (5,5)
+ *  29..31  0, reserved
+ * The products are formed in double: exact for an fp32 handle, one rounding for an fp64 one (no contraction).
+ * Order of summation: lane l of a wavefront starts at +0 and adds the terms of members l, l + 64, .. of the group's list in
+ * that order; then for w = 32, 16, 8, 4, 2, 1 every lane l replaces its value by (value of l) + (value of l ^ w) (the kernel
+ * evaluates this tree of pairwise sums only in the lanes that store: 32 doubles cross lanes per row, not 27 x 6). The order
+ * of a (step, group) row is a function of that group's member list alone: it does not depend on G, on the other groups, on
+ * how the step range is cut into calls, or on the run -- the same bits every time, no floating-point atomics. Each entry
+ * is within (n + 8) 2^-53 sum |term| of the exact sum of its terms for an fp32 handle ((n + 9) for fp64, whose products
+ * round). RAW MOMENTS ADD: the rows 0..28 of the blocks of a sharded job, or of a cell split over column blocks, sum to the
+ * undivided rows (score.py, combine_dispersions) -- which the order statistics do not.
+ * umpcBatchDispersionEllipsoids: one row of ell [count][G][UMPC_ELL_ROWS] DOUBLE per row of mom, fp64 throughout:
+ *   0, 1   n scored, skipped        2..7  mean m = S1 / n (NaN when n = 0)
+ *   8..28  covariance C = (S2 - S1 S1^T / n) / (n - 1), upper triangle in the order of mom
+ *  29..31  eigenvalues of the 3 x 3 position block C_pp, descending
+ *  32..40  V [3][3] row by row: COLUMN c is the eigenvector of eigenvalue c; its component of largest magnitude is positive
+ *          (ties: the lowest index). Cyclic Jacobi, pairs (0,1), (0,2), (1,2), 8 sweeps whatever the data.
+ *  41      status. 0: usable. 1: n < 2 -- rows 8..47 are NaN except this one. 2: C_pp is not positive definite: a pivot
+ *          of its Cholesky factorisation is <= 1e-12 trace(C_pp) (or NaN) -- rows 42..47 are NaN, the rest is filled.
+ *          A cell whose draws all start on one point has status 2 at its first steps: a normal case, not an error.
+ *  42..47  Linv, the inverse of the lower Cholesky factor of C_pp, its lower triangle row by row: (0,0) (1,0) (1,1) (2,0)
+ *          (2,1) (2,2). d2 = |Linv (d - m_p)|^2 is the squared Mahalanobis distance of a position error d.
+ * The covariance is formed from raw moments: its entries carry the summation error above amplified by about
+ * (|m|^2 + sigma^2) / sigma^2. Derived, not measured: fine while |m| / sigma stays below about 1e4 for an fp32 handle's
+ * tables and 1e3 for an fp64 handle's.
+ * umpcBatchMahalanobis: a per-robot score msc [UMPC_MAHA_ROWS][B] in the handle's dtype, in/out, over the steps of the call.
+ * ell covers exactly the steps first .. first + count - 1 of THIS call (row i = step first + i); group [B] is the array
+ * umpcBatchGroupIndex took. Per step a robot reads p and pdes (6 words) and the row of its own cell: d = p - pdes in the
+ * dtype, widened; d2 in fp64; rounded once to the dtype. The step is skipped when a word is not finite, the id is outside
+ * [0, G), or the row's status is not 0. Step i of the call carries the number k = step0 + i.
+ *   0  steps scored                 1  sum d2
+ *   2  max d2                       3  step of the maximum (the first on a tie), -1 when row 0 is 0
+ *   4  steps with d2 > limit        5, 6  first / last step over the limit, -1 if none
+ *   7  last d2                      8  steps skipped               9..11  0, reserved
+ * (`limit` is compared after rounding to the dtype.) Row 0 is the score's "enters when row 0 > 0", so
+ * umpcBatchScoreQuantiles and umpcBatchScoreBootstrap take this table unchanged (num = 1, den = 0: the mean d2; num = 2:
+ * the worst). umpcBatchMahalanobisInit writes the identity (rows 3, 5, 6 = -1, the others 0); a chunked run accumulates as
+ * umpcBatchScore does: rows 0, 2..8 do not depend on how a range is cut into calls, row 1 to rounding ((steps + 8) u).
+ * The covariance includes the robot itself, so d2 <= (n - 1)^2 / n: a limit above that never fires in a small cell.
+ * Not built: a 6 x 6 distance or eigen-decomposition; attitude components in z; leave-one-out distances and calibrated
+ * limits; bootstrap bands of covariance entries; a DPP fold; shifted or two-pass accumulation for |m| / sigma beyond the
+ * range above; combining across GPUs inside the library.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; a table pointer, order, offset, group, mom, ell or msc NULL; both
+ * or neither of ref_tab and ref; count, first, ref_first or step0 < 0; count > 2^31 - 1 (Mahalanobis: 2^31 - 17); G < 1;
+ * limit <= 0 or not finite; an fp32 handle with step0 + count > 2^24. count == 0 is a successful no-op. */
+#define UMPC_DISP_ROWS 32
+#define UMPC_ELL_ROWS 48
+#define UMPC_MAHA_ROWS 12
+int umpcBatchDispersion(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref,
+                        long long first, long long count, long long ref_first, int after,
+                        const int32_t *order, const int32_t *offset, int G, double *mom, void *stream);
+int umpcBatchDispersionEllipsoids(umpc_batch_t *h, const double *mom, long long count, int G, double *ell, void *stream);
+int umpcBatchMahalanobisInit(umpc_batch_t *h, void *msc, void *stream);
+int umpcBatchMahalanobis(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref,
+                         const double *ell, const int32_t *group, int G, long long first, long long count,
+                         long long ref_first, long long step0, int after, double limit, void *msc, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

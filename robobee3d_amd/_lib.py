@@ -27,6 +27,7 @@ TERM_EP, TERM_ES, TERM_TAU = 0, 1, 2
 BOOT_MEAN, BOOT_QUANTILE, BOOT_ROWS, BOOT_MAX_REPS = 0, 1, 5, 1 << 20
 BAND_ROWS, BAND_MAX_REPS = 6, 4096
 RSUM_ROWS, RESP_ROWS = 33, 12
+DISP_ROWS, ELL_ROWS, MAHA_ROWS = 32, 48, 12
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -39,6 +40,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchSetImpulses", "umpcBatchImpulseCursor", "umpcBatchScoreInit", "umpcBatchScore", "umpcBatchScoreGroups",
            "umpcBatchGroupIndex", "umpcBatchEnsemble", "umpcBatchEnsembleQuantiles", "umpcBatchScoreQuantiles", "umpcBatchScoreBootstrap",
            "umpcBatchEnsembleBootstrap", "umpcBatchResponseInit", "umpcBatchResponse", "umpcBatchResponseFit",
+           "umpcBatchDispersion", "umpcBatchDispersionEllipsoids", "umpcBatchMahalanobisInit", "umpcBatchMahalanobis",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -294,6 +296,12 @@ def lib():
         L.umpcBatchResponseInit.argtypes = [C.c_void_p] * 3
         L.umpcBatchResponse.argtypes = [C.c_void_p] * 5 + [C.c_longlong] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchResponseFit.argtypes = [C.c_void_p] * 4
+        L.umpcBatchDispersion.argtypes = [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p]
+        L.umpcBatchDispersionEllipsoids.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchMahalanobisInit.argtypes = [C.c_void_p] * 3
+        L.umpcBatchMahalanobis.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_longlong] * 4 + [C.c_int, C.c_double, C.c_void_p,
+                                           C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

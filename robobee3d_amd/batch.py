@@ -717,6 +717,81 @@ class BatchUprightMPC:
                 self._check(self.L.umpcBatchResponseFit(self.h, _ptr(sums), _ptr(resp), self._stream()))
         return resp, sums
 
+    def dispersion(self, index, first=0, count=None, after=False, ref_table=None, ref_first=0, out=None):
+        """The recorded steps first .. first + count - 1 of the step history as the raw moments of the error state
+        z = (p - pdes, v - dpdes) of each group [count, G, 32] float64 on the device (umpcBatchDispersion; rows:
+        robobee3d_amd/score.py -- members scored / skipped, S1 = sum z [6], S2 = sum z_i z_j [21], the upper triangle row by
+        row), in ONE pass over the tables: what dispersion_ellipsoids() turns into the mean, the covariance and the ellipsoid
+        of a cell's cloud at every step. index = group_index(group, G). first, count, after, ref_table, ref_first and out are
+        those of ensemble(), and the reference is resolved as there. A member is scored when p, v, pdes and dpdes are finite
+        (not ensemble()'s rule: v is read, s, out and the status are not). Every (step, group) row is independent and
+        bit-reproducible, and raw moments ADD: the rows of the blocks of a sharded job combine exactly in their counts and to
+        rounding in their sums (score.combine_dispersions). Keep the cells contiguous in the batch (cell = b // 64)."""
+        hist, first, count = self._history_window("dispersion", first, count)
+        order, offset, G = self._group_index_arg("dispersion", index)
+        reftab, rfirst = self._scoring_reference("dispersion", first, count, ref_table, ref_first)
+        out = self._out_arg(out, (count, G, _lib.DISP_ROWS))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchDispersion(self.h, _ptr(hist["state"]), _ptr(reftab),
+                                                   None if reftab is not None else _ptr(self.ref), first, count, rfirst,
+                                                   int(bool(after)), _ptr(order), _ptr(offset), G, _ptr(out), self._stream()))
+        return out
+
+    def dispersion_ellipsoids(self, mom, out=None):
+        """[count, G, 48] float64 from the moments [count, G, 32] of dispersion() (umpcBatchDispersionEllipsoids; rows:
+        robobee3d_amd/score.py -- n, skipped, the mean [6], the covariance [21] (upper triangle), the eigenvalues of its 3 x 3
+        position block descending, their eigenvectors as the columns of V [3, 3], the status (0 usable, 1 fewer than two
+        members, 2 the position block is not positive definite -- a cell whose draws start on one point) and Linv [6], the
+        inverse of the lower Cholesky factor of the position block: |Linv (d - m_p)|^2 is a squared Mahalanobis distance.
+        The k-sigma ellipsoid of a cell at a step has the semi-axes k sqrt(eigenvalue) along the columns of V. The
+        covariance comes from raw moments: fine while |mean| / sigma stays below about 1e4 (fp32 tables) or 1e3 (fp64)."""
+        if (mom.dim() != 3 or int(mom.shape[2]) != _lib.DISP_ROWS or mom.dtype != torch.float64 or mom.device != self.state.device
+                or not mom.is_contiguous()):
+            raise ValueError("mom must be a contiguous [count, G, 32] float64 tensor on the handle's device (dispersion())")
+        count, G = int(mom.shape[0]), int(mom.shape[1])
+        if G < 1:
+            raise ValueError("dispersion_ellipsoids: G >= 1")
+        out = self._out_arg(out, (count, G, _lib.ELL_ROWS))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchDispersionEllipsoids(self.h, _ptr(mom), count, G, _ptr(out), self._stream()))
+        return out
+
+    def mahalanobis(self, ell, group, G, first=0, count=None, limit=None, after=False, ref_table=None, ref_first=0, score=None,
+                    step0=None):
+        """How far every robot sits from its own cell's cloud over the recorded steps first .. first + count - 1: a score
+        [12, B] in the handle's dtype (umpcBatchMahalanobis; rows: robobee3d_amd/score.py -- steps scored, sum and max of
+        d2 = |Linv (d - m_p)|^2 with d = p - pdes, the step of the maximum, the steps with d2 > limit and the first / last of
+        them, the last d2, the steps skipped). ell [count, G, 48] = dispersion_ellipsoids() of exactly these steps; group [B]
+        is the array group_index() took (ids outside [0, G) are skipped). limit None = score.chi2_3_quantile(0.99), the 99 %
+        point of a Gaussian cloud in three dimensions; the covariance includes the robot itself, so d2 <= (n - 1)^2 / n and a
+        larger limit never fires in a small cell. first, count, after, ref_table, ref_first, score and step0 are those of
+        score(): passing a score back in accumulates a chunked run. Row 0 > 0 means "enters", as in score(): score_quantiles
+        and score_bootstrap take the table unchanged (num=1, den=0 or num=2). A draw that sits 5 sigma out in a direction
+        where its cell is tight is inside the isotropic tube of score() and shows here."""
+        from .score import chi2_3_quantile
+        hist, first, count = self._history_window("mahalanobis", first, count)
+        reftab, rfirst = self._scoring_reference("mahalanobis", first, count, ref_table, ref_first)
+        G = int(G)
+        group = torch.as_tensor(group).to(torch.int32).to(self.device).contiguous()
+        if tuple(group.shape) != (self.B,):
+            raise ValueError("group must be [%d]" % self.B)
+        if (tuple(ell.shape) != (count, G, _lib.ELL_ROWS) or ell.dtype != torch.float64 or ell.device != self.state.device
+                or not ell.is_contiguous()):
+            raise ValueError("ell must be a contiguous [%d, %d, 48] float64 tensor on the handle's device: the ellipsoids of "
+                             "exactly the steps asked for" % (count, G))
+        limit = chi2_3_quantile(0.99) if limit is None else float(limit)
+        with torch.cuda.device(self.device):
+            if score is None:
+                score = torch.empty((_lib.MAHA_ROWS, self.B), dtype=self.dtype, device=self.device)
+                self._check(self.L.umpcBatchMahalanobisInit(self.h, _ptr(score), self._stream()))
+            else:
+                self._score_arg("score", score)
+            self._check(self.L.umpcBatchMahalanobis(self.h, _ptr(hist["state"]), _ptr(reftab),
+                                                    None if reftab is not None else _ptr(self.ref), _ptr(ell), _ptr(group), G,
+                                                    first, count, rfirst, first if step0 is None else int(step0),
+                                                    int(bool(after)), limit, _ptr(score), self._stream()))
+        return score
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

@@ -1,6 +1,6 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchResponseFit) and their
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchMahalanobis) and their
 // host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
-// umpc_band.h and umpc_response.h: nothing here reads the step path or a generated header.
+// umpc_band.h, umpc_response.h and umpc_dispersion.h: nothing here reads the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -13,6 +13,7 @@
 #include "umpc_bootstrap.h" // bootstrap intervals of a per-group cost table (umpcBatchScoreBootstrap)
 #include "umpc_band.h"     // bootstrap bands of per-step, per-group curves (umpcBatchEnsembleBootstrap)
 #include "umpc_response.h" // per-robot sine fit at the robot's own frequency (umpcBatchResponse / umpcBatchResponseFit)
+#include "umpc_dispersion.h" // per-step, per-group moments, ellipsoids and Mahalanobis scores (umpcBatchDispersion ..)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -252,6 +253,33 @@ static int launch_response(umpc_batch_t *h, const ScoreWindow &w, const double *
   return launch_status("umpcBatchResponse");
 }
 
+// (w carries neither an out nor a status record: the kernel reads state rows 0..2, 12..14 and reference rows 0..5)
+template <typename T>
+static int launch_dispersion(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G, double *mom,
+                             void *stream) {
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, 0, nullptr);
+  umpc::DispArgs<T> a;
+  a.state = t.state; a.reftab = t.reftab; a.ref = t.ref; a.order = order; a.offset = offset; a.mom = mom;
+  a.B = t.B; a.count = t.count; a.G = G;
+  const dim3 grid((unsigned)G, step_slices(G, w.count, umpc::kDispWaves)), block(64, umpc::kDispWaves);
+  if (a.reftab) hipLaunchKernelGGL((umpc::umpc_dispersion_kernel<T, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((umpc::umpc_dispersion_kernel<T, false>), grid, block, 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchDispersion");
+}
+
+template <typename T>
+static int launch_mahalanobis(umpc_batch_t *h, const ScoreWindow &w, const double *ell, const int32_t *group, int G, long long step0,
+                              double limit, void *msc, void *stream) {
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, step0, nullptr);
+  umpc::MahaArgs<T> a;
+  a.state = t.state; a.reftab = t.reftab; a.ref = t.ref; a.ell = ell; a.group = group; a.msc = (T *)msc;
+  a.B = t.B; a.count = t.count; a.G = G; a.step0 = step0; a.limit = (T)limit;
+  const dim3 grid((unsigned)((h->B + 63) / 64)), block(64, umpc::kMahaSlices);
+  if (a.reftab) hipLaunchKernelGGL((umpc::umpc_mahalanobis_kernel<T, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((umpc::umpc_mahalanobis_kernel<T, false>), grid, block, 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchMahalanobis");
+}
+
 extern "C" {
 
 int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
@@ -412,6 +440,57 @@ int umpcBatchResponseFit(umpc_batch_t *h, const double *sums, void *resp, void *
   else
     hipLaunchKernelGGL(umpc::umpc_response_fit_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, sums, (double *)resp, h->B);
   return launch_status(fn);
+}
+int umpcBatchDispersion(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, long long first,
+                        long long count, long long ref_first, int after, const int32_t *order, const int32_t *offset, int G,
+                        double *mom, void *stream) {
+  const char *fn = "umpcBatchDispersion";
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !mom) return refuse(fn, "bad argument (state_hist, order, offset and mom must be given)");
+  if (check_window(fn, w) || check_groups(fn, G)) return -1;
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_dispersion<float>(h, w, order, offset, G, mom, stream)
+                              : launch_dispersion<double>(h, w, order, offset, G, mom, stream);
+}
+int umpcBatchDispersionEllipsoids(umpc_batch_t *h, const double *mom, long long count, int G, double *ell, void *stream) {
+  const char *fn = "umpcBatchDispersionEllipsoids";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!mom || !ell) return refuse(fn, "bad argument (mom and ell must be given)");
+  if (count < 0 || count > 0x7fffffffLL) return refuse(fn, "bad argument (0 <= count <= 2^31 - 1)");
+  if (check_groups(fn, G)) return -1;
+  if (count == 0) return 0;
+  const long long rows = count * G;
+  if ((rows + 255) / 256 > 0x7fffffffLL) return refuse(fn, "count x G too large for one call (2^39 rows at the most)");
+  hipLaunchKernelGGL(umpc::umpc_dispersion_ellipsoid_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     mom, rows, ell);
+  return launch_status(fn);
+}
+int umpcBatchMahalanobisInit(umpc_batch_t *h, void *msc, void *stream) {
+  const char *fn = "umpcBatchMahalanobisInit";
+  if (!h || !msc) return refuse(fn, "bad argument (h and msc must be given)");
+  const dim3 grid((unsigned)((h->B + 255) / 256));
+  if (h->dtype == UMPC_F32) hipLaunchKernelGGL(umpc::umpc_mahalanobis_init_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (float *)msc, h->B);
+  else hipLaunchKernelGGL(umpc::umpc_mahalanobis_init_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (double *)msc, h->B);
+  return launch_status(fn);
+}
+int umpcBatchMahalanobis(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, const double *ell,
+                         const int32_t *group, int G, long long first, long long count, long long ref_first, long long step0,
+                         int after, double limit, void *msc, void *stream) {
+  const char *fn = "umpcBatchMahalanobis";
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !ell || !group || !msc) return refuse(fn, "bad argument (state_hist, ell, group and msc must be given)");
+  if (check_window(fn, w) || check_groups(fn, G)) return -1;
+  if (step0 < 0) return refuse(fn, "bad argument (step0 >= 0)");
+  if (!(limit > 0) || !(limit <= 1.79769313486231570815e308)) return refuse(fn, "bad argument (limit must be finite and > 0)");
+  if (count > 0x7fffffffLL - 2 * umpc::kMahaSlices) return refuse(fn, "count too large for one call (2^31 - 17 steps at the most)");
+  // counts and step numbers are scalars of the dtype, as in umpcBatchScore
+  if (h->dtype == UMPC_F32 && step0 + count > (1LL << 24))
+    return refuse(fn, "step0 + count passes 2^24, the largest step number and count an fp32 score holds exactly (score in fp64, or in parts)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_mahalanobis<float>(h, w, ell, group, G, step0, limit, msc, stream)
+                              : launch_mahalanobis<double>(h, w, ell, group, G, step0, limit, msc, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,9 @@ numpy fp64 mirrors. The device path is BatchUprightMPC.score / score_groups (bat
 the mirrors are the definition the kernels are tested against, not a fallback. The same holds for the ensemble rows of
 umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble) and for the order statistics of
 umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles), the bootstrap of
-umpcBatchScoreBootstrap (score_bootstrap) and the bootstrap bands of umpcBatchEnsembleBootstrap (ensemble_bootstrap) further down.
+umpcBatchScoreBootstrap (score_bootstrap) and the bootstrap bands of umpcBatchEnsembleBootstrap (ensemble_bootstrap) further down,
+and for the moments, ellipsoids and Mahalanobis scores of umpcBatchDispersion / umpcBatchDispersionEllipsoids /
+umpcBatchMahalanobis (dispersion / dispersion_ellipsoids / mahalanobis) at the end.
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -699,3 +701,242 @@ def response_fit_reference(sums):
             o[RESP_STEPS, ~fit] = 0.0
             o[RESP_SKIPPED] = sm[RSUM_SKIPPED]
     return resp
+
+
+# ---- dispersion ellipsoids (umpcBatchDispersion / umpcBatchDispersionEllipsoids / umpcBatchMahalanobis) ------------------------
+DISP_ROWS, ELL_ROWS, MAHA_ROWS = 32, 48, 12
+# moment rows, per (step, group): members scored / skipped, S1 = sum z [6], S2 = sum z_i z_j [21] (upper triangle row by row)
+D_N, D_SKIPPED, D_S1, D_S2 = 0, 1, 2, 8
+DISP_PAIRS = tuple((i, j) for i in range(6) for j in range(i, 6))      # the (i, j) of S2 entry k, and of covariance entry k
+DISP_PP = (0, 1, 2, 6, 7, 11)                                          # the entries of the 3 x 3 position block: 00 01 02 11 12 22
+# ellipsoid rows: n, skipped, mean [6], covariance [21], eigenvalues of C_pp descending [3], V [3, 3] row by row (column c =
+# eigenvector c), status, Linv [6] (lower triangle row by row: 00 10 11 20 21 22)
+L_N, L_SKIPPED, L_MEAN, L_COV, L_EIGVAL, L_EIGVEC, L_STATUS, L_LINV = 0, 1, 2, 8, 29, 32, 41, 42
+ELL_OK, ELL_FEW, ELL_NOT_PD = 0, 1, 2
+ELL_SWEEPS = 8              # cyclic Jacobi sweeps of the 3 x 3 block, fixed
+ELL_PIVOT_TOL = 1e-12       # a Cholesky pivot fails when it is <= ELL_PIVOT_TOL * trace(C_pp)
+# Mahalanobis score rows, per robot
+(M_STEPS, M_SUM_D2, M_MAX_D2, M_STEP_MAX, M_OVER, M_FIRST_OVER, M_LAST_OVER, M_LAST_D2, M_SKIPPED) = range(9)
+MAHA_ROW_NAMES = ("steps", "sum_d2", "max_d2", "step_max", "over", "first_over", "last_over", "last_d2", "skipped", "", "", "")
+
+
+def _error_state(y, r, dtype):
+    """(ok [B], z [6, B] float64): z = (p - pdes, v - dpdes) of one step, each difference formed in `dtype` with one rounding
+    and then widened; ok: all 12 words are finite"""
+    y, r = np.asarray(y, dtype), np.asarray(r, dtype)
+    a, b = np.concatenate([y[0:3], y[12:15]]), r[0:6]
+    with np.errstate(invalid="ignore", over="ignore"):
+        z = (a - b).astype(np.float64)
+    return np.isfinite(a).all(0) & np.isfinite(b).all(0), z
+
+
+def dispersion_reference(state_hist, ref, first, count, ref_first, after, order, offset, dtype=np.float64):
+    """umpcBatchDispersion in numpy, IN THE DEVICE'S ORDER OF SUMMATION: [count, G, 32] float64. The tables, first, count,
+    ref_first and after are those of ensemble_reference (no out, no status); dtype is the handle's: the differences are
+    formed in it, everything after is float64. Per (step, group) row, lane l of 64 starts at +0 and adds the terms of members
+    l, l + 64, .. of the list in order (+0 for a member that is not scored); then for w = 32, 16, .., 1 lane l becomes
+    (lane l) + (lane l ^ w). Elementwise IEEE additions in that order: the kernel's bits (the kernel evaluates this tree for the
+    one lane that stores the entry)."""
+    st = np.asarray(state_hist)
+    ref = np.asarray(ref)
+    order, offset = np.asarray(order), np.asarray(offset)
+    first, count, ref_first, after = int(first), int(count), int(ref_first), int(bool(after))
+    G = len(offset) - 1
+    if count < 0 or first < 0 or ref_first < 0 or G < 1:
+        raise ValueError("dispersion_reference: bad argument")
+    mom = np.zeros((count, G, DISP_ROWS))
+    lanes = np.arange(64)
+    for i in range(count):
+        ok, z = _error_state(st[first + i + after], ref[ref_first + i] if ref.ndim == 3 else ref, dtype)
+        z = np.where(ok, z, 0.0)
+        with np.errstate(over="ignore", invalid="ignore"):
+            terms = np.concatenate([z, np.stack([z[a] * z[b] for a, b in DISP_PAIRS])])       # [27, B]
+        for g in range(G):
+            mem = order[offset[g]:offset[g + 1]]
+            part = np.zeros((27, 64))
+            for m0 in range(0, len(mem), 64):
+                t = terms[:, mem[m0:m0 + 64]]
+                part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
+            with np.errstate(over="ignore", invalid="ignore"):
+                for w in (32, 16, 8, 4, 2, 1):
+                    part = part + part[:, lanes ^ w]
+            scored = int(ok[mem].sum())
+            mom[i, g, D_N], mom[i, g, D_SKIPPED] = scored, len(mem) - scored
+            mom[i, g, D_S1:D_S1 + 27] = part[:, 0]
+    return mom
+
+
+def combine_dispersions(parts):
+    """The moments of a whole job from the moments [count, G, 32] of its blocks of robots, or of the column blocks a cell is
+    split over: raw moments add, so rows 0..28 are sums (counts exactly; S1 and S2 to the rounding of one more addition per
+    part) -- what order statistics cannot do. numpy arrays or torch tensors; the result is of the first part's kind and the
+    parts are not modified. dispersion_ellipsoids / ellipsoid_reference of the result is the ellipsoid of the whole cell."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_dispersions: no parts")
+    total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
+    for p in parts[1:]:
+        total[..., :D_S2 + 21] = total[..., :D_S2 + 21] + p[..., :D_S2 + 21]
+    return total
+
+
+def _jacobi_rotate(app, aqq, apq, arp, arq, vp, vq):
+    """one rotation of ell_rotate (csrc/umpc_dispersion.h), elementwise over arrays, same operations in the same order"""
+    theta = (aqq - app) / (2.0 * apq)
+    t = np.copysign(1.0, theta) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+    t = np.where(apq != 0.0, t, 0.0)
+    c = 1.0 / np.sqrt(t * t + 1.0)
+    s = t * c
+    app, aqq = app - t * apq, aqq + t * apq
+    arp, arq = c * arp - s * arq, s * arp + c * arq
+    vp, vq = c * vp - s * vq, s * vp + c * vq
+    return app, aqq, np.zeros_like(apq), arp, arq, vp, vq
+
+
+def ellipsoid_reference(mom):
+    """umpcBatchDispersionEllipsoids in numpy fp64, in the kernel's operation order: [.., 48] from the moments [.., 32]. Mean
+    S1 / n; covariance (S2 - S1 S1^T / n) / (n - 1); the 3 x 3 position block by cyclic Jacobi, pairs (0,1), (0,2), (1,2),
+    ELL_SWEEPS sweeps whatever the data; eigenvalues descending, eigenvectors the columns of V with the component of largest
+    magnitude positive (ties: the lowest index); status ELL_FEW when n < 2 (rows 8..47 NaN but the status), ELL_NOT_PD when a
+    Cholesky pivot of the position block is <= ELL_PIVOT_TOL * trace or NaN (rows 42..47 NaN); Linv = inverse of the lower
+    Cholesky factor."""
+    mom = np.asarray(mom, np.float64)
+    if mom.shape[-1] != DISP_ROWS:
+        raise ValueError("ellipsoid_reference: mom must be [.., 32]")
+    ell = np.full(mom.shape[:-1] + (ELL_ROWS,), np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        n = mom[..., D_N]
+        s1 = [mom[..., D_S1 + j] for j in range(6)]
+        ell[..., L_N], ell[..., L_SKIPPED] = n, mom[..., D_SKIPPED]
+        for j in range(6):
+            ell[..., L_MEAN + j] = s1[j] / n
+        few = ~(n >= 2.0)
+        c = [(mom[..., D_S2 + k] - s1[i] * s1[j] / n) / (n - 1.0) for k, (i, j) in enumerate(DISP_PAIRS)]
+        for k in range(21):
+            ell[..., L_COV + k] = c[k]
+        c00, c01, c02, c11, c12, c22 = (c[k] for k in DISP_PP)
+        a00, a01, a02, a11, a12, a22 = c00, c01, c02, c11, c12, c22
+        one, zero = np.ones_like(n), np.zeros_like(n)
+        v = [np.stack([one, zero, zero]), np.stack([zero, one, zero]), np.stack([zero, zero, one])]     # v[c][k]: column c
+        for _ in range(ELL_SWEEPS):
+            a00, a11, a01, a02, a12, v[0], v[1] = _jacobi_rotate(a00, a11, a01, a02, a12, v[0], v[1])
+            a00, a22, a02, a01, a12, v[0], v[2] = _jacobi_rotate(a00, a22, a02, a01, a12, v[0], v[2])
+            a11, a22, a12, a01, a02, v[1], v[2] = _jacobi_rotate(a11, a22, a12, a01, a02, v[1], v[2])
+        lam = [a00, a11, a22]
+        for i, j in ((0, 1), (1, 2), (0, 1)):
+            sw = lam[i] < lam[j]
+            lam[i], lam[j] = np.where(sw, lam[j], lam[i]), np.where(sw, lam[i], lam[j])
+            v[i], v[j] = np.where(sw, v[j], v[i]), np.where(sw, v[i], v[j])
+        for cidx in range(3):
+            big = v[cidx][0]
+            big = np.where(np.abs(v[cidx][1]) > np.abs(big), v[cidx][1], big)
+            big = np.where(np.abs(v[cidx][2]) > np.abs(big), v[cidx][2], big)
+            v[cidx] = np.where(big < 0.0, -v[cidx], v[cidx])
+            ell[..., L_EIGVAL + cidx] = lam[cidx]
+            for k in range(3):
+                ell[..., L_EIGVEC + 3 * k + cidx] = v[cidx][k]
+        floor = ELL_PIVOT_TOL * ((c00 + c11) + c22)
+        l00 = np.sqrt(c00)
+        l10, l20 = c01 / l00, c02 / l00
+        p1 = c11 - l10 * l10
+        l11 = np.sqrt(p1)
+        l21 = (c12 - l20 * l10) / l11
+        p2 = (c22 - l20 * l20) - l21 * l21
+        l22 = np.sqrt(p2)
+        bad = ~(c00 > floor) | ~(p1 > floor) | ~(p2 > floor)
+        i00, i11, i22 = 1.0 / l00, 1.0 / l11, 1.0 / l22
+        i10, i21 = -(l10 * i00) * i11, -(l21 * i11) * i22
+        i20 = -(l20 * i00 + l21 * i10) * i22
+        for k, x in enumerate((i00, i10, i11, i20, i21, i22)):
+            ell[..., L_LINV + k] = np.where(few | bad, np.nan, x)
+        ell[..., L_COV:L_STATUS][few] = np.nan
+        ell[..., L_STATUS] = np.where(few, ELL_FEW, np.where(bad, ELL_NOT_PD, ELL_OK))
+    return ell
+
+
+def mahalanobis_terms(state_hist, ref, ell, group, G, first, count, ref_first, after, dtype=np.float64):
+    """(ok [count, B], d2 [count, B], A [count, B]) of umpcBatchMahalanobis: per step and robot whether the step is scored
+    (p and pdes finite, the id inside [0, G), the row's status 0), d2 = |Linv (d - m_p)|^2 with d = p - pdes formed in `dtype`
+    and widened, evaluated in float64 in the kernel's operation order and rounded once to `dtype` (returned as float64), and
+    A = (sum_jk |Linv_jk| |d_k - m_k|)^2, the scale of d2's own rounding error. d2 and A are 0 where the step is not scored."""
+    st, ref, ell = np.asarray(state_hist), np.asarray(ref), np.asarray(ell, np.float64)
+    group, G = np.asarray(group), int(G)
+    first, count, ref_first, after = int(first), int(count), int(ref_first), int(bool(after))
+    B = st.shape[-1]
+    gok = (group >= 0) & (group < G)
+    gc = np.where(gok, group, 0)
+    ok, d2, A = np.zeros((count, B), bool), np.zeros((count, B)), np.zeros((count, B))
+    for i in range(count):
+        y = np.asarray(st[first + i + after][0:3], dtype)
+        r = np.asarray((ref[ref_first + i] if ref.ndim == 3 else ref)[0:3], dtype)
+        row = ell[i][gc]                                   # [B, 48]
+        with np.errstate(invalid="ignore", over="ignore"):
+            e = (y - r).astype(np.float64) - row[:, L_MEAN:L_MEAN + 3].T
+            li = row[:, L_LINV:L_LINV + 6].T
+            y0, y1, y2 = li[0] * e[0], li[1] * e[0] + li[2] * e[1], (li[3] * e[0] + li[4] * e[1]) + li[5] * e[2]
+            v = ((y0 * y0 + y1 * y1) + y2 * y2).astype(dtype).astype(np.float64)
+            ae = np.abs(e)
+            a = (np.abs(li[0]) * ae[0] + np.abs(li[1]) * ae[0] + np.abs(li[2]) * ae[1] + np.abs(li[3]) * ae[0] + np.abs(li[4]) * ae[1]
+                 + np.abs(li[5]) * ae[2]) ** 2
+        ok[i] = gok & (row[:, L_STATUS] == ELL_OK) & np.isfinite(y).all(0) & np.isfinite(r).all(0)
+        d2[i], A[i] = np.where(ok[i], v, 0.0), np.where(ok[i], a, 0.0)
+    return ok, d2, A
+
+
+def mahalanobis_identity(B, dtype=np.float64):
+    """The score no step has entered (umpcBatchMahalanobisInit): rows 3, 5 and 6 = -1, all others 0."""
+    s = np.zeros((MAHA_ROWS, int(B)), dtype)
+    s[M_STEP_MAX] = s[M_FIRST_OVER] = s[M_LAST_OVER] = -1
+    return s
+
+
+def mahalanobis_reference(state_hist, ref, ell, group, G, first, count, ref_first, step0, after, limit, dtype=np.float64, score=None):
+    """umpcBatchMahalanobis in numpy, step by step in order: the score [12, B] float64 (rows M_*) of the steps first ..
+    first + count - 1 against the ellipsoids ell [count, G, 48] of exactly those steps; step i carries the number step0 + i;
+    `limit` is compared after rounding to `dtype`, as d2 is. Passing a score back in accumulates. The sum row is summed in
+    float64 in step order: the mirror has no slices."""
+    if not (limit > 0 and np.isfinite(limit)) or int(count) < 0 or int(first) < 0 or int(ref_first) < 0 or int(step0) < 0 or int(G) < 1:
+        raise ValueError("mahalanobis_reference: bad argument")
+    ok, d2, _ = mahalanobis_terms(state_hist, ref, ell, group, G, first, count, ref_first, after, dtype)
+    B = ok.shape[1]
+    sc = mahalanobis_identity(B) if score is None else np.array(score, np.float64)
+    lim = float(np.asarray(limit, dtype))
+    for i in range(int(count)):
+        k, o, v = int(step0) + i, ok[i], d2[i]
+        sc[M_SKIPPED] += ~o
+        sc[M_STEPS] += o
+        sc[M_SUM_D2, o] += v[o]
+        take = o & ((sc[M_STEP_MAX] < 0) | (v > sc[M_MAX_D2]) | ((v == sc[M_MAX_D2]) & (k < sc[M_STEP_MAX])))
+        sc[M_MAX_D2, take], sc[M_STEP_MAX, take] = v[take], k
+        sc[M_LAST_D2, o] = v[o]
+        over = o & (v > lim)
+        sc[M_OVER] += over
+        sc[M_FIRST_OVER, over] = np.where(sc[M_FIRST_OVER, over] < 0, k, np.minimum(sc[M_FIRST_OVER, over], k))
+        sc[M_LAST_OVER, over] = np.maximum(sc[M_LAST_OVER, over], k)
+    return sc
+
+
+def chi2_3_cdf(x):
+    """P(chi^2 with 3 degrees of freedom <= x) in closed form: erf(sqrt(x / 2)) - sqrt(2 x / pi) exp(-x / 2)"""
+    x = float(x)
+    return 0.0 if x <= 0 else math.erf(math.sqrt(0.5 * x)) - math.sqrt(2.0 * x / math.pi) * math.exp(-0.5 * x)
+
+
+def chi2_3_quantile(p):
+    """The x with chi2_3_cdf(x) = p, by bisection (no scipy): the squared Mahalanobis radius that holds a share p of a Gaussian
+    cloud in three dimensions -- chi2_3_quantile(0.99) = 11.345 is a `limit` for BatchUprightMPC.mahalanobis. 0 <= p < 1."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("chi2_3_quantile: 0 <= p < 1")
+    if p == 0.0:
+        return 0.0
+    lo, hi = 0.0, 1.0
+    while chi2_3_cdf(hi) < p:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if chi2_3_cdf(mid) < p:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
