@@ -668,6 +668,55 @@ int umpcBatchMahalanobis(umpc_batch_t *h, const void *state_hist, const void *re
                          const double *ell, const int32_t *group, int G, long long first, long long count,
                          long long ref_first, long long step0, int after, double limit, void *msc, void *stream);
 
+/* Error propagators: what relates the cloud of a group at step k to its cloud at step k + L. Every table above looks at one
+ * step at a time; these two calls give the cross moments of the error state z = (p - pdes, v - dpdes) between two steps and
+ * the affine map z_b ~ Phi z_a + c they determine -- the closed-loop dynamics of a gain cell as its Monte-Carlo draws show
+ * them: poles and decay rate (eigenvalues of Phi, on the host: robobee3d_amd/score.py propagator_poles), how much of the
+ * spread at k + L the linear model leaves unexplained (Q, r2), and growth, the mean squared amplification in the cloud's
+ * own metric.
+ *
+ * umpcBatchLagMoments takes the tables, the window and the group index of umpcBatchDispersion and a lag L >= 1. Row i of
+ * xmom [count][G][UMPC_XMOM_ROWS] DOUBLE pairs slice a (state first + after + i, reference ref_first + i) with slice b
+ * (state first + after + i + L, reference ref_first + i + L; a constant `ref` serves both): THE TABLES MUST HOLD
+ * count + L SLICES from the first one. A member is scored when all 24 words -- p, v, pdes, dpdes at a and at b, the rows
+ * umpcBatchDispersion reads -- are finite; differences in the handle's dtype with one rounding, every product and sum fp64.
+ *   row  0        n, the members scored
+ *        1        members skipped (some word at a or at b is not finite)
+ *        2..7     S1a = sum z_a          8..13   S1b = sum z_b
+ *        14..34   S2a = sum z_a,i z_a,j, i <= j, upper triangle row by row (the order of umpcBatchDispersion's S2)
+ *        35..55   S2b likewise
+ *        56..91   Sba[i][j] = sum z_b,i z_a,j, row-major 6 x 6
+ *        92..95   +0
+ * The order of summation of a row is umpcBatchDispersion's (lane partials in member order, then the butterfly w = 32 .. 1):
+ * a function of the group's member list and L alone, bit-reproducible; on tables where no member is skipped rows 2..7 and
+ * 14..34 are the bits of umpcBatchDispersion's row of step k, rows 8..13 and 35..55 those of step k + L. Raw moments add
+ * across the blocks of a sharded job (score.py combine_lag_moments). No atomics, no temporaries.
+ *
+ * umpcBatchPropagators: one row of prop [count][G][UMPC_PROP_ROWS] DOUBLE per row of xmom, fp64 throughout. With the means
+ * m = S1 / n and the covariances C_a, C_b, C_ba formed from the raw moments as umpcBatchDispersionEllipsoids forms C,
+ * C_a = L_a L_a^T (Cholesky): Phi = C_ba C_a^-1, c = m_b - Phi m_a, Q = C_b - Phi C_ba^T.
+ *   row  0, 1     n, skipped (copied)
+ *        2        status: 0 usable; 1 n < 8 (one more member than the seven coefficients of a row of the fit); 2 a pivot of
+ *                 the Cholesky factorisation of C_a is <= 1e-10 x C_a[j][j] or NaN (the cloud at a is flat in a direction)
+ *        3, 4     r2_p = 1 - (Q00 + Q11 + Q22) / (Cb00 + Cb11 + Cb22), r2_v likewise on the velocity block; NaN where
+ *                 the denominator is 0
+ *        5        growth = |L_a^-1 Phi L_a|_F^2 / 6; below 1: the cloud contracts on average over L steps
+ *        6, 7     0
+ *        8..43    Phi, row-major 6 x 6
+ *        44..49   c
+ *        50..70   Q, upper triangle row by row
+ *        71..79   0
+ * With status != 0 rows 3..5 and 8..70 are NaN. No eigen-solver on the device: the poles are host work.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; a table pointer, order, offset, xmom or prop NULL; both or neither
+ * of ref_tab and ref; count, first or ref_first < 0; count > 2^31 - 1; G < 1; lag < 1 or lag > 2^20. count == 0 is a
+ * successful no-op. */
+#define UMPC_XMOM_ROWS 96
+#define UMPC_PROP_ROWS 80
+int umpcBatchLagMoments(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref,
+                        long long first, long long count, long long ref_first, int after, int lag,
+                        const int32_t *order, const int32_t *offset, int G, double *xmom, void *stream);
+int umpcBatchPropagators(umpc_batch_t *h, const double *xmom, long long count, int G, double *prop, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

@@ -28,6 +28,7 @@ BOOT_MEAN, BOOT_QUANTILE, BOOT_ROWS, BOOT_MAX_REPS = 0, 1, 5, 1 << 20
 BAND_ROWS, BAND_MAX_REPS = 6, 4096
 RSUM_ROWS, RESP_ROWS = 33, 12
 DISP_ROWS, ELL_ROWS, MAHA_ROWS = 32, 48, 12
+XMOM_ROWS, PROP_ROWS = 96, 80
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -41,6 +42,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchGroupIndex", "umpcBatchEnsemble", "umpcBatchEnsembleQuantiles", "umpcBatchScoreQuantiles", "umpcBatchScoreBootstrap",
            "umpcBatchEnsembleBootstrap", "umpcBatchResponseInit", "umpcBatchResponse", "umpcBatchResponseFit",
            "umpcBatchDispersion", "umpcBatchDispersionEllipsoids", "umpcBatchMahalanobisInit", "umpcBatchMahalanobis",
+           "umpcBatchLagMoments", "umpcBatchPropagators",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -302,6 +304,9 @@ def lib():
         L.umpcBatchMahalanobisInit.argtypes = [C.c_void_p] * 3
         L.umpcBatchMahalanobis.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_longlong] * 4 + [C.c_int, C.c_double, C.c_void_p,
                                            C.c_void_p]
+        L.umpcBatchLagMoments.argtypes = [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p]
+        L.umpcBatchPropagators.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

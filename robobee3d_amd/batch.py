@@ -792,6 +792,55 @@ class BatchUprightMPC:
                                                     int(bool(after)), limit, _ptr(score), self._stream()))
         return score
 
+    def lag_moments(self, index, lag=1, first=0, count=None, after=False, ref_table=None, ref_first=0, out=None):
+        """The recorded steps first .. first + count - 1 of the step history, each PAIRED WITH THE STEP `lag` LATER, as the raw
+        cross moments of the error state z = (p - pdes, v - dpdes) of each group [count, G, 96] float64 on the device
+        (umpcBatchLagMoments; rows: robobee3d_amd/score.py X_* -- members scored / skipped, S1 and S2 of step k (a) and of
+        step k + lag (b) as dispersion() gives them, and Sba = sum z_b z_a^T [6, 6]), in ONE pass over the tables: what
+        propagators() turns into the linear map that carries a draw's deviation at step k to its deviation at step k + lag.
+        count None = up to the history cursor minus lag: the steps [first, first + count + lag) must be recorded, and the
+        reference table must cover them. index, after, ref_table, ref_first and out are those of dispersion(), and the
+        reference is resolved as there. A member is scored when p, v, pdes and dpdes are finite at BOTH steps. Every (step,
+        group) row is independent and bit-reproducible, and raw moments add across the blocks of a sharded job
+        (score.combine_lag_moments). Keep the cells contiguous in the batch (cell = b // 64)."""
+        from .score import LAG_MAX
+        lag = int(lag)
+        if not 1 <= lag <= LAG_MAX:
+            raise ValueError("lag_moments: 1 <= lag <= %d" % LAG_MAX)
+        if count is None:
+            count = self.history_cursor - int(first) - lag
+        hist, first, span = self._history_window("lag_moments", first, int(count) + lag if int(count) >= 0 else -1)
+        count = span - lag
+        order, offset, G = self._group_index_arg("lag_moments", index)
+        reftab, rfirst = self._scoring_reference("lag_moments", first, span, ref_table, ref_first)
+        out = self._out_arg(out, (count, G, _lib.XMOM_ROWS))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchLagMoments(self.h, _ptr(hist["state"]), _ptr(reftab),
+                                                   None if reftab is not None else _ptr(self.ref), first, count, rfirst,
+                                                   int(bool(after)), lag, _ptr(order), _ptr(offset), G, _ptr(out), self._stream()))
+        return out
+
+    def propagators(self, xmom, out=None):
+        """[count, G, 80] float64 from the lag moments [count, G, 96] of lag_moments() (umpcBatchPropagators; rows:
+        robobee3d_amd/score.py P_* -- n, skipped, the status (0 usable, 1 fewer than eight members, 2 the cloud at step k is
+        flat in some direction), r2 of the position and of the velocity block, growth, Phi [6, 6], c [6] and Q [21], upper
+        triangle): the affine model z_{k + lag} ~ Phi z_k + c of the cell's draws, the closed-loop dynamics of that cell as
+        the data show them. Q is the covariance the model leaves unexplained -- nonlinearity, saturation, unsolved steps --
+        and r2 = 1 - trace(Q) / trace(C_b) per block the share it explains; growth = |L_a^-1 Phi L_a|_F^2 / 6 is the mean
+        squared amplification in the cloud's own metric (below 1: the cloud contracts on average). The ellipsoid at k + lag
+        predicted from the one at k is Phi C_a Phi^T + Q around Phi m_a + c. The poles are host work:
+        score.propagator_poles(prop.cpu().numpy(), lag)."""
+        if (xmom.dim() != 3 or int(xmom.shape[2]) != _lib.XMOM_ROWS or xmom.dtype != torch.float64 or xmom.device != self.state.device
+                or not xmom.is_contiguous()):
+            raise ValueError("xmom must be a contiguous [count, G, 96] float64 tensor on the handle's device (lag_moments())")
+        count, G = int(xmom.shape[0]), int(xmom.shape[1])
+        if G < 1:
+            raise ValueError("propagators: G >= 1")
+        out = self._out_arg(out, (count, G, _lib.PROP_ROWS))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchPropagators(self.h, _ptr(xmom), count, G, _ptr(out), self._stream()))
+        return out
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

@@ -1,6 +1,6 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchMahalanobis) and their
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchPropagators) and their
 // host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
-// umpc_band.h, umpc_response.h and umpc_dispersion.h: nothing here reads the step path or a generated header.
+// umpc_band.h, umpc_response.h, umpc_dispersion.h and umpc_propagator.h: nothing here reads the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -14,6 +14,7 @@
 #include "umpc_band.h"     // bootstrap bands of per-step, per-group curves (umpcBatchEnsembleBootstrap)
 #include "umpc_response.h" // per-robot sine fit at the robot's own frequency (umpcBatchResponse / umpcBatchResponseFit)
 #include "umpc_dispersion.h" // per-step, per-group moments, ellipsoids and Mahalanobis scores (umpcBatchDispersion ..)
+#include "umpc_propagator.h" // per-step, per-group lagged moments and the affine map between two steps (umpcBatchLagMoments ..)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -267,6 +268,21 @@ static int launch_dispersion(umpc_batch_t *h, const ScoreWindow &w, const int32_
   return launch_status("umpcBatchDispersion");
 }
 
+// (the window of launch_dispersion; the tables hold w.count + lag slices from their first)
+template <typename T>
+static int launch_lag_moments(umpc_batch_t *h, const ScoreWindow &w, int lag, const int32_t *order, const int32_t *offset, int G,
+                              double *xmom, void *stream) {
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, 0, nullptr);
+  umpc::LagArgs<T> a;
+  a.t.state = t.state; a.t.reftab = t.reftab; a.t.ref = t.ref; a.t.order = order; a.t.offset = offset; a.t.mom = xmom;
+  a.t.B = t.B; a.t.count = t.count; a.t.G = G; a.lag = lag;
+  // (one row per wavefront and trip: as many slices as there are rows for a block's wavefronts, at the most)
+  const dim3 grid((unsigned)G, step_slices(G, 2 * w.count, umpc::kLagWaves)), block(64, umpc::kLagWaves);
+  if (a.t.reftab) hipLaunchKernelGGL((umpc::umpc_lagmom_kernel<T, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((umpc::umpc_lagmom_kernel<T, false>), grid, block, 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchLagMoments");
+}
+
 template <typename T>
 static int launch_mahalanobis(umpc_batch_t *h, const ScoreWindow &w, const double *ell, const int32_t *group, int G, long long step0,
                               double limit, void *msc, void *stream) {
@@ -491,6 +507,32 @@ int umpcBatchMahalanobis(umpc_batch_t *h, const void *state_hist, const void *re
   if (count == 0) return 0;
   return h->dtype == UMPC_F32 ? launch_mahalanobis<float>(h, w, ell, group, G, step0, limit, msc, stream)
                               : launch_mahalanobis<double>(h, w, ell, group, G, step0, limit, msc, stream);
+}
+int umpcBatchLagMoments(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, long long first,
+                        long long count, long long ref_first, int after, int lag, const int32_t *order, const int32_t *offset, int G,
+                        double *xmom, void *stream) {
+  const char *fn = "umpcBatchLagMoments";
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !xmom) return refuse(fn, "bad argument (state_hist, order, offset and xmom must be given)");
+  if (check_window(fn, w) || check_groups(fn, G)) return -1;
+  if (lag < 1 || lag > (1 << 20)) return refuse(fn, "bad argument (1 <= lag <= 2^20)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_lag_moments<float>(h, w, lag, order, offset, G, xmom, stream)
+                              : launch_lag_moments<double>(h, w, lag, order, offset, G, xmom, stream);
+}
+int umpcBatchPropagators(umpc_batch_t *h, const double *xmom, long long count, int G, double *prop, void *stream) {
+  const char *fn = "umpcBatchPropagators";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!xmom || !prop) return refuse(fn, "bad argument (xmom and prop must be given)");
+  if (count < 0 || count > 0x7fffffffLL) return refuse(fn, "bad argument (0 <= count <= 2^31 - 1)");
+  if (check_groups(fn, G)) return -1;
+  if (count == 0) return 0;
+  const long long rows = count * G, blocks = (rows + umpc::kPropBlock - 1) / umpc::kPropBlock;
+  if (blocks > 0x7fffffffLL) return refuse(fn, "count x G too large for one call (2^39 rows at the most)");
+  hipLaunchKernelGGL(umpc::umpc_propagator_kernel, dim3((unsigned)blocks), dim3(umpc::kPropBlock), 0, (hipStream_t)stream, xmom, rows,
+                     prop);
+  return launch_status(fn);
 }
 
 }  // extern "C"

@@ -940,3 +940,185 @@ def chi2_3_quantile(p):
         else:
             hi = mid
     return 0.5 * (lo + hi)
+
+
+# ---- error propagators (umpcBatchLagMoments / umpcBatchPropagators) ---------------------------------------------------------
+XMOM_ROWS, PROP_ROWS = 96, 80
+# lag-moment rows, per (step, group): members scored / skipped, S1a = sum z_a [6], S1b = sum z_b [6], S2a and S2b [21] (upper
+# triangles in DISP_PAIRS order), Sba[i][j] = sum z_b,i z_a,j [36] row-major; a = step k, b = step k + lag
+X_N, X_SKIPPED, X_S1A, X_S1B, X_S2A, X_S2B, X_SBA, X_END = 0, 1, 2, 8, 14, 35, 56, 92
+# propagator rows: n, skipped, status, r2 of the position and of the velocity block, growth, Phi [6, 6] row-major, c [6],
+# Q [21] (upper triangle in DISP_PAIRS order)
+P_N, P_SKIPPED, P_STATUS, P_R2_P, P_R2_V, P_GROWTH, P_PHI, P_C, P_Q, P_END = 0, 1, 2, 3, 4, 5, 8, 44, 50, 71
+PROP_OK, PROP_FEW, PROP_NOT_PD = 0, 1, 2
+PROP_MIN_MEMBERS = 8        # one more than the seven coefficients of a row of the fit z_b,i ~ Phi[i] z_a + c_i
+PROP_PIVOT_TOL = 1e-10      # a Cholesky pivot of C_a fails when it is <= PROP_PIVOT_TOL * C_a[j][j]
+LAG_MAX = 1 << 20
+
+
+def lag_moments_reference(state_hist, ref, first, count, ref_first, after, lag, order, offset, dtype=np.float64):
+    """umpcBatchLagMoments in numpy, IN THE DEVICE'S ORDER OF SUMMATION: [count, G, 96] float64. Row i pairs state slice
+    first + after + i (a) with first + after + i + lag (b), reference slice ref_first + i with ref_first + i + lag (a constant
+    reference [9, B] serves both). A member is scored when all 24 words are finite (_error_state's rule at a and at b); the
+    order of a row is dispersion_reference's: lane l of 64 starts at +0 and adds the terms of members l, l + 64, .. in order,
+    then for w = 32, 16, .., 1 lane l becomes (lane l) + (lane l ^ w)."""
+    st = np.asarray(state_hist)
+    ref = np.asarray(ref)
+    order, offset = np.asarray(order), np.asarray(offset)
+    first, count, ref_first, after, lag = int(first), int(count), int(ref_first), int(bool(after)), int(lag)
+    G = len(offset) - 1
+    if count < 0 or first < 0 or ref_first < 0 or G < 1 or not 1 <= lag <= LAG_MAX:
+        raise ValueError("lag_moments_reference: bad argument")
+    xmom = np.zeros((count, G, XMOM_ROWS))
+    lanes = np.arange(64)
+    nt = X_END - X_S1A
+    for i in range(count):
+        oka, za = _error_state(st[first + i + after], ref[ref_first + i] if ref.ndim == 3 else ref, dtype)
+        okb, zb = _error_state(st[first + i + after + lag], ref[ref_first + i + lag] if ref.ndim == 3 else ref, dtype)
+        ok = oka & okb
+        za, zb = np.where(ok, za, 0.0), np.where(ok, zb, 0.0)
+        with np.errstate(over="ignore", invalid="ignore"):
+            terms = np.concatenate([za, zb, np.stack([za[a] * za[b] for a, b in DISP_PAIRS]),
+                                    np.stack([zb[a] * zb[b] for a, b in DISP_PAIRS]),
+                                    np.stack([zb[a] * za[b] for a in range(6) for b in range(6)])])       # [90, B]
+        for g in range(G):
+            mem = order[offset[g]:offset[g + 1]]
+            part = np.zeros((nt, 64))
+            for m0 in range(0, len(mem), 64):
+                t = terms[:, mem[m0:m0 + 64]]
+                part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
+            with np.errstate(over="ignore", invalid="ignore"):
+                for w in (32, 16, 8, 4, 2, 1):
+                    part = part + part[:, lanes ^ w]
+            scored = int(ok[mem].sum())
+            xmom[i, g, X_N], xmom[i, g, X_SKIPPED] = scored, len(mem) - scored
+            xmom[i, g, X_S1A:X_END] = part[:, 0]
+    return xmom
+
+
+def combine_lag_moments(parts):
+    """The lag moments of a whole job from the moments [count, G, 96] of its blocks of robots, or of the column blocks a cell
+    is split over, all at the same lag: raw moments add, so rows 0..91 are sums (counts exactly; the others to the rounding of
+    one more addition per part), as in combine_dispersions. numpy arrays or torch tensors; the result is of the first part's
+    kind and the parts are not modified. propagators() / propagator_reference of the result is the map of the whole cell."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_lag_moments: no parts")
+    total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
+    for p in parts[1:]:
+        total[..., :X_END] = total[..., :X_END] + p[..., :X_END]
+    return total
+
+
+def _pair(i, j):
+    """the entry of an upper triangle in DISP_PAIRS order that holds (i, j) or (j, i)"""
+    i, j = min(i, j), max(i, j)
+    return i * 6 - i * (i - 1) // 2 + (j - i)
+
+
+def propagator_reference(xmom):
+    """umpcBatchPropagators in numpy fp64, THE DEFINITION OF THE KERNEL'S OPERATION ORDER: [.., 80] from the lag moments
+    [.., 96]. m_a = S1a / n, m_b = S1b / n; every covariance entry (S - S1_i S1_j / n) / (n - 1) as ellipsoid_reference forms
+    it. C_a = L L^T row by row (s = C_a[j][j]; s -= L[j][k]^2, k ascending; pivot_j = s; L[j][j] = sqrt(s); L[i][j] =
+    (C_a[i][j] - sum_k L[i][k] L[j][k]) / L[j][j]); Y = L^-1 C_ba^T and W = L^-1 Y^T by forward substitution column by column,
+    growth = sum W^2 / 6 row by row; X = L^-T Y by back substitution (k = i + 1 .. 5 ascending), Phi = X^T = C_ba C_a^-1;
+    c = m_b - Phi m_a; Q = C_b - Phi C_ba^T; r2 = 1 - trace(Q block) / trace(C_b block), NaN where that trace is 0. Status
+    PROP_FEW when n < 8, PROP_NOT_PD when a pivot is <= PROP_PIVOT_TOL * C_a[j][j] or NaN; then rows 3..5 and 8..70 are NaN.
+    The affine model is z_b ~ Phi z_a + c and Q the covariance it leaves unexplained."""
+    xmom = np.asarray(xmom, np.float64)
+    if xmom.shape[-1] != XMOM_ROWS:
+        raise ValueError("propagator_reference: xmom must be [.., 96]")
+    prop = np.zeros(xmom.shape[:-1] + (PROP_ROWS,))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        n = xmom[..., X_N]
+        n1 = n - 1.0
+        few = ~(n >= float(PROP_MIN_MEMBERS))
+        s1a = [xmom[..., X_S1A + j] for j in range(6)]
+        s1b = [xmom[..., X_S1B + j] for j in range(6)]
+        ma, mb = [s / n for s in s1a], [s / n for s in s1b]
+        ca = [(xmom[..., X_S2A + k] - s1a[i] * s1a[j] / n) / n1 for k, (i, j) in enumerate(DISP_PAIRS)]
+        cb = [(xmom[..., X_S2B + k] - s1b[i] * s1b[j] / n) / n1 for k, (i, j) in enumerate(DISP_PAIRS)]
+        cba = [[(xmom[..., X_SBA + 6 * i + j] - s1b[i] * s1a[j] / n) / n1 for j in range(6)] for i in range(6)]
+        L = [[None] * 6 for _ in range(6)]
+        bad = np.zeros(n.shape, bool)
+        for j in range(6):
+            s = ca[_pair(j, j)]
+            for k in range(j):
+                s = s - L[j][k] * L[j][k]
+            bad = bad | ~(s > PROP_PIVOT_TOL * ca[_pair(j, j)])
+            L[j][j] = np.sqrt(s)
+            for i in range(j + 1, 6):
+                t = ca[_pair(j, i)]
+                for k in range(j):
+                    t = t - L[i][k] * L[j][k]
+                L[i][j] = t / L[j][j]
+        y = [[None] * 6 for _ in range(6)]
+        w = [[None] * 6 for _ in range(6)]
+        for c in range(6):
+            for i in range(6):
+                s = cba[c][i]
+                for k in range(i):
+                    s = s - L[i][k] * y[k][c]
+                y[i][c] = s / L[i][i]
+        for c in range(6):
+            for i in range(6):
+                s = y[c][i]
+                for k in range(i):
+                    s = s - L[i][k] * w[k][c]
+                w[i][c] = s / L[i][i]
+        gsum = np.zeros_like(n)
+        for i in range(6):
+            for c in range(6):
+                gsum = gsum + w[i][c] * w[i][c]
+        growth = gsum / 6.0
+        for c in range(6):
+            for i in range(5, -1, -1):
+                s = y[i][c]
+                for k in range(i + 1, 6):
+                    s = s - L[k][i] * y[k][c]
+                y[i][c] = s / L[i][i]
+        phi = [[y[j][i] for j in range(6)] for i in range(6)]
+        prop[..., P_N], prop[..., P_SKIPPED] = n, xmom[..., X_SKIPPED]
+        prop[..., P_STATUS] = np.where(few, PROP_FEW, np.where(bad, PROP_NOT_PD, PROP_OK))
+        prop[..., P_GROWTH] = growth
+        for i in range(6):
+            s = mb[i]
+            for j in range(6):
+                prop[..., P_PHI + 6 * i + j] = phi[i][j]
+                s = s - phi[i][j] * ma[j]
+            prop[..., P_C + i] = s
+        q = []
+        for k, (i, j) in enumerate(DISP_PAIRS):
+            s = cb[k]
+            for t in range(6):
+                s = s - phi[i][t] * cba[j][t]
+            q.append(s)
+            prop[..., P_Q + k] = s
+        for row, blk in ((P_R2_P, (0, 1, 2)), (P_R2_V, (3, 4, 5))):
+            d = [_pair(t, t) for t in blk]
+            den = (cb[d[0]] + cb[d[1]]) + cb[d[2]]
+            prop[..., row] = np.where(den == 0.0, np.nan, 1.0 - ((q[d[0]] + q[d[1]]) + q[d[2]]) / den)
+        none = few | bad
+        prop[..., P_R2_P:P_GROWTH + 1][none] = np.nan
+        prop[..., P_PHI:P_END][none] = np.nan
+    return prop
+
+
+def propagator_poles(prop, lag=1):
+    """The poles of each usable row of prop [count, G, 80] (propagators() downloaded, or propagator_reference): [count, G, 6]
+    complex, numpy.linalg.eigvals of Phi, and for lag > 1 the principal lag-th root of each (Phi carries a deviation over
+    `lag` steps, so its eigenvalues are the lag-th powers of the per-step poles; which of the lag roots the plant has is not in
+    the data: the principal one is right while a pole turns less than half a revolution in `lag` steps). NaN where the status
+    is not PROP_OK. The decay rate per step of a mode is log|lambda| (negative: it contracts; the slowest mode is the largest)
+    and its frequency angle(lambda) / (2 pi) cycles per step. No order is imposed on the six. CPU only: eigenvalues of a
+    6 x 6 non-symmetric matrix are not hot-path work."""
+    prop = np.asarray(prop, np.float64)
+    lag = int(lag)
+    if prop.ndim != 3 or prop.shape[-1] != PROP_ROWS or lag < 1:
+        raise ValueError("propagator_poles: prop must be [count, G, 80] and lag >= 1")
+    poles = np.full(prop.shape[:2] + (6,), np.nan + 0j, np.complex128)
+    use = prop[..., P_STATUS] == PROP_OK
+    if use.any():
+        lam = np.linalg.eigvals(prop[..., P_PHI:P_C][use].reshape(-1, 6, 6)).astype(np.complex128)
+        poles[use] = lam if lag == 1 else np.abs(lam) ** (1.0 / lag) * np.exp(1j * np.angle(lam) / lag)
+    return poles
