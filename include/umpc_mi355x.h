@@ -717,6 +717,73 @@ int umpcBatchLagMoments(umpc_batch_t *h, const void *state_hist, const void *ref
                         const int32_t *order, const int32_t *offset, int G, double *xmom, void *stream);
 int umpcBatchPropagators(umpc_batch_t *h, const double *xmom, long long count, int G, double *prop, void *stream);
 
+/* Sensitivity indices: which of the inputs DRAWN for a sweep explains the error of a cell. The user drew per-robot inputs --
+ * initial offset and tilt per axis, push size, direction and time, a task parameter, a weight --; the first-order index
+ * (correlation ratio) of input j is eta2_j = Var(E[y | x_j]) / Var(y), the share of a cell's error variance that goes away
+ * when x_j is known. The estimator is the given-data, binned one: the range of a factor is cut into M bins of equal count
+ * inside the cell, by rank, and eta2 = SSB / SST, the between-bin sum of squares over the total. The error terms are even
+ * functions of a signed offset, so the linear fit of umpcBatchPropagators finds a coefficient of 0 where eta2 is 1. All four
+ * calls are pure functions of their arguments, asynchronous on `stream`, and allocate nothing; from the handle they take B and
+ * the dtype (umpcBatchSensitivity also taulim). 1 <= F <= UMPC_SENS_MAX_FACTORS, 2 <= M <= UMPC_SENS_MAX_BINS.
+ *
+ * umpcBatchFactorBins, once per sweep: factors [F][B] in the handle's dtype, order / offset / G a group index
+ * (umpcBatchGroupIndex), bins [F][B] int32 OVERWRITTEN. For every group and factor the members with a finite value are
+ * ranked by value with <, ties broken by position in the member list (-0 and +0 are equal): numpy.argsort(kind="stable").
+ * bin = (rank * M) / n_f in integers, n_f the members of the group with a finite value. A value that is not finite gets -1,
+ * and so does every robot outside every group. Integers only and exact. n^2 comparisons per (group, factor): meant for
+ * cells of tens to thousands. `bins` may as well be written by hand: a categorical factor is its own bin.
+ *
+ * umpcBatchSensitivity: the tables, the window, the reference (exactly ONE of ref_tab / ref), the group index and `term` are
+ * exactly those of umpcBatchEnsembleQuantiles. The value y of a member is formed in the handle's dtype by the expressions of
+ * umpcBatchScore and widened; y^2 and every sum are fp64. A member is scored at a step when umpcBatchEnsembleQuantiles with
+ * the same out_hist scores it AND all F of its bins lie in [0, M); it is skipped otherwise. sens [count][G][4 + 2 F M] is
+ * DOUBLE and OVERWRITTEN; row i belongs to step first + i and rows are independent (chunked runs write disjoint slices):
+ *   0  n scored          1  skipped          2  S1 = sum y          3  S2 = sum y^2
+ *   4 + f M + m          N_fm, the scored members of bin m of factor f (sum_m N_fm = n for every f)
+ *   4 + F M + f M + m    S_fm = sum y over them
+ * Order of summation: umpcBatchDispersion's -- lane l of a wavefront starts at +0 and adds the terms of members l, l + 64, ..
+ * in list order (+0 for a member that is not scored or not in the bin), then for w = 32, 16, 8, 4, 2, 1 every lane l replaces
+ * its value by (value of l) + (value of l ^ w). A row is a function of the member list and the bins alone: the same bits
+ * every time, no atomics, no temporaries (score.py, sensitivity_reference, follows it operation by operation). Rows 0 and 1
+ * with valid bins are rows 0 and 1 of umpcBatchEnsemble. RAW SUMS ADD across the blocks of a sharded job when the bins were
+ * assigned on the whole job (score.py, combine_sensitivities).
+ *
+ * umpcBatchSensitivityIndices: one row of idx [count][G][8 + F (4 + M)] DOUBLE per row of sens, fp64 throughout:
+ *   0  n      1  skipped      2  status      3  mean = S1 / n      4  variance = SST / (n - 1)
+ *   5  SST = S2 - S1 S1 / n   6, 7  0
+ *   per factor f at 8 + f (4 + M):
+ *     +0  eta2 = SSB / SST, SSB = sum over the non-empty bins, m ascending, of S_fm S_fm / N_fm, minus S1 S1 / n
+ *     +1  eps2 = 1 - (1 - eta2)(n - 1) / (n - M_f), the bias-adjusted index (with no effect E eta2 ~ (M_f - 1) / (n - 1))
+ *     +2  F = (SSB / (M_f - 1)) / ((SST - SSB) / (n - M_f))
+ *     +3  M_f, the non-empty bins
+ *     +4 .. +3 + M  the bin means S_fm / N_fm, the main-effect curve E[y | bin]; NaN for an empty bin
+ * status 1: n < 2 M. status 2: !(SST > 0), or S1 or S2 is not finite. With either, +0 .. +2 of every factor are NaN (the
+ * other rows are filled as the formulas give them). A factor with M_f < 2 or n <= M_f has NaN in +0 .. +2. Nothing is
+ * clamped: rounding may put eta2 a hair outside [0, 1]. SST comes from raw moments: eta2 carries the summation error
+ * amplified by about S2 / SST.
+ *
+ * umpcBatchScoreSensitivity: the same sums over one column of a per-robot score [UMPC_SCORE_ROWS][B] in the handle's dtype,
+ * sens [G][4 + 2 F M]. The value of robot b is that of umpcBatchScoreQuantiles (score[num][b], or score[num][b] /
+ * score[den][b] in double; den = -1: no division); it enters when row 0 > 0, the value is finite and all F bins lie in
+ * [0, M). umpcBatchSensitivityIndices takes the result with count = 1.
+ * Not built: total-effect or interaction indices (two-factor bins); a permutation null on the device; p-values.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; a table pointer, factors, order, offset, bins, sens or idx NULL; both
+ * or neither of ref_tab and ref; count, first or ref_first < 0; count > 2^31 - 1; G < 1; F outside 1..6 or M outside 2..8;
+ * term outside 0..2; UMPC_TERM_TAU without out_hist; num outside 0..11, den outside -1..11. count == 0 is a successful
+ * no-op. */
+#define UMPC_SENS_MAX_FACTORS 6
+#define UMPC_SENS_MAX_BINS 8
+int umpcBatchFactorBins(umpc_batch_t *h, const void *factors, int F, const int32_t *order, const int32_t *offset, int G,
+                        int M, int32_t *bins, void *stream);
+int umpcBatchSensitivity(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab,
+                         const void *ref, long long first, long long count, long long ref_first, int after,
+                         const int32_t *order, const int32_t *offset, int G, int term, const int32_t *bins, int F, int M,
+                         double *sens, void *stream);
+int umpcBatchSensitivityIndices(umpc_batch_t *h, const double *sens, long long count, int G, int F, int M, double *idx,
+                                void *stream);
+int umpcBatchScoreSensitivity(umpc_batch_t *h, const void *score, const int32_t *order, const int32_t *offset, int G,
+                              int num, int den, const int32_t *bins, int F, int M, double *sens, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

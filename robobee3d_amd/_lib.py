@@ -29,6 +29,7 @@ BAND_ROWS, BAND_MAX_REPS = 6, 4096
 RSUM_ROWS, RESP_ROWS = 33, 12
 DISP_ROWS, ELL_ROWS, MAHA_ROWS = 32, 48, 12
 XMOM_ROWS, PROP_ROWS = 96, 80
+SENS_MAX_FACTORS, SENS_MAX_BINS = 6, 8
 NX, NC, NADATA = 45, 39, 48
 
 # every symbol include/umpc_mi355x.h declares
@@ -43,6 +44,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchEnsembleBootstrap", "umpcBatchResponseInit", "umpcBatchResponse", "umpcBatchResponseFit",
            "umpcBatchDispersion", "umpcBatchDispersionEllipsoids", "umpcBatchMahalanobisInit", "umpcBatchMahalanobis",
            "umpcBatchLagMoments", "umpcBatchPropagators",
+           "umpcBatchFactorBins", "umpcBatchSensitivity", "umpcBatchSensitivityIndices", "umpcBatchScoreSensitivity",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -307,6 +309,12 @@ def lib():
         L.umpcBatchLagMoments.argtypes = [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p]
         L.umpcBatchPropagators.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchFactorBins.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchSensitivity.argtypes = [C.c_void_p] * 5 + [C.c_longlong] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchSensitivityIndices.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchScoreSensitivity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

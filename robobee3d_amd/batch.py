@@ -841,6 +841,109 @@ class BatchUprightMPC:
             self._check(self.L.umpcBatchPropagators(self.h, _ptr(xmom), count, G, _ptr(out), self._stream()))
         return out
 
+    def _bins_arg(self, what, bins, nbins):
+        from .score import SENS_MAX_BINS, SENS_MAX_FACTORS
+        M = int(nbins)
+        if (bins.dim() != 2 or int(bins.shape[1]) != self.B or bins.dtype != torch.int32 or bins.device != self.state.device
+                or not bins.is_contiguous()):
+            raise ValueError("%s: bins must be a contiguous [F, %d] int32 tensor on the handle's device (factor_bins())" % (what, self.B))
+        F = int(bins.shape[0])
+        if not 1 <= F <= SENS_MAX_FACTORS or not 2 <= M <= SENS_MAX_BINS:
+            raise ValueError("%s: 1 to %d factors, 2 to %d bins" % (what, SENS_MAX_FACTORS, SENS_MAX_BINS))
+        return F, M
+
+    def factor_bins(self, factors, index, nbins=8):
+        """bins [F, B] int32 on the device (umpcBatchFactorBins), once per sweep: each of the F drawn inputs `factors` [F, B] --
+        initial offsets, tilts, push sizes, a task parameter, a weight: whatever the sweep drew per robot -- cut into `nbins`
+        bins of equal count INSIDE each cell of index = group_index(group, G), by rank (numpy.argsort(kind="stable") over the
+        cell's member list; bin = rank * nbins // finite members). -1 for a value that is not finite and for a robot outside
+        every group. What sensitivity() and score_sensitivity() take. A categorical factor (a push direction index) is its own
+        bin: write that row by hand. 1 to 6 factors, 2 to 8 bins."""
+        from .score import SENS_MAX_BINS, SENS_MAX_FACTORS
+        order, offset, G = self._group_index_arg("factor_bins", index)
+        factors = torch.as_tensor(factors).to(self.dtype).to(self.device).contiguous()
+        if factors.dim() == 1:
+            factors = factors[None]
+        F, M = int(factors.shape[0]), int(nbins)
+        if factors.dim() != 2 or int(factors.shape[1]) != self.B:
+            raise ValueError("factors must be [F, %d]" % self.B)
+        if not 1 <= F <= SENS_MAX_FACTORS or not 2 <= M <= SENS_MAX_BINS:
+            raise ValueError("factor_bins: 1 to %d factors, 2 to %d bins" % (SENS_MAX_FACTORS, SENS_MAX_BINS))
+        bins = torch.empty((F, self.B), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchFactorBins(self.h, _ptr(factors), F, _ptr(order), _ptr(offset), G, M, _ptr(bins), self._stream()))
+        return bins
+
+    def sensitivity(self, index, bins, nbins, term="ep", first=0, count=None, after=False, ref_table=None, ref_first=0, out=None):
+        """The recorded steps first .. first + count - 1 of the step history as the binned sums of a term over the drawn inputs
+        [count, G, 4 + 2 F nbins] float64 on the device (umpcBatchSensitivity; rows: robobee3d_amd/score.py S_* -- members
+        scored / skipped, S1 = sum y, S2 = sum y^2, then per factor f and bin m the scored members N_fm and S_fm = sum y over
+        them), in ONE pass over the tables: what sensitivity_indices() turns into the share of a cell's error variance that
+        each drawn input explains. bins = factor_bins(factors, index, nbins) (or written by hand); term, index, first, count,
+        after, ref_table, ref_first and out are those of ensemble_quantiles(), and the reference is resolved as there. A member
+        is scored when ensemble_quantiles() scores it and all its bins lie in [0, nbins). Every (step, group) row is independent
+        and bit-reproducible, and raw sums ADD across the blocks of a sharded job when the bins were assigned on the whole job
+        (score.combine_sensitivities). Keep the cells contiguous in the batch (cell = b // 64)."""
+        from .score import TERM_NAMES, sens_cols
+        hist, first, count = self._history_window("sensitivity", first, count)
+        order, offset, G = self._group_index_arg("sensitivity", index)
+        F, M = self._bins_arg("sensitivity", bins, nbins)
+        if term not in TERM_NAMES:
+            raise ValueError("sensitivity: term is one of %s" % (TERM_NAMES,))
+        if term == "tau" and hist["out"] is None:
+            raise RuntimeError("sensitivity: term 'tau' needs the out record of the step history")
+        reftab, rfirst = self._scoring_reference("sensitivity", first, count, ref_table, ref_first)
+        out = self._out_arg(out, (count, G, sens_cols(F, M)))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchSensitivity(self.h, _ptr(hist["state"]), _ptr(hist["out"]), _ptr(reftab),
+                                                    None if reftab is not None else _ptr(self.ref), first, count, rfirst,
+                                                    int(bool(after)), _ptr(order), _ptr(offset), G, TERM_NAMES.index(term),
+                                                    _ptr(bins), F, M, _ptr(out), self._stream()))
+        return out
+
+    def sensitivity_indices(self, sens, F, nbins, out=None):
+        """[count, G, 8 + F (4 + nbins)] float64 from the sums [count, G, 4 + 2 F nbins] of sensitivity(), or [G, ..] from the
+        [G, ..] of score_sensitivity() (umpcBatchSensitivityIndices; rows: robobee3d_amd/score.py I_* -- n, skipped, the
+        status (0 usable, 1 fewer than 2 nbins members, 2 the term does not vary in the cell), mean, variance and SST of the
+        term, then per factor eta2 = SSB / SST, the correlation ratio: the share of the cell's variance that goes away when
+        that input is known; eps2, the same adjusted for the (M_f - 1) / (n - 1) that eta2 shows with no effect at all; the
+        one-way ANOVA F; the non-empty bins M_f; and the bin means, the main-effect curve E[y | bin]). First-order indices:
+        they need not add up to 1, the rest is interaction and noise. Nothing is clamped."""
+        from .score import SENS_MAX_BINS, SENS_MAX_FACTORS, sens_cols, sens_index_cols
+        F, M = int(F), int(nbins)
+        if not 1 <= F <= SENS_MAX_FACTORS or not 2 <= M <= SENS_MAX_BINS:
+            raise ValueError("sensitivity_indices: 1 to %d factors, 2 to %d bins" % (SENS_MAX_FACTORS, SENS_MAX_BINS))
+        if (sens.dim() not in (2, 3) or int(sens.shape[-1]) != sens_cols(F, M) or sens.dtype != torch.float64
+                or sens.device != self.state.device or not sens.is_contiguous()):
+            raise ValueError("sens must be a contiguous [count, G, %d] (or [G, %d]) float64 tensor on the handle's device "
+                             "(sensitivity(), score_sensitivity())" % (sens_cols(F, M), sens_cols(F, M)))
+        flat = sens.dim() == 2
+        count, G = (1, int(sens.shape[0])) if flat else (int(sens.shape[0]), int(sens.shape[1]))
+        if G < 1:
+            raise ValueError("sensitivity_indices: G >= 1")
+        if flat and out is not None:
+            out = out[None]
+        out = self._out_arg(out, (count, G, sens_index_cols(F, M)))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchSensitivityIndices(self.h, _ptr(sens), count, G, F, M, _ptr(out), self._stream()))
+        return out[0] if flat else out
+
+    def score_sensitivity(self, score, index, bins, nbins, num, den=None):
+        """[G, 4 + 2 F nbins] float64: the sums of sensitivity() over one column of a per-robot score over the robots of each
+        group (umpcBatchScoreSensitivity). The value of robot b is that of score_quantiles() (score[num, b], or score[num, b] /
+        score[den, b] in double: num = 1, den = 0 is the per-robot mean tracking error); it enters when its row 0 > 0, the
+        value is finite and all its bins lie in [0, nbins). sensitivity_indices(result, F, nbins) says which drawn input
+        explains the spread of a cell's cost."""
+        from .score import sens_cols
+        order, offset, G = self._group_index_arg("score_sensitivity", index)
+        self._score_arg("score", score)
+        F, M = self._bins_arg("score_sensitivity", bins, nbins)
+        sens = torch.empty((G, sens_cols(F, M)), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchScoreSensitivity(self.h, _ptr(score), _ptr(order), _ptr(offset), G, int(num),
+                                                         -1 if den is None else int(den), _ptr(bins), F, M, _ptr(sens), self._stream()))
+        return sens
+
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device
         at the fire times t_ms + k * nsub * dtsim (umpcBatchTaskTable; t_ms None = the handle's clock). tasks: a name of

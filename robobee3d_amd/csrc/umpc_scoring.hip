@@ -1,6 +1,7 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchPropagators) and their
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchScoreSensitivity) and their
 // host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
-// umpc_band.h, umpc_response.h, umpc_dispersion.h and umpc_propagator.h: nothing here reads the step path or a generated header.
+// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h and umpc_sensitivity.h: nothing here reads the step path or a
+// generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -15,6 +16,7 @@
 #include "umpc_response.h" // per-robot sine fit at the robot's own frequency (umpcBatchResponse / umpcBatchResponseFit)
 #include "umpc_dispersion.h" // per-step, per-group moments, ellipsoids and Mahalanobis scores (umpcBatchDispersion ..)
 #include "umpc_propagator.h" // per-step, per-group lagged moments and the affine map between two steps (umpcBatchLagMoments ..)
+#include "umpc_sensitivity.h" // per-step, per-group binned sums over the drawn inputs and their correlation ratios (umpcBatchSensitivity ..)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -87,6 +89,9 @@ static int check_probs(const char *fn, const double *probs, int nq) {
   bool ok = nq >= 1 && nq <= UMPC_QUANT_MAX_PROBS;
   for (int j = 0; ok && j < nq; ++j) ok = probs[j] >= 0.0 && probs[j] <= 1.0;
   return ok ? 0 : refuse(fn, "bad argument (1 to 8 probabilities, each in [0, 1])");
+}
+static int check_factors(const char *fn, int F, int M) {
+  return F < 1 || F > UMPC_SENS_MAX_FACTORS || M < 2 || M > UMPC_SENS_MAX_BINS ? refuse(fn, "bad argument (1 <= F <= 6 factors, 2 <= M <= 8 bins)") : 0;
 }
 static int check_rows(const char *fn, int num, int den) {
   return num < 0 || num >= UMPC_SCORE_ROWS || den < -1 || den >= UMPC_SCORE_ROWS ? refuse(fn, "bad argument (num in 0..11, den in -1..11)") : 0;
@@ -294,6 +299,52 @@ static int launch_mahalanobis(umpc_batch_t *h, const ScoreWindow &w, const doubl
   if (a.reftab) hipLaunchKernelGGL((umpc::umpc_mahalanobis_kernel<T, true>), grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((umpc::umpc_mahalanobis_kernel<T, false>), grid, block, 0, (hipStream_t)stream, a);
   return launch_status("umpcBatchMahalanobis");
+}
+
+// one block per (group, factor) and one row of blocks for the robots outside every group
+template <typename T>
+static int launch_factor_bins(umpc_batch_t *h, const void *factors, int F, const int32_t *order, const int32_t *offset, int G, int M,
+                              int32_t *bins, void *stream) {
+  umpc::BinArgs<T> a;
+  a.factors = (const T *)factors; a.order = order; a.offset = offset; a.bins = bins;
+  a.B = h->B; a.G = G; a.M = M;
+  hipLaunchKernelGGL(umpc::umpc_factor_bins_kernel<T>, dim3((unsigned)G + 1u, (unsigned)F), dim3(umpc::kBinThreads), 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchFactorBins");
+}
+
+// (w carries no status record and there is no tube, as in launch_ens_quantiles; F <= 3 runs the form with 26 sums per lane)
+template <typename T>
+static int launch_sensitivity(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G, int term,
+                              const int32_t *bins, int F, int M, double *sens, void *stream) {
+  umpc::SensArgs<T> e;
+  e.t = score_args<T>(h, w, 0.0, 0, nullptr);
+  e.order = order; e.offset = offset; e.bins = bins; e.sens = sens;
+  e.G = G; e.F = F; e.M = M; e.term = term;
+  // (one row per wavefront and trip, as in launch_lag_moments)
+  const dim3 grid((unsigned)G, step_slices(G, 2 * w.count, umpc::kSensWaves)), block(64, umpc::kSensWaves);
+  const int form = (F > 3 ? 4 : 0) | (w.ref_tab ? 2 : 0) | (w.out_hist ? 1 : 0);
+#define UMPC_SENS_FORM(f)                                                                                               \
+  case f:                                                                                                               \
+    hipLaunchKernelGGL((umpc::umpc_sensitivity_kernel<T, ((f) & 2) != 0, ((f) & 1) != 0, ((f) & 4) ? 6 : 3>), grid, block, 0, \
+                       (hipStream_t)stream, e);                                                                         \
+    break;
+  switch (form) {
+    UMPC_SENS_FORM(0) UMPC_SENS_FORM(1) UMPC_SENS_FORM(2) UMPC_SENS_FORM(3) UMPC_SENS_FORM(4) UMPC_SENS_FORM(5)
+    UMPC_SENS_FORM(6) UMPC_SENS_FORM(7)
+  }
+#undef UMPC_SENS_FORM
+  return launch_status("umpcBatchSensitivity");
+}
+
+template <typename T>
+static int launch_score_sensitivity(umpc_batch_t *h, const void *score, const int32_t *order, const int32_t *offset, int G, int num,
+                                    int den, const int32_t *bins, int F, int M, double *sens, void *stream) {
+  umpc::ScoreSensArgs<T> e;
+  e.score = (const T *)score; e.order = order; e.offset = offset; e.bins = bins; e.sens = sens;
+  e.B = h->B; e.num = num; e.den = den; e.F = F; e.M = M;
+  if (F > 3) hipLaunchKernelGGL((umpc::umpc_score_sensitivity_kernel<T, 6>), dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream, e);
+  else hipLaunchKernelGGL((umpc::umpc_score_sensitivity_kernel<T, 3>), dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream, e);
+  return launch_status("umpcBatchScoreSensitivity");
 }
 
 extern "C" {
@@ -533,6 +584,52 @@ int umpcBatchPropagators(umpc_batch_t *h, const double *xmom, long long count, i
   hipLaunchKernelGGL(umpc::umpc_propagator_kernel, dim3((unsigned)blocks), dim3(umpc::kPropBlock), 0, (hipStream_t)stream, xmom, rows,
                      prop);
   return launch_status(fn);
+}
+
+int umpcBatchFactorBins(umpc_batch_t *h, const void *factors, int F, const int32_t *order, const int32_t *offset, int G, int M,
+                        int32_t *bins, void *stream) {
+  const char *fn = "umpcBatchFactorBins";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!factors || !order || !offset || !bins) return refuse(fn, "bad argument (factors, order, offset and bins must be given)");
+  if (check_groups(fn, G) || check_factors(fn, F, M)) return -1;
+  return h->dtype == UMPC_F32 ? launch_factor_bins<float>(h, factors, F, order, offset, G, M, bins, stream)
+                              : launch_factor_bins<double>(h, factors, F, order, offset, G, M, bins, stream);
+}
+int umpcBatchSensitivity(umpc_batch_t *h, const void *state_hist, const void *out_hist, const void *ref_tab, const void *ref,
+                         long long first, long long count, long long ref_first, int after, const int32_t *order,
+                         const int32_t *offset, int G, int term, const int32_t *bins, int F, int M, double *sens, void *stream) {
+  const char *fn = "umpcBatchSensitivity";
+  const ScoreWindow w = {state_hist, out_hist, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !bins || !sens) return refuse(fn, "bad argument (state_hist, order, offset, bins and sens must be given)");
+  if (check_window(fn, w) || check_groups(fn, G) || check_factors(fn, F, M)) return -1;
+  if (term < UMPC_TERM_EP || term > UMPC_TERM_TAU) return refuse(fn, "bad argument (term is UMPC_TERM_EP, UMPC_TERM_ES or UMPC_TERM_TAU)");
+  if (term == UMPC_TERM_TAU && !out_hist) return refuse(fn, "UMPC_TERM_TAU needs out_hist (the moments are read from it)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_sensitivity<float>(h, w, order, offset, G, term, bins, F, M, sens, stream)
+                              : launch_sensitivity<double>(h, w, order, offset, G, term, bins, F, M, sens, stream);
+}
+int umpcBatchSensitivityIndices(umpc_batch_t *h, const double *sens, long long count, int G, int F, int M, double *idx, void *stream) {
+  const char *fn = "umpcBatchSensitivityIndices";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!sens || !idx) return refuse(fn, "bad argument (sens and idx must be given)");
+  if (count < 0 || count > 0x7fffffffLL) return refuse(fn, "bad argument (0 <= count <= 2^31 - 1)");
+  if (check_groups(fn, G) || check_factors(fn, F, M)) return -1;
+  if (count == 0) return 0;
+  const long long rows = count * G, blocks = (rows + umpc::kSensIdxBlock - 1) / umpc::kSensIdxBlock;
+  if (blocks > 0x7fffffffLL) return refuse(fn, "count x G too large for one call (2^39 rows at the most)");
+  hipLaunchKernelGGL(umpc::umpc_sensitivity_indices_kernel, dim3((unsigned)blocks), dim3(umpc::kSensIdxBlock), 0, (hipStream_t)stream,
+                     sens, rows, F, M, idx);
+  return launch_status(fn);
+}
+int umpcBatchScoreSensitivity(umpc_batch_t *h, const void *score, const int32_t *order, const int32_t *offset, int G, int num, int den,
+                              const int32_t *bins, int F, int M, double *sens, void *stream) {
+  const char *fn = "umpcBatchScoreSensitivity";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!score || !order || !offset || !bins || !sens) return refuse(fn, "bad argument (score, order, offset, bins and sens must be given)");
+  if (check_groups(fn, G) || check_factors(fn, F, M) || check_rows(fn, num, den)) return -1;
+  return h->dtype == UMPC_F32 ? launch_score_sensitivity<float>(h, score, order, offset, G, num, den, bins, F, M, sens, stream)
+                              : launch_score_sensitivity<double>(h, score, order, offset, G, num, den, bins, F, M, sens, stream);
 }
 
 }  // extern "C"

@@ -5,7 +5,9 @@ umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble)
 umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles), the bootstrap of
 umpcBatchScoreBootstrap (score_bootstrap) and the bootstrap bands of umpcBatchEnsembleBootstrap (ensemble_bootstrap) further down,
 and for the moments, ellipsoids and Mahalanobis scores of umpcBatchDispersion / umpcBatchDispersionEllipsoids /
-umpcBatchMahalanobis (dispersion / dispersion_ellipsoids / mahalanobis) at the end.
+umpcBatchMahalanobis (dispersion / dispersion_ellipsoids / mahalanobis), the propagators and, at the end, the binned sums and
+correlation ratios of umpcBatchFactorBins / umpcBatchSensitivity / umpcBatchSensitivityIndices / umpcBatchScoreSensitivity
+(factor_bins / sensitivity / sensitivity_indices / score_sensitivity).
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -1122,3 +1124,206 @@ def propagator_poles(prop, lag=1):
         lam = np.linalg.eigvals(prop[..., P_PHI:P_C][use].reshape(-1, 6, 6)).astype(np.complex128)
         poles[use] = lam if lag == 1 else np.abs(lam) ** (1.0 / lag) * np.exp(1j * np.angle(lam) / lag)
     return poles
+
+
+# ---- sensitivity indices (umpcBatchFactorBins / umpcBatchSensitivity / umpcBatchSensitivityIndices / umpcBatchScoreSensitivity) --
+SENS_MAX_FACTORS, SENS_MAX_BINS = 6, 8
+# sum rows, per (step, group): members scored / skipped, S1 = sum y, S2 = sum y^2, then N_fm at S_BINS + f M + m (the scored
+# members of bin m of factor f) and S_fm = sum y over them at S_BINS + F M + f M + m
+S_N, S_SKIPPED, S_S1, S_S2, S_BINS = 0, 1, 2, 3, 4
+# index rows: n, skipped, status, mean, variance, SST, two zeros, then per factor f at I_FIRST + f (4 + M): eta2, eps2, F, M_f and
+# the M bin means
+I_N, I_SKIPPED, I_STATUS, I_MEAN, I_VAR, I_SST, I_FIRST = 0, 1, 2, 3, 4, 5, 8
+I_ETA2, I_EPS2, I_F, I_MF, I_BINMEAN = 0, 1, 2, 3, 4
+SENS_OK, SENS_FEW, SENS_FLAT = 0, 1, 2
+
+
+def sens_cols(F, nbins):
+    """the length 4 + 2 F M of a row of sums"""
+    return S_BINS + 2 * int(F) * int(nbins)
+
+
+def sens_index_cols(F, nbins):
+    """the length 8 + F (4 + M) of a row of indices"""
+    return I_FIRST + int(F) * (4 + int(nbins))
+
+
+def _check_factors(what, F, M):
+    if not 1 <= F <= SENS_MAX_FACTORS or not 2 <= M <= SENS_MAX_BINS:
+        raise ValueError("%s: 1 to %d factors, 2 to %d bins" % (what, SENS_MAX_FACTORS, SENS_MAX_BINS))
+
+
+def factor_bins_reference(factors, order, offset, nbins=8):
+    """umpcBatchFactorBins in numpy: bins [F, B] int32 from factors [F, B] (any float dtype) and a group index. Per group and
+    factor the members with a finite value are ranked by numpy.argsort(kind="stable") over the member list (ties, -0 against +0
+    among them, go to the earlier position); bin = rank * M // n_f with n_f the finite members. -1 for a value that is not
+    finite and for a robot outside every group. Bins of equal count by rank inside the cell: the given-data estimator of the
+    correlation ratio. A categorical factor needs no ranking: write its bins by hand."""
+    fac = np.atleast_2d(np.asarray(factors))
+    order, offset = np.asarray(order), np.asarray(offset)
+    F, M, G = fac.shape[0], int(nbins), len(offset) - 1
+    _check_factors("factor_bins_reference", F, M)
+    if G < 1 or fac.ndim != 2 or fac.shape[1] != len(order):
+        raise ValueError("factor_bins_reference: bad argument")
+    bins = np.full(fac.shape, -1, np.int32)
+    for g in range(G):
+        mem = order[offset[g]:offset[g + 1]]
+        for f in range(F):
+            v = fac[f, mem]
+            at = np.nonzero(np.isfinite(v))[0]
+            rank = np.empty(len(at), np.int64)
+            rank[np.argsort(v[at], kind="stable")] = np.arange(len(at))
+            bins[f, mem[at]] = rank * M // max(len(at), 1)
+    return bins
+
+
+def _dtype_terms(y, o, r, tl, dtype):
+    """(ok [B], ep, es, tau2 [B] in `dtype`) of one step IN THE DEVICE'S ARITHMETIC (score_terms, csrc/umpc_score.h): every
+    difference, product and sum formed in `dtype` in the order (d0 d0 + d1 d1) + d2 d2; the moments clipped at +-taulim rounded
+    to `dtype`; ok as _step_terms has it"""
+    y, r = np.asarray(y, dtype), np.asarray(r, dtype)
+    p, s, pdes, sdes = y[0:3], y[9:12], r[0:3], r[6:9]
+    ok = np.isfinite(p).all(0) & np.isfinite(s).all(0) & np.isfinite(pdes).all(0) & np.isfinite(sdes).all(0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d, c = p - pdes, s - sdes
+        ep = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+        es = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]
+        if o is not None:
+            o = np.asarray(o, dtype)
+            ok &= np.isfinite(o[1:3]).all(0)
+            lim = np.dtype(dtype).type(tl)
+            t = np.minimum(np.maximum(o[1:3], -lim), lim)
+            tau2 = t[0] * t[0] + t[1] * t[1]
+        else:
+            tau2 = np.zeros_like(ep)
+    return ok, ep, es, tau2
+
+
+def _sens_rows(y, fin, order, offset, bins, M):
+    """[G, 4 + 2 F M]: the rows of one table of values y [B] float64 (fin [B]: the value enters) IN THE DEVICE'S ORDER OF
+    SUMMATION: lane l of 64 starts at +0 and adds the terms of members l, l + 64, .. in list order (+0 for a member that is not
+    scored or not in the bin), then for w = 32, 16, .., 1 lane l becomes (lane l) + (lane l ^ w)"""
+    F, G = bins.shape[0], len(offset) - 1
+    ok = fin & ((bins >= 0) & (bins < M)).all(0)
+    lanes = np.arange(64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        yz = np.where(ok, y, 0.0)
+        hit = [ok & (bins[f] == m) for f in range(F) for m in range(M)]
+        terms = np.stack([yz, np.where(ok, y * y, 0.0)] + [np.where(h, yz, 0.0) for h in hit])       # [2 + F M, B]
+    rows = np.zeros((G, sens_cols(F, M)))
+    for g in range(G):
+        mem = order[offset[g]:offset[g + 1]]
+        part = np.zeros((terms.shape[0], 64))
+        for m0 in range(0, len(mem), 64):
+            t = terms[:, mem[m0:m0 + 64]]
+            part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
+        with np.errstate(over="ignore", invalid="ignore"):
+            for w in (32, 16, 8, 4, 2, 1):
+                part = part + part[:, lanes ^ w]
+        scored = int(ok[mem].sum())
+        rows[g, S_N], rows[g, S_SKIPPED] = scored, len(mem) - scored
+        rows[g, S_S1], rows[g, S_S2] = part[0, 0], part[1, 0]
+        rows[g, S_BINS:S_BINS + F * M] = [int(h[mem].sum()) for h in hit]
+        rows[g, S_BINS + F * M:] = part[2:, 0]
+    return rows
+
+
+def sensitivity_reference(state_hist, out_hist, ref, first, count, ref_first, after, taulim, order, offset, bins, nbins,
+                          term=TERM_EP, dtype=np.float64):
+    """umpcBatchSensitivity in numpy, IN THE DEVICE'S ARITHMETIC AND ORDER OF SUMMATION: [count, G, 4 + 2 F M] float64. The
+    tables, first, count, ref_first, after, order, offset and term are those of ensemble_quantiles_reference, bins [F, B]
+    int32 and nbins = M those of factor_bins_reference (or written by hand); dtype is the handle's: the term y of a member is
+    formed in it by the expressions of the scoring kernel and widened, y^2 and every sum are float64. A member is scored at a
+    step when ensemble_quantiles_reference with the same out_hist scores it and all F of its bins lie in [0, M). Rows: S_*."""
+    st, ref = np.asarray(state_hist), np.asarray(ref)
+    out = None if out_hist is None else np.asarray(out_hist)
+    order, offset, bins = np.asarray(order), np.asarray(offset), np.atleast_2d(np.asarray(bins))
+    first, count, ref_first, after, term, M = int(first), int(count), int(ref_first), int(bool(after)), int(term), int(nbins)
+    F, G = bins.shape[0], len(offset) - 1
+    _check_factors("sensitivity_reference", F, M)
+    if (count < 0 or first < 0 or ref_first < 0 or G < 1 or term not in (TERM_EP, TERM_ES, TERM_TAU)
+            or (term == TERM_TAU and out is None) or bins.shape[1] != st.shape[-1]):
+        raise ValueError("sensitivity_reference: bad argument")
+    sens = np.zeros((count, G, sens_cols(F, M)))
+    for i in range(count):
+        c = first + i
+        fin, ep, es, tau2 = _dtype_terms(st[c + after], None if out is None else out[c],
+                                         ref[ref_first + i] if ref.ndim == 3 else ref, float(taulim), dtype)
+        y = (ep if term == TERM_EP else es if term == TERM_ES else tau2).astype(np.float64)
+        sens[i] = _sens_rows(y, fin, order, offset, bins, M)
+    return sens
+
+
+def score_sensitivity_reference(score, order, offset, bins, nbins, num, den=None):
+    """umpcBatchScoreSensitivity in numpy: [G, 4 + 2 F M], the sums of sensitivity_reference over one column of a per-robot
+    score [12, B]. The value of robot b and whether it enters are those of score_quantiles_reference (score[num, b], or the
+    IEEE double quotient by score[den, b]; row 0 > 0 and the value finite); all F of its bins must lie in [0, M) as well."""
+    sc = np.asarray(score)
+    order, offset, bins = np.asarray(order), np.asarray(offset), np.atleast_2d(np.asarray(bins))
+    num, den, M = int(num), -1 if den is None else int(den), int(nbins)
+    _check_factors("score_sensitivity_reference", bins.shape[0], M)
+    if len(offset) < 2 or not 0 <= num < SCORE_ROWS or not -1 <= den < SCORE_ROWS or bins.shape[1] != sc.shape[1]:
+        raise ValueError("score_sensitivity_reference: bad argument")
+    x, fin = _table_value(sc, num, den)
+    return _sens_rows(x, fin, order, offset, bins, M)
+
+
+def sensitivity_indices_reference(sens, F, nbins):
+    """umpcBatchSensitivityIndices in numpy fp64, THE DEFINITION OF THE KERNEL'S OPERATION ORDER: [.., 8 + F (4 + M)] from the
+    sums [.., 4 + 2 F M]. mean = S1 / n; c = S1 * S1 / n; SST = S2 - c; variance = SST / (n - 1). Per factor: a = +0 and, over
+    the non-empty bins with m ascending, a = a + S_fm * S_fm / N_fm; SSB = a - c; eta2 = SSB / SST, the correlation ratio: the
+    share of the variance of y that the bin means of the factor explain; eps2 = 1 - ((1 - eta2) * (n - 1)) / (n - M_f), its
+    bias-adjusted form (with no effect eta2 averages (M_f - 1) / (n - 1), eps2 zero); F = (SSB / (M_f - 1)) / ((SST - SSB) /
+    (n - M_f)), the one-way ANOVA statistic; M_f the non-empty bins; the bin means S_fm / N_fm, NaN for an empty bin. Status
+    SENS_FEW when n < 2 M, SENS_FLAT when not SST > 0 or S1 or S2 is not finite: eta2, eps2 and F of every factor are then NaN,
+    as they are for a factor with M_f < 2 or n <= M_f. Nothing is clamped."""
+    sens = np.asarray(sens, np.float64)
+    F, M = int(F), int(nbins)
+    _check_factors("sensitivity_indices_reference", F, M)
+    if sens.shape[-1] != sens_cols(F, M):
+        raise ValueError("sensitivity_indices_reference: sens must be [.., %d]" % sens_cols(F, M))
+    idx = np.zeros(sens.shape[:-1] + (sens_index_cols(F, M),))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        n, s1, s2 = sens[..., S_N], sens[..., S_S1], sens[..., S_S2]
+        c = s1 * s1 / n
+        sst, n1 = s2 - c, n - 1.0
+        few = ~(n >= 2.0 * M)
+        bad = ~(sst > 0.0) | ~np.isfinite(s1) | ~np.isfinite(s2)
+        none = few | bad
+        idx[..., I_N], idx[..., I_SKIPPED] = n, sens[..., S_SKIPPED]
+        idx[..., I_STATUS] = np.where(few, SENS_FEW, np.where(bad, SENS_FLAT, SENS_OK))
+        idx[..., I_MEAN], idx[..., I_VAR], idx[..., I_SST] = s1 / n, sst / n1, sst
+        for f in range(F):
+            at = I_FIRST + f * (4 + M)
+            acc, mf = np.zeros_like(n), np.zeros_like(n)
+            for m in range(M):
+                nm, sm = sens[..., S_BINS + f * M + m], sens[..., S_BINS + F * M + f * M + m]
+                has = nm > 0.0
+                acc = np.where(has, acc + sm * sm / nm, acc)
+                mf = np.where(has, mf + 1.0, mf)
+                idx[..., at + I_BINMEAN + m] = np.where(has, sm / nm, np.nan)
+            ssb = acc - c
+            eta = ssb / sst
+            eps = 1.0 - ((1.0 - eta) * n1) / (n - mf)
+            fst = (ssb / (mf - 1.0)) / ((sst - ssb) / (n - mf))
+            nof = none | ~(mf >= 2.0) | ~(n > mf)
+            idx[..., at + I_ETA2] = np.where(nof, np.nan, eta)
+            idx[..., at + I_EPS2] = np.where(nof, np.nan, eps)
+            idx[..., at + I_F] = np.where(nof, np.nan, fst)
+            idx[..., at + I_MF] = mf
+    return idx
+
+
+def combine_sensitivities(parts):
+    """The sums of a whole job from the sums [.., 4 + 2 F M] of its blocks of robots, or of the column blocks a cell is split
+    over: every row is a raw sum, so the rows add (counts exactly; the others to the rounding of one more addition per part) --
+    PROVIDED THE BINS WERE ASSIGNED ON THE WHOLE JOB: factor_bins of a block ranks inside the block and cuts other bins. numpy
+    arrays or torch tensors; the result is of the first part's kind and the parts are not modified.
+    sensitivity_indices / sensitivity_indices_reference of the result are the indices of the whole cell."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_sensitivities: no parts")
+    total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
+    for p in parts[1:]:
+        total = total + p
+    return total
