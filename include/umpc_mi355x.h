@@ -784,6 +784,91 @@ int umpcBatchSensitivityIndices(umpc_batch_t *h, const double *sens, long long c
 int umpcBatchScoreSensitivity(umpc_batch_t *h, const void *score, const int32_t *order, const int32_t *offset, int G,
                               int num, int den, const int32_t *bins, int F, int M, double *sens, void *stream);
 
+/* Error spectra: the oscillation nobody asked for. A gain cell whose position error rings at 30 Hz has the sum_ep of a cell
+ * with a steady offset, and a cell whose moments chatter at the step rate the sum_tau2 of one that pushes smoothly;
+ * umpcBatchResponse fits ONE frequency the caller knows in advance. This block projects a 3-channel signal of every robot
+ * onto K windowed cosine / sine pairs over a window of the step history in one pass, turns the raw sums into a periodogram
+ * and a chatter score per robot, and sums the periodograms over the draws of each grid cell -- the average over draws is
+ * the consistent spectral estimate, and a Monte-Carlo sweep provides it for free. Array expressions would need the signal
+ * as an fp64 [steps][3][B] temporary in front of a matrix product. All four calls are pure functions of their arguments,
+ * take only B and the dtype from the handle, are asynchronous on `stream` and allocate nothing.
+ *
+ * Signals, 3 channels each:
+ *   UMPC_SPEC_EP  p - pdes: state rows 0..2 minus reference rows 0..2
+ *   UMPC_SPEC_ES  s - sdes: state rows 9..11 minus reference rows 6..8
+ *   UMPC_SPEC_U   out rows 0..2 as recorded (specific thrust and the two moments, unclipped); state_hist, ref_tab and ref
+ *                 are not read and may be NULL, out_hist is required and `after` does not enter
+ * A difference is formed in the handle's dtype with one rounding and then widened exactly. state_hist, ref_tab / ref (exactly
+ * ONE of the two), first, count, ref_first and after are those of umpcBatchResponse.
+ *
+ * basis [W][1 + 2 K] DOUBLE on the device, made on the host (robobee3d_amd/score.py spectrum_basis): column 0 is the window
+ * weight w_k, columns 1 + 2 j and 2 + 2 j are w_k cos(2 pi u_jk) and w_k sin(2 pi u_jk) of frequency j. Step i of the call
+ * reads row basis_first + i: the caller makes sure the table holds basis_first + count rows. There is no sincos on the
+ * device: the sums are bit-identical to the numpy mirror, and the call is a projection onto ANY temporal basis -- the
+ * spectrum is its first user. Every entry must be finite. 1 <= K <= UMPC_SPEC_MAX_K.
+ *
+ * sums [2 + 3 (2 + 2 K)][B] DOUBLE, in/out: umpcBatchSpectrum ADDS into it; umpcBatchSpectrumInit writes zeros. A step
+ * enters for a robot when every word it reads for the three channels is finite; otherwise row 1 counts it and every other
+ * row receives +0. With y the channel's value, w, bc_j, bs_j the step's basis row and t = w y:
+ *   0  n, steps that entered        1  skipped steps
+ *   2 + c (2 + 2 K) + 0, channel c:  sum t            + 1:  sum t y
+ *   2 + c (2 + 2 K) + 2 + 2 j:       C_j = sum y bc_j     + 3 + 2 j:  S_j = sum y bs_j
+ * Every product and every sum is a separate IEEE fp64 operation (no fused multiply-add).
+ * Order of summation: a block of 64 robots is UMPC_SPEC_SLICES = 2 wavefronts; wavefront s folds steps s, s + 2, s + 4, ..
+ * of the call in order from +0, the partial sums are added in the order 0, 1 and the total is added to `sums`. Nothing
+ * crosses robots, and how the K frequencies are cut into tiles on the device does not enter: a robot's sums depend on its
+ * own columns, the basis rows and count alone -- bit-equal from run to run and between a column block on a handle of its
+ * own and the same columns of the whole batch; no atomics, no temporaries. A chunked run calls umpcBatchSpectrum once per
+ * chunk with basis_first advanced: rows 0 and 1 are exact across the cut, the other rows agree to rounding (each within
+ * (n + 4) 2^-53 times the sum of its terms' magnitudes of the exact sum).
+ *
+ * umpcBatchSpectrumPower: one lane per robot, fp64 throughout, rounded to the handle's dtype at the store. wsum [1 + 2 K]
+ * and freq_hz [K] are HOST arrays (they travel in the launch arguments): wsum the column sums of the basis rows that were
+ * used, added sequentially in row order -- W0 = wsum[0], Wc_j = wsum[1 + 2 j], Ws_j = wsum[2 + 2 j] --, freq_hz the frequency
+ * of each column pair in Hz (any unit: rows 6, 9 and 10 are in it). Per channel:
+ *   m = sum t / W0,  var = sum t y / W0 - m m
+ *   A_j = C_j - m Wc_j,  B_j = S_j - m Ws_j          (the mean is removed through the window's own transform)
+ *   P_j = 4 (A_j^2 + B_j^2) / W0^2                   (an on-grid sinusoid of amplitude a gives a^2, as row 2 of a response)
+ * power [3][K][B] and spec [3][UMPC_SPEC_ROWS][B] in the handle's dtype, overwritten; per channel the rows of spec:
+ *   0  n, or 0 when the fit is refused            1  skipped steps
+ *   2  m                                          3  var
+ *   4  total = sum_j P_j, j ascending             5  peak bin, the first maximum of P_j
+ *   6  freq_hz of the peak bin                    7  P of the peak bin
+ *   8  peak share, row 7 / row 4                  9  centroid sum_j f_j P_j / total
+ *  10  bandwidth sqrt(sum_j (f_j - centroid)^2 P_j / total)
+ *  11  high share sum_{j >= jsplit} P_j / total: the chatter score (jsplit = K: 0)
+ * The fit is REFUSED when skipped > 0 (the window has a hole), n != nrows (the sums are not those of the nrows basis rows
+ * wsum was taken over), n < 2, or total is not > 0 and finite: row 0 is then 0 and rows 2..11 and the channel's power are
+ * NaN. Nothing is clamped: rounding may put var a hair below 0. spec[c] is shaped as a score on purpose -- row 0 > 0
+ * meaning "enters" -- so umpcBatchScoreQuantiles, umpcBatchScoreBootstrap and umpcBatchScoreSensitivity take it unchanged.
+ * The bins are read with the factor of a frequency strictly between 0 and half the step rate; the caller keeps them there.
+ *
+ * umpcBatchSpectrumGroups: the cell-summed periodogram on the tables of umpcBatchGroupIndex, gspec [G][3][2 + K] DOUBLE,
+ * overwritten; per group and channel: the members that enter (row 0 of spec[c] > 0), the members that do not, and per
+ * frequency the sum of P_j over the members that enter (divide by column 0 for the cell's averaged periodogram). Order of
+ * summation: that of umpcBatchDispersion -- lane l of 64 adds members l, l + 64, .. of the list in order from +0, then for
+ * w = 32, 16, 8, 4, 2, 1 every lane becomes (itself) + (lane ^ w). A row is a function of the group's member list alone;
+ * raw sums ADD over the blocks of a sharded job.
+ * Not built: an MFMA Gram product (its order of accumulation is undocumented: no mirror could follow it); Welch averaging
+ * over time segments; cross-spectra and coherence; peak interpolation between bins.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; basis, sums, wsum, freq_hz, power, spec, order, offset or gspec
+ * NULL; K outside 1..64; signal outside 0..2; state_hist NULL for UMPC_SPEC_EP / ES, out_hist NULL for UMPC_SPEC_U; both or
+ * neither of ref_tab and ref (UMPC_SPEC_EP / ES); count, first, ref_first or basis_first < 0; count > 2^31 - 5; nrows < 0;
+ * jsplit outside 0..K; G < 1. count == 0 is a successful no-op. */
+#define UMPC_SPEC_EP 0
+#define UMPC_SPEC_ES 1
+#define UMPC_SPEC_U 2
+#define UMPC_SPEC_ROWS 12
+#define UMPC_SPEC_MAX_K 64
+int umpcBatchSpectrumInit(umpc_batch_t *h, int K, double *sums, void *stream);
+int umpcBatchSpectrum(umpc_batch_t *h, int signal, const void *state_hist, const void *out_hist, const void *ref_tab,
+                      const void *ref, const double *basis, long long basis_first, int K, long long first, long long count,
+                      long long ref_first, int after, double *sums, void *stream);
+int umpcBatchSpectrumPower(umpc_batch_t *h, const double *sums, const double *wsum, const double *freq_hz, int K,
+                           long long nrows, int jsplit, void *power, void *spec, void *stream);
+int umpcBatchSpectrumGroups(umpc_batch_t *h, const void *power, const void *spec, const int32_t *order, const int32_t *offset,
+                            int G, int K, double *gspec, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

@@ -1,7 +1,7 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchScoreSensitivity) and their
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchSpectrumGroups) and their
 // host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
-// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h and umpc_sensitivity.h: nothing here reads the step path or a
-// generated header.
+// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h, umpc_sensitivity.h and umpc_spectrum.h: nothing here reads
+// the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -17,10 +17,18 @@
 #include "umpc_dispersion.h" // per-step, per-group moments, ellipsoids and Mahalanobis scores (umpcBatchDispersion ..)
 #include "umpc_propagator.h" // per-step, per-group lagged moments and the affine map between two steps (umpcBatchLagMoments ..)
 #include "umpc_sensitivity.h" // per-step, per-group binned sums over the drawn inputs and their correlation ratios (umpcBatchSensitivity ..)
+#include "umpc_spectrum.h" // per-robot projections onto a temporal basis, periodograms and their per-group sums (umpcBatchSpectrum ..)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
   static const bool v = [] { const char *e_ = getenv("UMPC_SCORE_NT"); return e_ && atoi(e_) != 0; }();
+  return v;
+}
+
+// UMPC_SPEC_KT=16 runs the sums kernel of umpcBatchSpectrum with tiles of 16 frequencies instead of 8 (A/B timing,
+// tools/time_spectrum.py: 8 is the faster one at the shape of record; the sums do not depend on it)
+static int spec_kt() {
+  static const int v = [] { const char *e_ = getenv("UMPC_SPEC_KT"); return e_ && atoi(e_) == 16 ? 16 : 8; }();
   return v;
 }
 
@@ -347,6 +355,65 @@ static int launch_score_sensitivity(umpc_batch_t *h, const void *score, const in
   return launch_status("umpcBatchScoreSensitivity");
 }
 
+// (the window is that of launch_response; signal UMPC_SPEC_U reads rows 0..2 of the out record and no reference)
+template <typename T>
+static int launch_spectrum(umpc_batch_t *h, int signal, const ScoreWindow &w, const double *basis, long long basis_first, int K,
+                           double *sums, void *stream) {
+  const size_t B = (size_t)h->B;
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, 0, nullptr);
+  umpc::SpecArgs<T> a;
+  const int yrow = signal == UMPC_SPEC_ES ? 9 : 0, rrow = signal == UMPC_SPEC_ES ? 6 : 0;
+  const bool cmd = signal == UMPC_SPEC_U;
+  a.y = cmd ? t.out : t.state + (size_t)yrow * B;
+  a.ystride = cmd ? 9 : 18;
+  a.reftab = !cmd && t.reftab ? t.reftab + (size_t)rrow * B : nullptr;
+  a.ref = !cmd && t.ref ? t.ref + (size_t)rrow * B : nullptr;
+  a.basis = basis + (size_t)basis_first * (1 + 2 * (size_t)K);
+  a.sums = sums;
+  a.B = h->B; a.count = (int)w.count; a.K = K;
+  const int kt = spec_kt();
+  const dim3 grid((unsigned)((h->B + 63) / 64), (unsigned)((K + kt - 1) / kt)), block(64, umpc::kSpecSlices);
+  const hipStream_t s = (hipStream_t)stream;
+  const int ref = cmd ? umpc::kSpecRefNone : a.reftab ? umpc::kSpecRefTable : umpc::kSpecRefConst;
+#define UMPC_SPEC_FORM(R)                                                                                               \
+  case R:                                                                                                               \
+    if (kt == 8) hipLaunchKernelGGL((umpc::umpc_spectrum_kernel<T, R, 8>), grid, block, 0, s, a);                         \
+    else hipLaunchKernelGGL((umpc::umpc_spectrum_kernel<T, R, 16>), grid, block, 0, s, a);                                \
+    break;
+  switch (ref) { UMPC_SPEC_FORM(0) UMPC_SPEC_FORM(1) UMPC_SPEC_FORM(2) }
+#undef UMPC_SPEC_FORM
+  return launch_status("umpcBatchSpectrum");
+}
+
+template <typename T>
+static int launch_spectrum_power(umpc_batch_t *h, const double *sums, const double *wsum, const double *freq_hz, int K,
+                                 long long nrows, int jsplit, void *power, void *spec, void *stream) {
+  umpc::SpecPowerArgs<T> a;
+  for (int j = 0; j < 1 + 2 * umpc::kSpecMaxK; ++j) a.wsum[j] = j < 1 + 2 * K ? wsum[j] : 0.0;
+  for (int j = 0; j < umpc::kSpecMaxK; ++j) a.freq[j] = j < K ? freq_hz[j] : 0.0;
+  a.sums = sums; a.power = (T *)power; a.spec = (T *)spec;
+  a.nrows = (double)nrows; a.B = h->B; a.K = K; a.jsplit = jsplit;
+  hipLaunchKernelGGL(umpc::umpc_spectrum_power_kernel<T>, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchSpectrumPower");
+}
+
+// one wavefront per (group, channel); K <= 32 runs the form with one tree of 32 frequencies per lane
+template <typename T>
+static int launch_spectrum_groups(umpc_batch_t *h, const void *power, const void *spec, const int32_t *order, const int32_t *offset,
+                                  int G, int K, double *gspec, void *stream) {
+  umpc::SpecGroupArgs<T> a;
+  a.power = (const T *)power; a.spec = (const T *)spec; a.order = order; a.offset = offset; a.gspec = gspec;
+  a.B = h->B; a.K = K;
+  const dim3 grid((unsigned)G, 3u);
+  if (K > 32) hipLaunchKernelGGL((umpc::umpc_spectrum_groups_kernel<T, 2>), grid, dim3(64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((umpc::umpc_spectrum_groups_kernel<T, 1>), grid, dim3(64), 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchSpectrumGroups");
+}
+
+static int check_freqs(const char *fn, int K) {
+  return K < 1 || K > UMPC_SPEC_MAX_K ? refuse(fn, "bad argument (1 <= K <= 64 frequencies)") : 0;
+}
+
 extern "C" {
 
 int umpcBatchScoreInit(umpc_batch_t *h, void *score, void *stream) {
@@ -630,6 +697,54 @@ int umpcBatchScoreSensitivity(umpc_batch_t *h, const void *score, const int32_t 
   if (check_groups(fn, G) || check_factors(fn, F, M) || check_rows(fn, num, den)) return -1;
   return h->dtype == UMPC_F32 ? launch_score_sensitivity<float>(h, score, order, offset, G, num, den, bins, F, M, sens, stream)
                               : launch_score_sensitivity<double>(h, score, order, offset, G, num, den, bins, F, M, sens, stream);
+}
+
+int umpcBatchSpectrumInit(umpc_batch_t *h, int K, double *sums, void *stream) {
+  const char *fn = "umpcBatchSpectrumInit";
+  if (!h || !sums) return refuse(fn, "bad argument (h and sums must be given)");
+  if (check_freqs(fn, K)) return -1;
+  const hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * (2 + 3 * (2 + 2 * (size_t)K)) * (size_t)h->B, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail(e, fn);
+}
+int umpcBatchSpectrum(umpc_batch_t *h, int signal, const void *state_hist, const void *out_hist, const void *ref_tab,
+                      const void *ref, const double *basis, long long basis_first, int K, long long first, long long count,
+                      long long ref_first, int after, double *sums, void *stream) {
+  const char *fn = "umpcBatchSpectrum";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (signal < UMPC_SPEC_EP || signal > UMPC_SPEC_U) return refuse(fn, "bad argument (signal is UMPC_SPEC_EP, UMPC_SPEC_ES or UMPC_SPEC_U)");
+  if (!basis || !sums) return refuse(fn, "bad argument (basis and sums must be given)");
+  if (check_freqs(fn, K)) return -1;
+  const bool cmd = signal == UMPC_SPEC_U;
+  if (cmd && !out_hist) return refuse(fn, "UMPC_SPEC_U needs out_hist (the command is read from it)");
+  if (!cmd && !state_hist) return refuse(fn, "bad argument (state_hist must be given)");
+  // (the command has no reference: ref_tab and ref are not read with it)
+  const ScoreWindow w = {state_hist, out_hist, nullptr, cmd ? nullptr : ref_tab, cmd ? nullptr : ref, first, count, ref_first, after};
+  if (!cmd && check_one_reference(fn, w)) return -1;
+  if (count < 0 || first < 0 || ref_first < 0 || basis_first < 0) return refuse(fn, "bad argument (count, first, ref_first, basis_first >= 0)");
+  if (count > 0x7fffffffLL - 2 * umpc::kSpecSlices) return refuse(fn, "count too large for one call (2^31 - 5 steps at the most)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_spectrum<float>(h, signal, w, basis, basis_first, K, sums, stream)
+                              : launch_spectrum<double>(h, signal, w, basis, basis_first, K, sums, stream);
+}
+int umpcBatchSpectrumPower(umpc_batch_t *h, const double *sums, const double *wsum, const double *freq_hz, int K, long long nrows,
+                           int jsplit, void *power, void *spec, void *stream) {
+  const char *fn = "umpcBatchSpectrumPower";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!sums || !wsum || !freq_hz || !power || !spec) return refuse(fn, "bad argument (sums, wsum, freq_hz, power and spec must be given)");
+  if (check_freqs(fn, K)) return -1;
+  if (nrows < 0 || nrows > (1LL << 53)) return refuse(fn, "bad argument (0 <= nrows <= 2^53)");
+  if (jsplit < 0 || jsplit > K) return refuse(fn, "bad argument (0 <= jsplit <= K)");
+  return h->dtype == UMPC_F32 ? launch_spectrum_power<float>(h, sums, wsum, freq_hz, K, nrows, jsplit, power, spec, stream)
+                              : launch_spectrum_power<double>(h, sums, wsum, freq_hz, K, nrows, jsplit, power, spec, stream);
+}
+int umpcBatchSpectrumGroups(umpc_batch_t *h, const void *power, const void *spec, const int32_t *order, const int32_t *offset, int G,
+                            int K, double *gspec, void *stream) {
+  const char *fn = "umpcBatchSpectrumGroups";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!power || !spec || !order || !offset || !gspec) return refuse(fn, "bad argument (power, spec, order, offset and gspec must be given)");
+  if (check_groups(fn, G) || check_freqs(fn, K)) return -1;
+  return h->dtype == UMPC_F32 ? launch_spectrum_groups<float>(h, power, spec, order, offset, G, K, gspec, stream)
+                              : launch_spectrum_groups<double>(h, power, spec, order, offset, G, K, gspec, stream);
 }
 
 }  // extern "C"

@@ -5,9 +5,10 @@ umpcBatchGroupIndex / umpcBatchEnsemble (BatchUprightMPC.group_index / ensemble)
 umpcBatchEnsembleQuantiles / umpcBatchScoreQuantiles (ensemble_quantiles / score_quantiles), the bootstrap of
 umpcBatchScoreBootstrap (score_bootstrap) and the bootstrap bands of umpcBatchEnsembleBootstrap (ensemble_bootstrap) further down,
 and for the moments, ellipsoids and Mahalanobis scores of umpcBatchDispersion / umpcBatchDispersionEllipsoids /
-umpcBatchMahalanobis (dispersion / dispersion_ellipsoids / mahalanobis), the propagators and, at the end, the binned sums and
+umpcBatchMahalanobis (dispersion / dispersion_ellipsoids / mahalanobis), the propagators, the binned sums and
 correlation ratios of umpcBatchFactorBins / umpcBatchSensitivity / umpcBatchSensitivityIndices / umpcBatchScoreSensitivity
-(factor_bins / sensitivity / sensitivity_indices / score_sensitivity).
+(factor_bins / sensitivity / sensitivity_indices / score_sensitivity) and, at the end, the projections, periodograms and
+per-group spectra of umpcBatchSpectrum / umpcBatchSpectrumPower / umpcBatchSpectrumGroups (spectrum / spectrum_groups).
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -1323,6 +1324,252 @@ def combine_sensitivities(parts):
     parts = list(parts)
     if not parts:
         raise ValueError("combine_sensitivities: no parts")
+    total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
+    for p in parts[1:]:
+        total = total + p
+    return total
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Error spectra (umpcBatchSpectrumInit / umpcBatchSpectrum / umpcBatchSpectrumPower / umpcBatchSpectrumGroups): per robot
+# the projection of a 3-channel signal onto K windowed cosine / sine pairs, its periodogram and chatter score; per group the
+# periodogram summed over the members
+# ----------------------------------------------------------------------------------------------------------------------
+SPEC_ROWS, SPEC_MAX_K = 12, 64
+SPEC_SLICES = 2             # UMPC_SPEC_SLICES (csrc/umpc_spectrum.h): wavefronts a call's step range is split over
+SPEC_EP, SPEC_ES, SPEC_U = 0, 1, 2
+SPEC_SIGNALS = ("ep", "es", "u")      # p - pdes, s - sdes, the recorded command (out rows 0..2)
+SPEC_WINDOWS = ("hann", "rect")
+# sum rows: n, skipped, then per channel c at SSUM_CHANNEL + c (2 + 2 K): sum w y, sum w y y, then (C_j, S_j) per frequency
+SSUM_N, SSUM_SKIPPED, SSUM_CHANNEL = 0, 1, 2
+SSUM_WY, SSUM_WYY, SSUM_BINS = 0, 1, 2
+# spectrum rows, per channel (row 0 > 0 means "enters", as in a score)
+(SPEC_STEPS, SPEC_SKIPPED, SPEC_MEAN, SPEC_VAR, SPEC_TOTAL, SPEC_PEAK_BIN, SPEC_PEAK_HZ, SPEC_PEAK_POWER, SPEC_PEAK_SHARE,
+ SPEC_CENTROID_HZ, SPEC_BANDWIDTH_HZ, SPEC_HIGH_SHARE) = range(12)
+SPEC_ROW_NAMES = ("steps", "skipped", "mean", "var", "total", "peak_bin", "peak_hz", "peak_power", "peak_share", "centroid_hz",
+                  "bandwidth_hz", "high_share")
+# group rows, per (group, channel): members that enter, members that do not, then the sum of P_j per frequency
+GSPEC_N, GSPEC_SKIPPED, GSPEC_FIRST = 0, 1, 2
+
+
+def spectrum_sum_rows(K):
+    """rows of the sums of umpcBatchSpectrum for K frequencies: 2 + 3 (2 + 2 K)"""
+    K = int(K)
+    if not 1 <= K <= SPEC_MAX_K:
+        raise ValueError("1 <= K <= %d frequencies" % SPEC_MAX_K)
+    return 2 + 3 * (2 + 2 * K)
+
+
+def spectrum_identity(K, B):
+    """The sums no step has entered (umpcBatchSpectrumInit): zeros [2 + 3 (2 + 2 K), B] float64."""
+    return np.zeros((spectrum_sum_rows(K), int(B)))
+
+
+def spectrum_basis(nu, W, window="hann", step0=0):
+    """The basis table of umpcBatchSpectrum, float64 [W, 1 + 2 K]: row k holds the window weight w_k, then per frequency j
+    w_k cos(2 pi u_jk) and w_k sin(2 pi u_jk) with the phase of response_phase(step0 + k, nu) -- one double multiply, exact
+    zeros and ones at the quarter points, the same whatever step0 is. nu [K]: revolutions per step, each strictly inside
+    (0, 0.5): the power kernel reads a bin with the factor 4 / W0^2 of a frequency between 0 and half the step rate; at 0
+    and 0.5 the sine column is zero and the factor is another one. window: "rect" (w = 1) or "hann" (the periodic Hann
+    window w_k = 0.5 - 0.5 cos(2 pi k / W)); the window counts rows from 0, step0 moves the phase origin only."""
+    nu = np.atleast_1d(np.asarray(nu, np.float64))
+    W, step0 = int(W), int(step0)
+    if nu.ndim != 1 or not 1 <= len(nu) <= SPEC_MAX_K:
+        raise ValueError("spectrum_basis: 1 <= K <= %d frequencies" % SPEC_MAX_K)
+    if not np.all((nu > 0.0) & (nu < 0.5)):
+        raise ValueError("spectrum_basis: every nu must lie strictly inside (0, 0.5) revolutions per step")
+    if W < 1 or step0 < 0 or step0 + W > 1 << 53 or window not in SPEC_WINDOWS:
+        raise ValueError("spectrum_basis: bad argument (W >= 1, 0 <= step0, window is 'hann' or 'rect')")
+    basis = np.empty((W, 1 + 2 * len(nu)))
+    inv = np.array([1.0 / W])
+    for k in range(W):
+        w = 1.0 if window == "rect" else 0.5 - 0.5 * response_phase(k, inv)[0][0]
+        c, s, _ = response_phase(step0 + k, nu)
+        basis[k, 0] = w
+        basis[k, 1::2] = w * c
+        basis[k, 2::2] = w * s
+    return basis
+
+
+def spectrum_wsum(basis, basis_first=0, count=None):
+    """wsum [1 + 2 K] of umpcBatchSpectrumPower: the column sums of rows basis_first .. basis_first + count - 1 of the basis,
+    added sequentially in row order from +0."""
+    basis = np.asarray(basis, np.float64)
+    first = int(basis_first)
+    count = basis.shape[0] - first if count is None else int(count)
+    if basis.ndim != 2 or first < 0 or count < 0 or first + count > basis.shape[0]:
+        raise ValueError("spectrum_wsum: the rows asked for are not inside the basis")
+    total = np.zeros(basis.shape[1])
+    for k in range(first, first + count):
+        total = total + basis[k]
+    return total
+
+
+def _spectrum_signal(signal):
+    if signal in SPEC_SIGNALS:
+        return SPEC_SIGNALS.index(signal)
+    if signal in (SPEC_EP, SPEC_ES, SPEC_U):
+        return int(signal)
+    raise ValueError("signal is one of %s" % (SPEC_SIGNALS,))
+
+
+def spectrum_sums_reference(signal, state_hist, out_hist, ref, basis, basis_first, first, count, ref_first, after,
+                            dtype=np.float64, sums=None):
+    """umpcBatchSpectrum in numpy, IN THE DEVICE'S ORDER OF SUMMATION: the sums [2 + 3 (2 + 2 K), B] float64. signal "ep" / "es"
+    / "u"; state_hist [.., 18, B], ref -- a table [.., 9, B] (slice ref_first + i) or one constant reference [9, B] --, first,
+    count, ref_first and after are those of response_sums_reference; "u" reads rows 0..2 of out_hist [.., 9, B], slice first
+    + i, and neither state_hist nor ref. dtype is the handle's: a difference is formed in it with one rounding, everything
+    after is float64. basis [W, 1 + 2 K]: step i reads row basis_first + i. A step enters for a robot when every word it reads
+    is finite; otherwise it is counted in row 1 and its value is +0 in every product. Slice s of SPEC_SLICES adds steps s,
+    s + SPEC_SLICES, .. in order from +0, the partial sums are added in the order 0, 1, .. and the total is added to `sums`
+    (passing one back in accumulates). Elementwise IEEE operations in that order: the kernel's bits."""
+    sig = _spectrum_signal(signal)
+    basis = np.asarray(basis, np.float64)
+    first, count, ref_first, after, basis_first = int(first), int(count), int(ref_first), int(bool(after)), int(basis_first)
+    if basis.ndim != 2 or basis.shape[1] < 3 or basis.shape[1] % 2 != 1:
+        raise ValueError("spectrum_sums_reference: basis must be [W, 1 + 2 K]")
+    K = (basis.shape[1] - 1) // 2
+    rows = spectrum_sum_rows(K)
+    if count < 0 or first < 0 or ref_first < 0 or basis_first < 0 or basis_first + count > basis.shape[0]:
+        raise ValueError("spectrum_sums_reference: bad argument")
+    if sig == SPEC_U:
+        if out_hist is None:
+            raise ValueError("spectrum_sums_reference: signal 'u' needs out_hist")
+        src = np.asarray(out_hist, dtype)
+    else:
+        src = np.asarray(state_hist, dtype)
+        ref = np.asarray(ref, dtype)
+    B = src.shape[-1]
+    sm = spectrum_identity(K, B) if sums is None else np.array(sums, np.float64)
+    if sm.shape != (rows, B):
+        raise ValueError("spectrum_sums_reference: sums must be [%d, %d]" % (rows, B))
+    chan = 2 + 2 * K
+    total = None
+    with np.errstate(invalid="ignore", over="ignore"):
+        for s in range(SPEC_SLICES):
+            part = np.zeros((rows, B))
+            for i in range(s, count, SPEC_SLICES):
+                if sig == SPEC_U:
+                    y = src[first + i, 0:3]
+                    ok, d = np.isfinite(y).all(0), y
+                else:
+                    y0, r0 = (0, 0) if sig == SPEC_EP else (9, 6)
+                    y = src[first + i + after, y0:y0 + 3]
+                    r = (ref[ref_first + i] if ref.ndim == 3 else ref)[r0:r0 + 3]
+                    ok, d = np.isfinite(y).all(0) & np.isfinite(r).all(0), y - r
+                v = np.where(ok, d.astype(np.float64), 0.0)                    # [3, B]
+                row = basis[basis_first + i]
+                part[SSUM_N] += ok
+                part[SSUM_SKIPPED] += ~ok
+                for c in range(3):
+                    at = SSUM_CHANNEL + c * chan
+                    t = row[0] * v[c]
+                    part[at + SSUM_WY] += t
+                    part[at + SSUM_WYY] += t * v[c]
+                    part[at + SSUM_BINS:at + chan] += v[c][None, :] * row[1:, None]
+            total = part if total is None else total + part
+        sm = sm + total
+    return sm
+
+
+def spectrum_power_reference(sums, wsum, freq_hz, nrows, jsplit):
+    """umpcBatchSpectrumPower in numpy fp64, in the kernel's operation order: (spec [3, 12, B], power [3, K, B]) float64 from
+    the sums [2 + 3 (2 + 2 K), B], the window's column sums wsum [1 + 2 K] (spectrum_wsum), the frequencies freq_hz [K], the
+    number of basis rows wsum was taken over and the first bin of the high band. Per channel: m = sum wy / W0, var = sum wyy /
+    W0 - m m, A_j = C_j - m Wc_j, B_j = S_j - m Ws_j, P_j = (4 (A_j A_j + B_j B_j)) / (W0 W0); total, the centroid's numerator
+    sum f_j P_j and the high band's sum are added with j ascending from +0, the peak is the first maximum; then the bandwidth's
+    numerator sum ((f_j - centroid) (f_j - centroid)) P_j. Refused (row 0 = 0, rows 2..11 and the channel's power NaN) when
+    skipped > 0, n != nrows, n < 2 or total is not > 0 and finite. The device rounds to the handle's dtype at the store."""
+    sm = np.asarray(sums, np.float64)
+    wsum, f = np.asarray(wsum, np.float64), np.atleast_1d(np.asarray(freq_hz, np.float64))
+    K = len(f)
+    nrows, jsplit = int(nrows), int(jsplit)
+    if sm.ndim != 2 or f.ndim != 1 or sm.shape[0] != spectrum_sum_rows(K) or wsum.shape != (1 + 2 * K,):
+        raise ValueError("spectrum_power_reference: sums must be [2 + 3 (2 + 2 K), B], wsum [1 + 2 K], freq_hz [K]")
+    if nrows < 0 or not 0 <= jsplit <= K:
+        raise ValueError("spectrum_power_reference: bad argument (nrows >= 0, 0 <= jsplit <= K)")
+    B = sm.shape[1]
+    spec, power = np.full((3, SPEC_ROWS, B), np.nan), np.full((3, K, B), np.nan)
+    n, skipped = sm[SSUM_N], sm[SSUM_SKIPPED]
+    w0 = wsum[0]
+    w02 = w0 * w0
+    counts = (skipped > 0.0) | (n != float(nrows)) | ~(n >= 2.0)
+    chan = 2 + 2 * K
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for c in range(3):
+            ch = sm[SSUM_CHANNEL + c * chan:SSUM_CHANNEL + (c + 1) * chan]
+            m = ch[SSUM_WY] / w0
+            var = ch[SSUM_WYY] / w0 - m * m
+            P = np.empty((K, B))
+            total, peak, cnum, high = np.zeros(B), np.zeros(B), np.zeros(B), np.zeros(B)
+            jpeak = np.zeros(B, np.int64)
+            for j in range(K):
+                A = ch[SSUM_BINS + 2 * j] - m * wsum[1 + 2 * j]
+                Bq = ch[SSUM_BINS + 2 * j + 1] - m * wsum[2 + 2 * j]
+                P[j] = (4.0 * (A * A + Bq * Bq)) / w02
+                total = total + P[j]
+                better = (P[j] > peak) if j else np.ones(B, bool)
+                peak = np.where(better, P[j], peak)
+                jpeak = np.where(better, j, jpeak)
+                cnum = cnum + f[j] * P[j]
+                high = high + (P[j] if j >= jsplit else 0.0)
+            cen = cnum / total
+            refused = counts | ~(total > 0.0) | ~np.isfinite(total)
+            bnum = np.zeros(B)
+            for j in range(K):
+                d = f[j] - cen
+                bnum = bnum + (d * d) * P[j]
+            o = spec[c]
+            o[SPEC_STEPS] = n
+            o[SPEC_MEAN], o[SPEC_VAR], o[SPEC_TOTAL] = m, var, total
+            o[SPEC_PEAK_BIN], o[SPEC_PEAK_HZ], o[SPEC_PEAK_POWER] = jpeak, f[jpeak], peak
+            o[SPEC_PEAK_SHARE], o[SPEC_CENTROID_HZ] = peak / total, cen
+            o[SPEC_BANDWIDTH_HZ], o[SPEC_HIGH_SHARE] = np.sqrt(bnum / total), high / total
+            o[2:, refused] = np.nan
+            o[SPEC_STEPS, refused] = 0.0
+            o[SPEC_SKIPPED] = skipped
+            power[c] = np.where(refused, np.nan, P)
+    return spec, power
+
+
+def spectrum_groups_reference(power, spec, order, offset):
+    """umpcBatchSpectrumGroups in numpy, IN THE DEVICE'S ORDER OF SUMMATION: [G, 3, 2 + K] float64 from power [3, K, B] and
+    spec [3, 12, B] as the device holds them (in the handle's dtype; widened here) and the tables of group_index. Per group
+    and channel: the members that enter (row 0 of spec[c] > 0), the members that do not, and per frequency the sum of P_j over
+    the members that enter, in dispersion_reference's order: lane l of 64 starts at +0 and adds members l, l + 64, .. of the
+    list in order (+0 for a member that does not enter), then for w = 32, 16, .., 1 lane l becomes (lane l) + (lane l ^ w)."""
+    power, spec = np.asarray(power), np.asarray(spec)
+    order, offset = np.asarray(order), np.asarray(offset)
+    G, K = len(offset) - 1, power.shape[1]
+    if G < 1 or power.ndim != 3 or spec.shape != (3, SPEC_ROWS, power.shape[2]) or not 1 <= K <= SPEC_MAX_K:
+        raise ValueError("spectrum_groups_reference: bad argument")
+    out = np.zeros((G, 3, 2 + K))
+    lanes = np.arange(64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for g in range(G):
+            mem = order[offset[g]:offset[g + 1]]
+            for c in range(3):
+                ok = spec[c, SPEC_STEPS, mem] > 0
+                terms = np.where(ok[None, :], power[c][:, mem].astype(np.float64), 0.0)          # [K, members]
+                part = np.zeros((K, 64))
+                for m0 in range(0, len(mem), 64):
+                    t = terms[:, m0:m0 + 64]
+                    part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
+                for w in (32, 16, 8, 4, 2, 1):
+                    part = part + part[:, lanes ^ w]
+                out[g, c, GSPEC_N], out[g, c, GSPEC_SKIPPED] = ok.sum(), len(mem) - ok.sum()
+                out[g, c, GSPEC_FIRST:] = part[:, 0]
+    return out
+
+
+def combine_spectra(parts):
+    """The group table of a whole job from the tables [G, 3, 2 + K] of its blocks of robots, or of the column blocks a cell
+    is split over: every column is a raw sum, so the tables add (counts exactly; the powers to the rounding of one more
+    addition per part). numpy arrays or torch tensors; the result is of the first part's kind and the parts are not modified.
+    Column 2 + j divided by column 0 is the cell's averaged periodogram."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_spectra: no parts")
     total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
     for p in parts[1:]:
         total = total + p
