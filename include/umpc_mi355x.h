@@ -869,6 +869,67 @@ int umpcBatchSpectrumPower(umpc_batch_t *h, const double *sums, const double *ws
 int umpcBatchSpectrumGroups(umpc_batch_t *h, const void *power, const void *spec, const int32_t *order, const int32_t *offset,
                             int G, int K, double *gspec, void *stream);
 
+/* Trajectory modes: the Gram matrix of the error trajectories of the draws of a group, and weighted sums over the draws of a
+ * group at every step. Every table above is a marginal -- one robot condensed over time, or one (step, group) condensed
+ * over its draws; these two calls relate draw i of a cell to draw j of the same cell AS WHOLE TRAJECTORIES: which flight is
+ * the typical one (the medoid), in how many ways the draws differ (the eigenvalues of the doubly centred Gram matrix), what
+ * those ways look like over time (umpcBatchProject with the eigenvectors as weights) -- the host part is
+ * robobee3d_amd/score.py, trajectory_modes / trajectory_table. Both calls are pure functions of their arguments, as
+ * umpcBatchDispersion is, are asynchronous on `stream` and allocate nothing.
+ * umpcBatchGram takes state_hist, ref_tab / ref (exactly ONE of the two), first, count, ref_first, after, order, offset and G
+ * exactly as umpcBatchDispersion does; member slot i of group g is robot order[offset[g] + i]. The data rule is
+ * umpcBatchDispersion's: a step reads 12 words per member (state rows 0..2 and 12..14, reference rows 0..5); a (member,
+ * step) is SCORED when all 12 are finite; each difference is formed in the handle's dtype with one rounding, then widened;
+ * y_c = scale[c] * z_c is one fp64 product; a (member, step) that is not scored contributes y = +0, selected before the
+ * product. scale [6] is read on the HOST; a scale may be 0 (the default of the Python layer, (1, 1, 1, 0, 0, 0), is the
+ * position error alone), and the finiteness rule does not depend on the scales.
+ * gram [G][UMPC_GRAM_ROWS][UMPC_GRAM_COLS] is DOUBLE whatever the dtype. Per group of n members:
+ *   [i][j], i, j < 64   Gram[i][j] = sum over the steps k and the components c of y_i,c(k) y_j,c(k); +0 where i or j >= n
+ *   [64][i]             the number of steps at which slot i was scored (0 for i >= n)
+ *   [65][0]             the steps accumulated        [65][1]  n        [65][2..7]  the six scales        [65][8..63]  +0
+ * A group with n > 64 is FLAGGED, not computed and not an error: rows 0..63 are NaN, row 64 is 0, row 65 is as for any
+ * group. A group with n = 0 holds zeros. accumulate = 0 OVERWRITES every word; accumulate = 1 ADDS this window to what the
+ * table holds (the old matrix is the C operand of the first product, the counts add, [65][0] += count), so a chunked run
+ * is accumulated chunk by chunk as `score` is for umpcBatchScore. IT IS THE CALLER'S DUTY TO PASS THE SAME INDEX AND THE SAME
+ * SCALES to every call that accumulates into one table: the kernel does not compare them.
+ * The products run on the matrix cores (v_mfma_f64_16x16x4_f64): one block of four wavefronts per group stages 8 steps of
+ * y in LDS and computes the 10 upper 16 x 16 tiles; the lower triangle is their mirror image, so the stored matrix is
+ * SYMMETRIC BIT FOR BIT. The k index runs over (step ascending, component 0..5 ascending), four per product, a tail padded
+ * with +0. No atomics: a group's table is a function of its member list, the window and the scales alone -- not of G, the
+ * other groups or the run -- and bit-identical from run to run. The order of accumulation INSIDE one product is not
+ * documented, so the contract is a bound and not bit-identity with the numpy mirror (score.py, gram_reference): on data
+ * whose every difference, product and partial sum is exactly representable every word equals the mirror's; otherwise
+ * |gram - mirror| <= (2 N + 2) 2^-53 S_ij with N = 6 x (steps accumulated) and S_ij = sum |y_i,c(k) y_j,c(k)| (the
+ * dot-product bound for any order of N products and N - 1 additions, once for each side; an entry with S_ij = 0 is exactly
+ * 0). Counts and row 65 are exact.
+ * umpcBatchProject: proj [count][G][UMPC_PROJ_ROWS] DOUBLE, overwritten, row i = step first + i. weights [M][B] DOUBLE on the
+ * DEVICE, indexed by robot, 1 <= M <= UMPC_PROJ_MAX. Per (step, group):
+ *   0  members scored          1  members skipped          2 + 6 m + c  sum_b weights[m][b] z_c(b), m < M, c = 0..5
+ * and +0 in every other row. It is umpcBatchDispersion with S1 weighted and S2 dropped: the same 12 words, the same member
+ * rule (a member one of whose M weights is not finite is skipped too), each term one fp64 product, the same order of
+ * summation (lane l adds members l, l + 64, .. from +0, then the tree w = 32 .. 1): BIT-IDENTICAL to the mirror that follows
+ * that order (score.py, project_reference), for every group size -- there is no 64-member limit here. With an eigenvector
+ * of the centred Gram matrix as weights it is the time course of a mode, with 1 / n the mean path, with +-1 on two
+ * clusters their contrast.
+ * Not built: groups larger than 64 in umpcBatchGram; an eigensolver on the device; clustering beyond medoid and rank; a
+ * split of one group's window over several blocks when G is small; attitude components in y.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; state_hist, order, offset, scale, gram, weights or proj NULL; both
+ * or neither of ref_tab and ref; count, first or ref_first < 0; count > 2^31 - 1; G < 1; M outside 1..4; a scale that is
+ * negative or not finite; accumulate other than 0 or 1. count == 0 is a successful no-op, except that umpcBatchGram with
+ * accumulate = 0 writes the table of an empty window (zeros, n, the scales). */
+#define UMPC_GRAM_ROWS 66
+#define UMPC_GRAM_COLS 64
+#define UMPC_PROJ_ROWS 32
+#define UMPC_PROJ_MAX 4
+int umpcBatchGram(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref,
+                  long long first, long long count, long long ref_first, int after,
+                  const int32_t *order, const int32_t *offset, int G,
+                  const double *scale /* host, [6] */, int accumulate, double *gram, void *stream);
+int umpcBatchProject(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref,
+                     long long first, long long count, long long ref_first, int after,
+                     const int32_t *order, const int32_t *offset, int G,
+                     const double *weights /* device, [M][B] */, int M, double *proj, void *stream);
+
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and
  * row offsets within 31 bits; the task generators, per-robot weights, the fused WL step and a reference trajectory are

@@ -31,6 +31,7 @@ DISP_ROWS, ELL_ROWS, MAHA_ROWS = 32, 48, 12
 XMOM_ROWS, PROP_ROWS = 96, 80
 SENS_MAX_FACTORS, SENS_MAX_BINS = 6, 8
 SPEC_EP, SPEC_ES, SPEC_U, SPEC_ROWS, SPEC_MAX_K = 0, 1, 2, 12, 64
+GRAM_ROWS, GRAM_COLS, PROJ_ROWS, PROJ_MAX = 66, 64, 32, 4
 SPEC_SLICES = 2      # UMPC_SPEC_SLICES of csrc/umpc_spectrum.h: part of the order of summation of umpcBatchSpectrum
 NX, NC, NADATA = 45, 39, 48
 
@@ -48,6 +49,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchLagMoments", "umpcBatchPropagators",
            "umpcBatchFactorBins", "umpcBatchSensitivity", "umpcBatchSensitivityIndices", "umpcBatchScoreSensitivity",
            "umpcBatchSpectrumInit", "umpcBatchSpectrum", "umpcBatchSpectrumPower", "umpcBatchSpectrumGroups",
+           "umpcBatchGram", "umpcBatchProject",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -324,6 +326,10 @@ def lib():
         L.umpcBatchSpectrumPower.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
                                              C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.umpcBatchSpectrumGroups.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchGram.argtypes = [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchProject.argtypes = [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

@@ -841,6 +841,100 @@ class BatchUprightMPC:
             self._check(self.L.umpcBatchPropagators(self.h, _ptr(xmom), count, G, _ptr(out), self._stream()))
         return out
 
+    def trajectory_gram(self, index, first=0, count=None, after=False, ref_table=None, ref_first=0, scale=(1, 1, 1, 0, 0, 0),
+                        out=None):
+        """The recorded steps first .. first + count - 1 of the step history as the Gram matrix of the error trajectories of each
+        group's draws [G, 66, 64] float64 on the device (umpcBatchGram; layout: robobee3d_amd/score.py GR_* / GT_* -- rows 0..63
+        Gram[i][j] = sum over the steps and the components of y_i y_j with y = scale * (p - pdes, v - dpdes), member slot i being
+        robot order[offset[g] + i]; row 64 the steps at which each slot was scored; row 65 the steps accumulated, n and the six
+        scales), in ONE pass over the tables on the matrix cores (fp64 MFMA): what relates draw i of a cell to draw j as WHOLE
+        flights, where every other table here is a marginal. trajectory_modes() / trajectory_table() turn it into the cell's
+        medoid flight, the number of ways its draws differ and each draw's score on them. index = group_index(group, G).
+        first, count, after, ref_table and ref_first are those of dispersion(), the reference is resolved as there, and the
+        member rule is dispersion()'s (p, v, pdes and dpdes finite; what is not scored enters as 0 and is counted out in row
+        64). scale: six finite numbers >= 0, the default is the position error alone. A cell of more than 64 members is
+        flagged (rows 0..63 NaN), not computed. `out`, WHEN GIVEN, IS ACCUMULATED INTO: a chunked run passes the table of the
+        first chunk back in (rewind_history() in between) -- with the same index and the same scale, which nobody checks.
+        The matrix is symmetric bit for bit and bit-identical from run to run; against the numpy mirror (score.gram_reference)
+        it is exact on exactly representable data and within (2 N + 2) 2^-53 sum |y_i y_j|, N = 6 x steps, otherwise: the
+        order of accumulation inside an MFMA is not documented. Keep the cells contiguous in the batch (cell = b // 64)."""
+        hist, first, count = self._history_window("trajectory_gram", first, count)
+        order, offset, G = self._group_index_arg("trajectory_gram", index)
+        reftab, rfirst = self._scoring_reference("trajectory_gram", first, count, ref_table, ref_first)
+        accumulate = out is not None
+        out = self._out_arg(out, (G, _lib.GRAM_ROWS, _lib.GRAM_COLS))
+        scale = [float(x) for x in scale]
+        if len(scale) != 6:
+            raise ValueError("trajectory_gram: scale is six numbers")
+        sc = (C.c_double * 6)(*scale)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchGram(self.h, _ptr(hist["state"]), _ptr(reftab),
+                                             None if reftab is not None else _ptr(self.ref), first, count, rfirst,
+                                             int(bool(after)), _ptr(order), _ptr(offset), G, sc, int(accumulate), _ptr(out),
+                                             self._stream()))
+        return out
+
+    def _gram_arg(self, what, gram):
+        if (gram.dim() != 3 or tuple(gram.shape[1:]) != (_lib.GRAM_ROWS, _lib.GRAM_COLS) or gram.dtype != torch.float64
+                or gram.device != self.state.device or not gram.is_contiguous()):
+            raise ValueError("%s: gram must be a contiguous [G, 66, 64] float64 tensor on the handle's device (trajectory_gram())" % what)
+        return gram.cpu().numpy()
+
+    def trajectory_modes(self, gram, M=3):
+        """The ways the draws of each cell differ as whole trajectories, from the table of trajectory_gram(): a dict of numpy
+        arrays (score.trajectory_modes, which documents them -- lam [G, M], share, W [G, 64, M], neff, trace, nvalid, status).
+        The tables are G x 33 KB, so the small dense algebra (centring, numpy.linalg.eigh) is host work, as the poles of the
+        propagators are. A draw that was not finite at any step is left out of its cell."""
+        from .score import trajectory_modes
+        return trajectory_modes(self._gram_arg("trajectory_modes", gram), M)
+
+    def trajectory_table(self, gram, modes, index):
+        """The score-shaped table [12, B] in the handle's dtype on the device of trajectory_gram()'s table and its
+        trajectory_modes() (rows: robobee3d_amd/score.py T_* -- valid, Gram_ii, the squared distance from the cell's mean path,
+        the mean and the smallest squared distance to the other draws, the nearest neighbour, the medoid flag, the rank from
+        the most typical draw to the oddest, the share of the cell's variation, the scores on the first three modes). Row 0
+        is the score's "enters": score_quantiles / score_bootstrap / score_sensitivity take the table unchanged, e.g.
+        score_sensitivity(table, index, bins, nbins, num=9) asks which drawn input explains mode 0. (Robot indices in row 5
+        are exact in fp32 up to 2^24.)"""
+        from .score import trajectory_table
+        order, offset, G = self._group_index_arg("trajectory_table", index)
+        g = self._gram_arg("trajectory_table", gram)
+        if g.shape[0] != G:
+            raise ValueError("trajectory_table: gram has %d cells, the index %d" % (g.shape[0], G))
+        tab = trajectory_table(g, modes, order.cpu().numpy(), offset.cpu().numpy(), self.B)
+        return torch.as_tensor(tab).to(self.dtype).to(self.device).contiguous()
+
+    def mode_weights(self, modes, index, M=None):
+        """weights [M, B] float64 on the device for ensemble_projection() from the eigenvectors of trajectory_modes(): robot
+        order[offset[g] + i] gets W[g][i][m], a robot outside every usable cell 0 (score.mode_weights)."""
+        from .score import mode_weights
+        order, offset, _ = self._group_index_arg("mode_weights", index)
+        return torch.as_tensor(mode_weights(modes, order.cpu().numpy(), offset.cpu().numpy(), self.B, M)).to(self.device).contiguous()
+
+    def ensemble_projection(self, index, weights, first=0, count=None, after=False, ref_table=None, ref_first=0, out=None):
+        """The recorded steps first .. first + count - 1 of the step history as weighted sums of the error state over each group's
+        draws [count, G, 32] float64 on the device (umpcBatchProject; rows: robobee3d_amd/score.py P_* -- members scored /
+        skipped, then row 2 + 6 m + c = sum_b weights[m][b] z_c(b) for the M <= 4 weight vectors): dispersion() with S1 weighted
+        and S2 dropped. weights [M, B] float64 by robot -- mode_weights() of a cell's eigenvectors gives the time course of its
+        modes, 1 / n the mean path, +-1 on two clusters their contrast. A member is scored when p, v, pdes, dpdes and its M
+        weights are finite. index, first, count, after, ref_table, ref_first and out are those of dispersion(). Bit-identical to
+        score.project_reference, for every cell size."""
+        hist, first, count = self._history_window("ensemble_projection", first, count)
+        order, offset, G = self._group_index_arg("ensemble_projection", index)
+        reftab, rfirst = self._scoring_reference("ensemble_projection", first, count, ref_table, ref_first)
+        if not torch.is_tensor(weights):
+            weights = torch.as_tensor(np.asarray(weights, np.float64)).to(self.device)
+        if (weights.dim() != 2 or not 1 <= int(weights.shape[0]) <= _lib.PROJ_MAX or int(weights.shape[1]) != self.B
+                or weights.dtype != torch.float64 or weights.device != self.state.device or not weights.is_contiguous()):
+            raise ValueError("weights must be a contiguous [M, %d] float64 tensor on the handle's device, 1 <= M <= 4" % self.B)
+        out = self._out_arg(out, (count, G, _lib.PROJ_ROWS))
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchProject(self.h, _ptr(hist["state"]), _ptr(reftab),
+                                                None if reftab is not None else _ptr(self.ref), first, count, rfirst,
+                                                int(bool(after)), _ptr(order), _ptr(offset), G, _ptr(weights),
+                                                int(weights.shape[0]), _ptr(out), self._stream()))
+        return out
+
     def _bins_arg(self, what, bins, nbins):
         from .score import SENS_MAX_BINS, SENS_MAX_FACTORS
         M = int(nbins)

@@ -1,7 +1,7 @@
 // libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchSpectrumGroups) and their
 // host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
-// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h, umpc_sensitivity.h and umpc_spectrum.h: nothing here reads
-// the step path or a generated header.
+// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h, umpc_sensitivity.h, umpc_spectrum.h and umpc_gram.h: nothing
+// here reads the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,6 +18,7 @@
 #include "umpc_propagator.h" // per-step, per-group lagged moments and the affine map between two steps (umpcBatchLagMoments ..)
 #include "umpc_sensitivity.h" // per-step, per-group binned sums over the drawn inputs and their correlation ratios (umpcBatchSensitivity ..)
 #include "umpc_spectrum.h" // per-robot projections onto a temporal basis, periodograms and their per-group sums (umpcBatchSpectrum ..)
+#include "umpc_gram.h"     // per-group Gram matrix of the error trajectories (fp64 MFMA) and weighted sums over a group's draws (umpcBatchGram ..)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -410,6 +411,37 @@ static int launch_spectrum_groups(umpc_batch_t *h, const void *power, const void
   return launch_status("umpcBatchSpectrumGroups");
 }
 
+// (the window of launch_dispersion; one block per cell, whatever G and the window)
+template <typename T>
+static int launch_gram(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G, const double *scale,
+                       int accumulate, double *gram, void *stream) {
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, 0, nullptr);
+  umpc::GramArgs<T> a;
+  a.t.state = t.state; a.t.reftab = t.reftab; a.t.ref = t.ref; a.t.order = order; a.t.offset = offset; a.t.mom = nullptr;
+  a.t.B = t.B; a.t.count = t.count; a.t.G = G;
+  for (int c = 0; c < 6; ++c) a.scale[c] = scale[c];
+  a.gram = gram; a.accumulate = accumulate;
+  const dim3 grid((unsigned)G), block(64, umpc::kGramWaves);
+  if (a.t.reftab) hipLaunchKernelGGL((umpc::umpc_gram_kernel<T, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((umpc::umpc_gram_kernel<T, false>), grid, block, 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchGram");
+}
+
+// (the window and the grid of launch_dispersion)
+template <typename T>
+static int launch_project(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G,
+                          const double *weights, int M, double *proj, void *stream) {
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, 0, nullptr);
+  umpc::ProjArgs<T> a;
+  a.t.state = t.state; a.t.reftab = t.reftab; a.t.ref = t.ref; a.t.order = order; a.t.offset = offset; a.t.mom = nullptr;
+  a.t.B = t.B; a.t.count = t.count; a.t.G = G;
+  a.weights = weights; a.proj = proj; a.M = M;
+  const dim3 grid((unsigned)G, step_slices(G, w.count, umpc::kDispWaves)), block(64, umpc::kDispWaves);
+  if (a.t.reftab) hipLaunchKernelGGL((umpc::umpc_project_kernel<T, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((umpc::umpc_project_kernel<T, false>), grid, block, 0, (hipStream_t)stream, a);
+  return launch_status("umpcBatchProject");
+}
+
 static int check_freqs(const char *fn, int K) {
   return K < 1 || K > UMPC_SPEC_MAX_K ? refuse(fn, "bad argument (1 <= K <= 64 frequencies)") : 0;
 }
@@ -745,6 +777,35 @@ int umpcBatchSpectrumGroups(umpc_batch_t *h, const void *power, const void *spec
   if (check_groups(fn, G) || check_freqs(fn, K)) return -1;
   return h->dtype == UMPC_F32 ? launch_spectrum_groups<float>(h, power, spec, order, offset, G, K, gspec, stream)
                               : launch_spectrum_groups<double>(h, power, spec, order, offset, G, K, gspec, stream);
+}
+
+int umpcBatchGram(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, long long first, long long count,
+                  long long ref_first, int after, const int32_t *order, const int32_t *offset, int G, const double *scale,
+                  int accumulate, double *gram, void *stream) {
+  const char *fn = "umpcBatchGram";
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !scale || !gram) return refuse(fn, "bad argument (state_hist, order, offset, scale and gram must be given)");
+  if (check_window(fn, w) || check_groups(fn, G)) return -1;
+  for (int c = 0; c < 6; ++c)
+    if (!(scale[c] >= 0) || !(scale[c] <= 1.79769313486231570815e308)) return refuse(fn, "bad argument (the six scales must be finite and >= 0)");
+  if (accumulate != 0 && accumulate != 1) return refuse(fn, "bad argument (accumulate is 0 or 1)");
+  if (count == 0 && accumulate) return 0;      // (count == 0 without accumulate writes the table of an empty window)
+  return h->dtype == UMPC_F32 ? launch_gram<float>(h, w, order, offset, G, scale, accumulate, gram, stream)
+                              : launch_gram<double>(h, w, order, offset, G, scale, accumulate, gram, stream);
+}
+int umpcBatchProject(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, long long first, long long count,
+                     long long ref_first, int after, const int32_t *order, const int32_t *offset, int G, const double *weights, int M,
+                     double *proj, void *stream) {
+  const char *fn = "umpcBatchProject";
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!state_hist || !order || !offset || !weights || !proj) return refuse(fn, "bad argument (state_hist, order, offset, weights and proj must be given)");
+  if (check_window(fn, w) || check_groups(fn, G)) return -1;
+  if (M < 1 || M > UMPC_PROJ_MAX) return refuse(fn, "bad argument (1 <= M <= 4 weight vectors)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_project<float>(h, w, order, offset, G, weights, M, proj, stream)
+                              : launch_project<double>(h, w, order, offset, G, weights, M, proj, stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,9 @@ and for the moments, ellipsoids and Mahalanobis scores of umpcBatchDispersion / 
 umpcBatchMahalanobis (dispersion / dispersion_ellipsoids / mahalanobis), the propagators, the binned sums and
 correlation ratios of umpcBatchFactorBins / umpcBatchSensitivity / umpcBatchSensitivityIndices / umpcBatchScoreSensitivity
 (factor_bins / sensitivity / sensitivity_indices / score_sensitivity) and, at the end, the projections, periodograms and
-per-group spectra of umpcBatchSpectrum / umpcBatchSpectrumPower / umpcBatchSpectrumGroups (spectrum / spectrum_groups).
+per-group spectra of umpcBatchSpectrum / umpcBatchSpectrumPower / umpcBatchSpectrumGroups (spectrum / spectrum_groups), and
+the Gram matrices, trajectory modes and weighted sums of umpcBatchGram / umpcBatchProject (trajectory_gram / trajectory_modes /
+trajectory_table / ensemble_projection).
 
 A score [12, B] condenses what every closed-loop step of a run did against its reference; a group table [G, 8] condenses the
 scores of the robots of each group -- the draws of one grid cell of a gain sweep, the end of the reference's gainTuningSims
@@ -733,6 +735,21 @@ def _error_state(y, r, dtype):
     return np.isfinite(a).all(0) & np.isfinite(b).all(0), z
 
 
+def _lane_fold(terms):
+    """[rows] from terms [rows, n] of the n members of a group in list order, IN THE DEVICE'S ORDER (disp_store,
+    csrc/umpc_dispersion.h): lane l of 64 starts at +0 and adds the terms of members l, l + 64, ..; then for w = 32, 16, .., 1
+    lane l becomes (lane l) + (lane l ^ w)"""
+    lanes = np.arange(64)
+    part = np.zeros((terms.shape[0], 64))
+    with np.errstate(over="ignore", invalid="ignore"):
+        for m0 in range(0, terms.shape[1], 64):
+            t = terms[:, m0:m0 + 64]
+            part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
+        for w in (32, 16, 8, 4, 2, 1):
+            part = part + part[:, lanes ^ w]
+    return part[:, 0]
+
+
 def dispersion_reference(state_hist, ref, first, count, ref_first, after, order, offset, dtype=np.float64):
     """umpcBatchDispersion in numpy, IN THE DEVICE'S ORDER OF SUMMATION: [count, G, 32] float64. The tables, first, count,
     ref_first and after are those of ensemble_reference (no out, no status); dtype is the handle's: the differences are
@@ -748,7 +765,6 @@ def dispersion_reference(state_hist, ref, first, count, ref_first, after, order,
     if count < 0 or first < 0 or ref_first < 0 or G < 1:
         raise ValueError("dispersion_reference: bad argument")
     mom = np.zeros((count, G, DISP_ROWS))
-    lanes = np.arange(64)
     for i in range(count):
         ok, z = _error_state(st[first + i + after], ref[ref_first + i] if ref.ndim == 3 else ref, dtype)
         z = np.where(ok, z, 0.0)
@@ -756,16 +772,9 @@ def dispersion_reference(state_hist, ref, first, count, ref_first, after, order,
             terms = np.concatenate([z, np.stack([z[a] * z[b] for a, b in DISP_PAIRS])])       # [27, B]
         for g in range(G):
             mem = order[offset[g]:offset[g + 1]]
-            part = np.zeros((27, 64))
-            for m0 in range(0, len(mem), 64):
-                t = terms[:, mem[m0:m0 + 64]]
-                part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
-            with np.errstate(over="ignore", invalid="ignore"):
-                for w in (32, 16, 8, 4, 2, 1):
-                    part = part + part[:, lanes ^ w]
             scored = int(ok[mem].sum())
             mom[i, g, D_N], mom[i, g, D_SKIPPED] = scored, len(mem) - scored
-            mom[i, g, D_S1:D_S1 + 27] = part[:, 0]
+            mom[i, g, D_S1:D_S1 + 27] = _lane_fold(terms[:, mem])
     return mom
 
 
@@ -1574,3 +1583,262 @@ def combine_spectra(parts):
     for p in parts[1:]:
         total = total + p
     return total
+
+
+# ---- trajectory modes (umpcBatchGram / umpcBatchProject) ------------------------------------------------------------------------
+GRAM_ROWS, GRAM_COLS, PROJ_ROWS, PROJ_MAX = 66, 64, 32, 4
+# Gram table, per group [66, 64]: rows 0..63 the matrix over member slots (slot i = order[offset[g] + i]); row GR_COUNTS the steps
+# at which each slot was scored; row GR_TAIL: the steps accumulated, n, the six scales, zeros
+GR_COUNTS, GR_TAIL = 64, 65
+GT_STEPS, GT_N, GT_SCALE = 0, 1, 2
+GRAM_DEFAULT_SCALE = (1.0, 1.0, 1.0, 0.0, 0.0, 0.0)      # the position error alone
+# projection rows, per (step, group): members scored / skipped, then row P_FIRST + 6 m + c = sum_b weights[m][b] z_c(b)
+P_N, P_SKIPPED, P_FIRST = 0, 1, 2
+# status of a cell in trajectory_modes: usable; fewer than two valid members; trace(Gc) <= 0 (all valid draws on one path); n > 64
+MODES_OK, MODES_FEW, MODES_FLAT, MODES_BIG = 0, 1, 2, 3
+# trajectory table rows, per robot [12, B] (score-shaped: score_quantiles / score_bootstrap / score_sensitivity take it unchanged):
+#   0  1 when the robot is a valid member of a usable cell (the "enters" convention of a score), else 0 and rows 1..11 are 0
+#   1  Gram_ii, the squared length of the robot's error path        2  Gc_ii, its squared distance from the cell's mean path
+#   3  the mean of D2_ij = Gram_ii + Gram_jj - 2 Gram_ij over the other valid members        4  the smallest such D2
+#   5  the robot index of that nearest neighbour (ties: the lowest slot)
+#   6  1 for the cell's medoid: the minimum of row 3, ties to the lowest slot
+#   7  the rank of row 3 inside the cell, 0 = the most typical (ties: the lowest slot first)
+#   8  Gc_ii / trace(Gc), the robot's share of the cell's variation
+#   9..11  the mode scores sqrt(lam_m) W_im, m = 0..2 (0 beyond M)
+(T_VALID, T_GII, T_GCII, T_MEAN_D2, T_MIN_D2, T_NEAREST, T_MEDOID, T_RANK, T_SHARE, T_MODE0, T_MODE1, T_MODE2) = range(12)
+TRAJ_ROW_NAMES = ("valid", "gram_ii", "gc_ii", "mean_d2", "min_d2", "nearest", "medoid", "rank", "share", "mode0", "mode1", "mode2")
+
+
+def _check_scale(what, scale):
+    scale = np.asarray(scale, np.float64)
+    if scale.shape != (6,) or not np.all(np.isfinite(scale)) or np.any(scale < 0):
+        raise ValueError("%s: scale is six finite numbers >= 0" % what)
+    return scale
+
+
+def gram_reference(state_hist, ref, first, count, ref_first, after, order, offset, scale=GRAM_DEFAULT_SCALE, accumulate=False,
+                   gram=None, dtype=np.float64):
+    """umpcBatchGram in numpy: [G, 66, 64] float64. The tables, first, count, ref_first, after, order, offset and dtype are
+    those of dispersion_reference, and so is the data rule: a (member, step) is scored when its 12 words are finite, each
+    difference is formed in `dtype` and widened, y_c = scale[c] * z_c is one fp64 product, and what is not scored is y = +0.
+    Gram[i][j] is summed over k = (step ascending, component 0..5 ascending) in that order, one rounded product and one rounded
+    addition per term, from +0 or -- accumulate=True -- from the matrix of `gram`, whose counts and steps add. THE KERNEL'S ORDER
+    INSIDE ONE MFMA IS NOT DOCUMENTED AND NOT FOLLOWED: kernel and mirror agree bit for bit on exactly representable data and
+    within (2 N + 2) 2^-53 sum |y_i y_j|, N = 6 x steps accumulated, otherwise (each side is within (N + 1) 2^-53 of the exact
+    sum). A cell of n > 64 members is flagged: rows 0..63 NaN, row 64 zero."""
+    st = np.asarray(state_hist)
+    ref = np.asarray(ref)
+    order, offset = np.asarray(order), np.asarray(offset)
+    first, count, ref_first, after = int(first), int(count), int(ref_first), int(bool(after))
+    G = len(offset) - 1
+    if count < 0 or first < 0 or ref_first < 0 or G < 1:
+        raise ValueError("gram_reference: bad argument")
+    scale = _check_scale("gram_reference", scale)
+    if accumulate:
+        if gram is None or np.shape(gram) != (G, GRAM_ROWS, GRAM_COLS):
+            raise ValueError("gram_reference: accumulate needs gram [G, 66, 64]")
+        out = np.array(gram, np.float64)
+        if count == 0:
+            return out
+    else:
+        out = np.zeros((G, GRAM_ROWS, GRAM_COLS))
+    B = st.shape[-1]
+    oks, ys = np.zeros((count, B), bool), np.zeros((count, 6, B))
+    for i in range(count):
+        ok, z = _error_state(st[first + i + after], ref[ref_first + i] if ref.ndim == 3 else ref, dtype)
+        with np.errstate(over="ignore", invalid="ignore"):
+            oks[i], ys[i] = ok, scale[:, None] * np.where(ok, z, 0.0)
+    for g in range(G):
+        mem = order[offset[g]:offset[g + 1]]
+        n = len(mem)
+        t = out[g]
+        t[GR_TAIL, GT_STEPS] += count
+        t[GR_TAIL, GT_N] = n
+        t[GR_TAIL, GT_SCALE:GT_SCALE + 6] = scale
+        t[GR_TAIL, GT_SCALE + 6:] = 0.0
+        if n > GRAM_COLS:
+            t[:GRAM_COLS], t[GR_COUNTS] = np.nan, 0.0
+            continue
+        acc = t[:n, :n].copy()
+        yg = ys[:, :, mem]
+        with np.errstate(over="ignore", invalid="ignore"):
+            for i in range(count):
+                for c in range(6):
+                    acc = acc + np.multiply.outer(yg[i, c], yg[i, c])
+        t[:n, :n] = acc
+        t[GR_COUNTS, :n] += oks[:, mem].sum(0)
+    return out
+
+
+def combine_grams(parts):
+    """The Gram table of a whole window from the tables [G, 66, 64] of the pieces it is cut into (the same cells, the same
+    scales): the matrices, the counts and the steps add, as they do on the device with accumulate = 1 -- bit for bit on exactly
+    representable data, else to the rounding of one more addition per part. n and the scales of the parts must agree:
+    ValueError otherwise. numpy arrays or torch tensors; the result is of the first part's kind and the parts are not modified."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_grams: no parts")
+    total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
+    for p in parts[1:]:
+        if tuple(p.shape) != tuple(total.shape) or not bool((p[:, GR_TAIL, GT_N:GT_SCALE + 6] == total[:, GR_TAIL, GT_N:GT_SCALE + 6]).all()):
+            raise ValueError("combine_grams: the parts are tables of different cells or scales (n and the six scales must agree)")
+        total[:, :GR_TAIL] = total[:, :GR_TAIL] + p[:, :GR_TAIL]
+        total[:, GR_TAIL, GT_STEPS] = total[:, GR_TAIL, GT_STEPS] + p[:, GR_TAIL, GT_STEPS]
+    return total
+
+
+def project_reference(state_hist, ref, first, count, ref_first, after, order, offset, weights, dtype=np.float64):
+    """umpcBatchProject in numpy, IN THE DEVICE'S ORDER OF SUMMATION: [count, G, 32] float64. weights [M, B], 1 <= M <= 4, by robot.
+    The dispersion mirror with S1 weighted and S2 dropped: a member is scored when its 12 words AND its M weights are finite;
+    its term for row 2 + 6 m + c is the one fp64 product weights[m] * z_c, and (+0) * (+0) when it is not scored; the fold is
+    dispersion_reference's (_lane_fold). The kernel's bits, for every cell size."""
+    st = np.asarray(state_hist)
+    ref = np.asarray(ref)
+    order, offset = np.asarray(order), np.asarray(offset)
+    weights = np.asarray(weights, np.float64)
+    first, count, ref_first, after = int(first), int(count), int(ref_first), int(bool(after))
+    G = len(offset) - 1
+    if count < 0 or first < 0 or ref_first < 0 or G < 1:
+        raise ValueError("project_reference: bad argument")
+    if weights.ndim != 2 or not 1 <= weights.shape[0] <= PROJ_MAX or weights.shape[1] != st.shape[-1]:
+        raise ValueError("project_reference: weights is [M, B] with 1 <= M <= 4")
+    M = weights.shape[0]
+    wfin = np.isfinite(weights).all(0)
+    proj = np.zeros((count, G, PROJ_ROWS))
+    for i in range(count):
+        ok, z = _error_state(st[first + i + after], ref[ref_first + i] if ref.ndim == 3 else ref, dtype)
+        ok = ok & wfin
+        z = np.where(ok, z, 0.0)
+        w = np.where(ok, weights, 0.0)
+        with np.errstate(over="ignore", invalid="ignore"):
+            terms = (w[:, None, :] * z[None, :, :]).reshape(6 * M, -1)       # [6 M, B], row 6 m + c
+        for g in range(G):
+            mem = order[offset[g]:offset[g + 1]]
+            scored = int(ok[mem].sum())
+            proj[i, g, P_N], proj[i, g, P_SKIPPED] = scored, len(mem) - scored
+            proj[i, g, P_FIRST:P_FIRST + 6 * M] = _lane_fold(terms[:, mem])
+    return proj
+
+
+def _valid_slots(t):
+    """the member slots of one Gram table [66, 64] that were scored at every accumulated step"""
+    n = int(t[GR_TAIL, GT_N])
+    return np.nonzero((np.arange(GRAM_COLS) < n) & (t[GR_COUNTS] == t[GR_TAIL, GT_STEPS]))[0]
+
+
+def _centred(gv):
+    """H gv H with H = I - 11^T / n, symmetric by construction"""
+    gc = gv - gv.mean(0)[None, :]
+    gc = gc - gc.mean(1)[:, None]
+    return 0.5 * (gc + gc.T)
+
+
+def trajectory_modes(gram, M=3):
+    """The ways the draws of each cell differ AS WHOLE TRAJECTORIES, from the Gram tables [G, 66, 64] of umpcBatchGram /
+    gram_reference (numpy; the small dense algebra stays on the host, as propagator_poles does). Per cell, on its VALID slots
+    only -- slot i < n with gram[g][64][i] == gram[g][65][0]: a draw that was not finite at any step is left out, not zero-filled
+    --: Gc = H Gram H, the doubly centred matrix (H = I - 11^T / nvalid: the cell's mean path is removed), and its
+    eigen-decomposition by numpy.linalg.eigh. Returns a dict of
+      lam [G, M]      the M largest eigenvalues, descending (0 beyond nvalid)      share [G, M]   lam / trace(Gc)
+      W [G, 64, M]    their eigenvectors over the member slots, 0 on slots that are not valid; the component of largest
+                      magnitude is positive, ties to the lowest slot (the rule of the ellipsoids' eigenvectors)
+      neff [G]        trace(Gc)^2 / sum of all lambda^2: the number of ways the cell really varies (1: one drift direction)
+      trace [G], nvalid [G], status [G]: 0 usable, 1 fewer than two valid members, 2 trace(Gc) <= 0, 3 the cell had n > 64.
+    lam, share, W, neff and trace of a cell that is not usable are NaN. sqrt(lam_m) W_im is draw i's score on mode m
+    (trajectory_table); umpcBatchProject with W[:, :, m] as weights is the mode's time course."""
+    gram = np.asarray(gram, np.float64)
+    M = int(M)
+    if gram.ndim != 3 or gram.shape[1:] != (GRAM_ROWS, GRAM_COLS) or not 1 <= M <= GRAM_COLS:
+        raise ValueError("trajectory_modes: gram is [G, 66, 64] and 1 <= M <= 64")
+    G = gram.shape[0]
+    res = dict(lam=np.full((G, M), np.nan), share=np.full((G, M), np.nan), W=np.full((G, GRAM_COLS, M), np.nan),
+               neff=np.full(G, np.nan), trace=np.full(G, np.nan), nvalid=np.zeros(G, np.int64), status=np.zeros(G, np.int64))
+    for g in range(G):
+        t = gram[g]
+        if t[GR_TAIL, GT_N] > GRAM_COLS:
+            res["status"][g] = MODES_BIG
+            continue
+        v = _valid_slots(t)
+        res["nvalid"][g] = len(v)
+        if len(v) < 2:
+            res["status"][g] = MODES_FEW
+            continue
+        gc = _centred(t[np.ix_(v, v)])
+        tr = float(np.trace(gc))
+        if not tr > 0:
+            res["status"][g] = MODES_FLAT
+            continue
+        lam, vec = np.linalg.eigh(gc)
+        lam, vec = lam[::-1], vec[:, ::-1]
+        m = min(M, len(v))
+        W = np.zeros((GRAM_COLS, M))
+        for k in range(m):
+            w = vec[:, k]
+            big = w[int(np.argmax(np.abs(w)))]          # (argmax takes the lowest slot on a tie)
+            W[v, k] = -w if big < 0 else w
+        res["lam"][g], res["share"][g] = 0.0, 0.0
+        res["lam"][g, :m] = lam[:m]
+        res["share"][g, :m] = lam[:m] / tr
+        res["W"][g] = W
+        res["neff"][g] = tr * tr / float(np.sum(lam * lam))
+        res["trace"][g] = tr
+    return res
+
+
+def trajectory_table(gram, modes, order, offset, B):
+    """The score-shaped table [12, B] float64 of the Gram tables [G, 66, 64] and their trajectory_modes (rows: T_* above): per
+    robot that is a valid member of a usable cell, how long its error path is, how far it is from the cell's mean path and
+    from the other draws (D2_ij = Gram_ii + Gram_jj - 2 Gram_ij), its nearest neighbour, whether it is the cell's medoid --
+    the flight to plot as "the typical one" --, its rank from the most typical to the oddest, and its scores on the first
+    three modes. Every other robot has zeros. order, offset: the index the Gram tables were computed with."""
+    gram = np.asarray(gram, np.float64)
+    order, offset = np.asarray(order), np.asarray(offset)
+    G = len(offset) - 1
+    if gram.shape != (G, GRAM_ROWS, GRAM_COLS) or len(modes["status"]) != G:
+        raise ValueError("trajectory_table: gram, modes and the index are of different numbers of cells")
+    tab = np.zeros((12, int(B)))
+    for g in range(G):
+        if modes["status"][g] != MODES_OK:
+            continue
+        t = gram[g]
+        v = _valid_slots(t)
+        rob = order[offset[g] + v]
+        gv = t[np.ix_(v, v)]
+        d = np.diag(gv)
+        d2 = (d[:, None] + d[None, :]) - 2.0 * gv
+        gc = np.diag(_centred(gv))
+        nv = len(v)
+        mean_d2 = (d2.sum(1) - np.diag(d2)) / (nv - 1)
+        off = d2 + np.where(np.eye(nv, dtype=bool), np.inf, 0.0)
+        near = np.argmin(off, 1)                      # (argmin takes the lowest slot on a tie)
+        by = np.argsort(mean_d2, kind="stable")
+        rank = np.empty(nv)
+        rank[by] = np.arange(nv)
+        tab[T_VALID, rob] = 1.0
+        tab[T_GII, rob], tab[T_GCII, rob] = d, gc
+        tab[T_MEAN_D2, rob], tab[T_MIN_D2, rob] = mean_d2, off[np.arange(nv), near]
+        tab[T_NEAREST, rob] = rob[near]
+        tab[T_MEDOID, rob[by[0]]] = 1.0
+        tab[T_RANK, rob] = rank
+        tab[T_SHARE, rob] = gc / modes["trace"][g]
+        lam, W = modes["lam"][g], modes["W"][g]
+        for k in range(min(3, W.shape[1])):
+            tab[T_MODE0 + k, rob] = np.sqrt(max(lam[k], 0.0)) * W[v, k]
+    return tab
+
+
+def mode_weights(modes, order, offset, B, M=None):
+    """weights [M, B] float64 for umpcBatchProject / project_reference from the eigenvectors W [G, 64, M'] of trajectory_modes:
+    weights[m][order[offset[g] + i]] = W[g][i][m] for the member slots of every usable cell, 0 for every other robot. M None =
+    all the modes there are, 4 at the most."""
+    order, offset = np.asarray(order), np.asarray(offset)
+    W = modes["W"]
+    M = min(W.shape[2], PROJ_MAX) if M is None else int(M)
+    if not 1 <= M <= min(W.shape[2], PROJ_MAX):
+        raise ValueError("mode_weights: 1 <= M <= min(the modes computed, 4)")
+    out = np.zeros((M, int(B)))
+    for g in range(len(offset) - 1):
+        n = int(offset[g + 1] - offset[g])
+        if modes["status"][g] == MODES_OK and n <= GRAM_COLS:
+            out[:, order[offset[g]:offset[g + 1]]] = W[g, :n, :M].T
+    return out
