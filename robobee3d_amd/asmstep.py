@@ -129,7 +129,23 @@ NT_PTRS = ("state", "ctrl", "ref", "out", "stats")
 # The ten AGPRs nobody owns (the loop: a0..a229, the weights: a230..a245) take c and the first nine D words across the loop
 # instead of workspace rows (lane form only: the quad entry composes words in AGPRs): 10 stores + 10 loads fewer per step
 A_SPARE, N_SPARE_D = 246, 9
-
+# WIDE ROWS (lane form): the ITERATES x, y, z between the steps of one launch. Inside a launch nobody can look at `ctrl`
+# between two steps, so only the first step reads its public x, y, z rows and only the last one writes them (K = 1: exactly
+# the public accesses); step k leaves x, y, z in `ws` and step k + 1 loads them -- not on [row][B] rows but in GROUPS of
+# four words per lane, [group][lane][4]: one global_store_dwordx4 / global_load_dwordx4 per group, a lane stride of 16 B, so a
+# wave's access is one contiguous 1-KB segment and a group is 4 * stride bytes from the next. A LOAD of the lone wave costs
+# per instruction, not per byte (profiles/r03_microbench_vmem.txt); a store costs per byte
+# (profiles/microbench_vmem_store.txt) and is wide only because the load wants the words side by side. Same bytes, a quarter
+# of the instructions and of the address updates between them (profiles/wide_rows_ab.txt). The groups are the loop's own
+# register homes in order -- x | y slots as one run of 86 registers (21 groups and a two-word one), then the 40 z slots -- so
+# no register is copied, and the pad slots ride along. T0 and the thrust-row E words keep their public rows on every step.
+# `ws` keeps pointing at workspace row WS_DS, where the parked D, E, c rows stay as they are (rows 0..84 behind the pointer:
+# tests/test_asm_quad.py compares them with the quad stream's); the groups start behind them.
+WIDE_ITER = [(V_X + 4 * g, 4) for g in range(21)] + [(V_X + 84, 2)] + [(V_Z + 4 * g, 4) for g in range(10)]   # (first register, words)
+assert V_X % 2 == 0 and V_Z == V_X + 86 and V_Z % 2 == 0
+WIDE_FIRST = (asmgen.WS_C - asmgen.WS_DS + 1 + 3) // 4     # the first group behind the rows D, E, c
+WIDE_GROUPS = WIDE_FIRST + len(WIDE_ITER)
+WIDE_ROWS = 4 * WIDE_GROUPS       # the groups end this many [row][B] rows behind workspace row WS_DS (the host sizes `ws` by it)
 
 class Pool:
     """VGPR bookkeeping for the straight-line phases: explicit get / free, aligned pairs and quads, peak tracking.
@@ -331,12 +347,15 @@ class Struct:
 # The generator
 # ----------------------------------------------------------------------------------------------------------
 class StepGen:
-    def __init__(self, N=3, perm=None, quad=False, exact_ruiz=False):
+    def __init__(self, N=3, perm=None, quad=False, exact_ruiz=False, narrow_rows=False):
         """quad: one robot per lane QUAD (asmquad.py) -- every phase runs redundantly in the four lanes of a quad and the
         ADMM iterations from the second on split the unknowns over lanes 0..2; the stream of the latency-bound shapes
         (B = 1 drop-in, batches that cannot give every SIMD a wave).
         exact_ruiz: the lane form with all ten Ruiz passes through the exact limit_scaling body and no speculation -- the
-        stream the shipped one must equal bit for bit (tests/test_ruiz_fast_path.py); never written to a header."""
+        stream the shipped one must equal bit for bit (tests/test_ruiz_fast_path.py); never written to a header.
+        narrow_rows: the lane form with x, y, z on their public rows of `ctrl` on every step of a launch, one one-word access
+        each -- the stream before the four-word groups (WIDE ROWS above), kept for comparison (tests/test_wide_rows.py, A/B
+        builds); never written to a header. The quad form is always narrow."""
         self.st = Struct(N, perm)
         self.s = self.st.s
         self.e = Emit()
@@ -348,6 +367,10 @@ class StepGen:
         self.ruiz_span = self.restart_at = None           # instruction indices, for the interpreter's counts (simulate)
         self.nt = () if quad else ("nt",)      # cache policy of the streaming rows and of the parked workspace rows
         self.homes = asmgen.Homes(NRING, 0 if quad else XV_N, XV_B)     # the loop's ring and extra homes of L
+        self.wide_iterates = not quad and not narrow_rows      # x, y, z between the steps of a launch in four-word groups
+        # instruction index ranges, for the counts of tests/test_wide_rows.py: every access of the public x, y, z rows of
+        # `ctrl`, and every access of the groups of the in-launch iterates
+        self.public_spans, self.group_spans = [], []
 
     # ---- small emit helpers -----------------------------------------------------------------------------
     def label(self):
@@ -459,6 +482,39 @@ class StepGen:
                 self.adv(voff)
         if own:
             self.pool.free(voff, kill=False)
+
+    # ---- WIDE ROWS: groups of four words per lane in `ws` ------------------------------------------------
+    def groups_ptr(self, voff):
+        """voff = 16 * b + WIDE_FIRST * 4 * stride, s<S_TMP> = 4 * stride (the bytes from one group to the next; it stays
+        until the next rows_ptr)"""
+        e = self.e
+        e("v_lshlrev_b32", v(voff), 2, "v0")
+        e("s_mul_i32", sg(S_TMP), sg(S_INT["stride"]), 4 * WIDE_FIRST)
+        e("v_add_u32", v(voff), sg(S_TMP), v(voff))
+        e("s_lshl_b32", sg(S_TMP), sg(S_INT["stride"]), 2)
+
+    def adv_group(self, voff):
+        self.e("v_add_u32", v(voff), sg(S_TMP), v(voff))
+
+    def iterate_groups(self, voff, reg, load=False, before=None):
+        """the groups of the in-launch iterates (WIDE_ITER), one access each: group k of `n` words moves to / from
+        v[reg(k, base, n) ...], base being its home in the loop's layout; before(k, base, n) emits what fills the registers"""
+        e = self.e
+        k0 = len(e.ins)
+        self.groups_ptr(voff)
+        for k, (base, n) in enumerate(WIDE_ITER):
+            if before:
+                before(k, base, n)
+            r = reg(k, base, n)
+            assert r % 2 == 0
+            vr, w = "v[%d:%d]" % (r, r + n - 1), "dwordx%d" % n
+            if load:
+                e("global_load_" + w, vr, v(voff), sp(S_PTR["ws"]), *self.nt)
+            else:
+                e("global_store_" + w, v(voff), vr, sp(S_PTR["ws"]), *self.nt)
+            if k + 1 < len(WIDE_ITER):
+                self.adv_group(voff)
+        self.group_spans.append((k0, len(e.ins)))
 
     # ---- prologue: parameters and constants into SGPRs ---------------------------------------------------
     def prologue(self):
@@ -1307,11 +1363,29 @@ class StepGen:
         pool.reserve(V_Y, V_Z - V_Y)
         pool.reserve(V_Z, 40)
         voff = 245          # free here: the loop's temporaries start at v214, its extra L registers at v246
-        self.load_rows("ctrl", 0, [V_X + st.xs[r] for r in range(nx)] + [V_Y + st.zs[r] for r in range(nc)] +
-                       [V_Z + st.zs[r] for r in range(nc)], voff)
-        for pad in (V_X + nx, V_Y + nc, V_Z + nc, V_W + nx, V_WZ + nc):
-            e("v_mov_b32", v(pad), 0)
-        e("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
+        public = [V_X + st.xs[r] for r in range(nx)] + [V_Y + st.zs[r] for r in range(nc)] + [V_Z + st.zs[r] for r in range(nc)]
+        pads = (V_X + nx, V_Y + nc, V_Z + nc, V_W + nx, V_WZ + nc)
+        if self.wide_iterates:
+            # WIDE ROWS: the first step of a launch reads the public rows of `ctrl`, every later one the groups the step
+            # before it left in `ws` (phase_c). The pads are load targets there: zero behind the wait
+            lab_first, lab_go = self.label(), self.label()
+            e("s_cmp_eq_u32", sg(S_STEP), 0)
+            e("s_cbranch_scc1", lab_first + "f")
+            self.iterate_groups(voff, lambda k, base, n: base, load=True)
+            e("s_branch", lab_go + "f")
+            e("label", lab_first)
+            k0 = len(e.ins)
+            self.load_rows("ctrl", 0, public, voff)
+            self.public_spans.append((k0, len(e.ins)))
+            e("label", lab_go)
+            e("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
+            for pad in pads:
+                e("v_mov_b32", v(pad), 0)
+        else:
+            self.load_rows("ctrl", 0, public, voff)
+            for pad in pads:
+                e("v_mov_b32", v(pad), 0)
+            e("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
         plan = st.plan
         # the right-hand side of entries whose q / l is structurally zero is formed without the AGPR read (asmgen.body)
         zk = dict(qzero=st.qzero, lzero=st.lzero, homes=self.homes)
@@ -1412,7 +1486,29 @@ class StepGen:
         self.load_rows("ctrl", nx + 2 * nc, [T0], voff)
         e("v_mov_b32", v(DS(nx)), 0)
         # 2. the controller record goes back now (a cold start, if any, rewrites it below): x, y, z
-        zt = [g_() for _ in range(4)]
+        if self.wide_iterates:
+            # WIDE ROWS: every step but the last of the launch leaves x, y, z in the groups of `ws` the next step loads
+            # (admm) instead. The next step's load is issued behind this step's wait below, and nothing rewrites the groups
+            # in between: a Ruiz restart of that step happens ahead of its load, in phase A, which reads no iterate.
+            # z of the dynamics rows comes from the AGPR home of l, slot by slot, through two quads in turn.
+            lab_last, lab_stored = self.label(), self.label()
+            zq = (pool.get4(), pool.get4())
+            zt = list(range(zq[0], zq[0] + 4))
+            row_at = {st.zs[r]: r for r in range(nc)}
+            e("s_sub_i32", sg(S_TMP), sg(S_INT["K"]), 1)
+            e("s_cmp_eq_u32", sg(S_STEP), sg(S_TMP))
+            e("s_cbranch_scc1", lab_last + "f")
+
+            def fill(k, base, n):
+                if V_Z <= base < V_Z + neq:
+                    for i in range(n):
+                        e("v_accvgpr_read_b32", v(zq[k % 2] + i), "a%d" % (A_LO + row_at[base - V_Z + i]))
+            self.iterate_groups(voff, lambda k, base, n: zq[k % 2] if V_Z <= base < V_Z + neq else base, before=fill)
+            e("s_branch", lab_stored + "f")
+            e("label", lab_last)
+        else:
+            zt = [g_() for _ in range(4)]
+        k0 = len(e.ins)
         self.rows_ptr(voff, 0)
         for r in range(nx):
             e("global_store_dword", v(voff), v(XR(r)), sp(S_PTR["ctrl"]), *self.nt)
@@ -1428,7 +1524,12 @@ class StepGen:
             else:
                 e("global_store_dword", v(voff), v(ZR(r)), sp(S_PTR["ctrl"]), *self.nt)
             self.adv(voff)
-        pool.free(*zt)
+        self.public_spans.append((k0, len(e.ins)))
+        if self.wide_iterates:
+            e("label", lab_stored)
+            pool.free(*zt, *range(zq[1], zq[1] + 4))
+        else:
+            pool.free(*zt)
         e("s_waitcnt", "vmcnt(0)")
         # 3. unscaled step and solution: dxu = D dx (in W), xu = D x (in X)
         for k in range(0, nx + 1, 2):
@@ -1789,10 +1890,25 @@ class StepGen:
         e("s_and_saveexec_b64", sp(S_M1), MBAD)
         e("s_cbranch_execz", lab_c + "f")
         e("v_mov_b32", v(a1), 0)
+        if self.wide_iterates:
+            # WIDE ROWS: ... in the groups where the next step of the launch looks for them, on the public rows after the last
+            lab_cl = self.label()
+            zq = pool.get4()
+            for i in range(4):
+                e("v_mov_b32", v(zq + i), 0)
+            e("s_sub_i32", sg(S_TMP), sg(S_INT["K"]), 1)
+            e("s_cmp_eq_u32", sg(S_STEP), sg(S_TMP))
+            e("s_cbranch_scc1", lab_cl + "f")
+            self.iterate_groups(voff, lambda k, base, n: zq)
+            e("s_branch", lab_c + "f")
+            e("label", lab_cl)
+            pool.free(*range(zq, zq + 4), kill=False)
+        k0 = len(e.ins)
         self.rows_ptr(voff, 0)
         for r in range(nx + 2 * nc):
             e("global_store_dword", v(voff), v(a1), sp(S_PTR["ctrl"]))
             self.adv(voff)
+        self.public_spans.append((k0, len(e.ins)))
         e("label", lab_c)
         e("s_mov_b64", "exec", sp(S_M1))
         pool.free(pri, dua, stv, a1, a2, t, T0, *RF)
@@ -2323,11 +2439,13 @@ fmt = functools.partial(asmtext.fmt, hex_ints=asmtext.HEX_ABOVE_64)       # this
 PSEUDO = ("kill", "quad_begin", "quad_end")      # markers for the CPU interpreters, not instructions
 
 
-def write(path=None, N=3, perm=None, quad=False):
+def write(path=None, N=3, perm=None, quad=False, narrow_rows=False):
     """quad: the one-robot-per-lane-quad stream (asmquad.py) -> csrc/umpc_step_asm_quad.h, macro UMPC_STEP_ASM_QUAD; it
-    shares struct StepParams with the one-lane header, which must be included first."""
+    shares struct StepParams with the one-lane header, which must be included first.
+    narrow_rows (StepGen): only with a `path` of the caller's, for A/B builds (tools/build_variant.py)."""
+    assert not narrow_rows or (path and not quad), "the shipped headers carry the default streams"
     path = path or os.path.join(HERE, "csrc", "umpc_step_asm_quad.h" if quad else "umpc_step_asm.h")
-    g = StepGen(N, perm, quad=quad)
+    g = StepGen(N, perm, quad=quad, narrow_rows=narrow_rows)
     ins = [t for t in g.program() if t[0] not in PSEUDO]
     if quad:
         head = ["// GENERATED by robobee3d_amd/asmstep.py (quad=True) + asmquad.py -- do not edit.", asmgen.switch_banner(),
@@ -2359,7 +2477,13 @@ def write(path=None, N=3, perm=None, quad=False):
                 "struct StepArgs {", "  StepParams p;", "  StepHist h;", "  StepImp i;", "};",
                 "static_assert(offsetof(StepArgs, h) == %d && sizeof(StepHist) == %d, \"StepHist layout\");" % (HIST_OFF, HIST_BYTES),
                 "static_assert(offsetof(StepArgs, i) == %d && sizeof(StepImp) == %d && offsetof(StepImp, impstep) == 8, \"StepImp layout\");" % (IMP_OFF, IMP_BYTES),
-                "constexpr int STEP_LDS_BYTES_PER_LANE = %d;" % (NLDS * 4), "}  // namespace umpcasm",
+                "constexpr int STEP_LDS_BYTES_PER_LANE = %d;" % (NLDS * 4),
+                "// `ws` points at workspace row WS_DS. Behind it the stream keeps words only it reads back, in groups of four per",
+                "// lane, [group][lane][4] with 4 * stride bytes per group: behind the %d rows of D, E, c, %d groups of x, y, z"
+                % (4 * WIDE_FIRST, len(WIDE_ITER)),
+                "// between the steps of one launch. The allocation must hold WS_WIDE_ROWS rows of `stride` bytes behind the",
+                "// pointer, and 1 KB more for the last wave of a batch that is no multiple of 64.",
+                "constexpr int WS_WIDE_ROWS = %d;" % WIDE_ROWS, "}  // namespace umpcasm",
                 "// inputs: v0 = 4 * robot, v1 = lane LDS address, s[4:5] = &StepParams (kernarg)"]
     asmtext.write_if_changed(path, asmtext.asm_block(
         head, "UMPC_STEP_ASM%s(voff, ldsaddr, params)" % ("_QUAD" if quad else ""), ins,
@@ -2424,6 +2548,11 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None, lanes=
     regions = [(PBASE, 4, np.frombuffer(bytes(blob), np.uint32))] + \
         [(base_of[n], 4 if n in FLAT or lanes > 1 else STRIDE, arrays[n].reshape(-1))
          for n in PTRS + ["impulse"] if arrays.get(n) is not None]
+    if lanes == 1 and arrays.get("ws") is not None:
+        # WIDE ROWS with one lane: rows are STRIDE bytes apart here, so a group (four words at 16 * lane, 4 * STRIDE bytes from
+        # the next group) has no row to land on. The groups get a flat backing of their own behind the same base address;
+        # one-word accesses keep finding the rows of arrays["ws"] first. (With lanes > 1 the array itself is contiguous.)
+        regions.append((base_of["ws"], 4, np.zeros(WIDE_GROUPS * STRIDE, np.uint32)))
     assert all(arrays[n].flags.c_contiguous for n in PTRS + ["impulse"] if arrays.get(n) is not None)
     m = isasim.Machine(ins, lanes, regions=regions, sgpr={S_PARAM: PBASE & 0xFFFFFFFF, S_PARAM + 1: PBASE >> 32},
                        vgpr={0: 4 * np.arange(lanes)}, lds=np.zeros((lanes, NLDS), np.uint32), max_exec=max_exec,

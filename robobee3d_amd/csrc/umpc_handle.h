@@ -56,7 +56,8 @@ struct umpc_batch {
   double task_p[4] = {0, 0, 0, 0};
   double t_ms = 0;               // time of the next MPC step
   const void *weights = nullptr;  // [8][B] device table or null
-  void *ws;  // [WS_ROWS][B] scratch the step parks Ruiz scalings / x_prev / delta_y in
+  void *ws;  // [WS_ROWS][B] scratch the step parks Ruiz scalings / x_prev / delta_y in; fp32: at least WS_WIDE_ROWS rows and
+             // 1 KB behind row WS_DS, where the lane stream keeps its four-word groups (umpcBatchCreate sizes it)
   int step_kernel = 0;            // 0 = automatic, 1 = always the C++ / loop-assembly kernel, 2 / 3 = the all-assembly stream with one lane / one lane quad per robot
   umpc::WLDev *wl = nullptr;      // device copy of the WL parameters (umpcBatchSetWL), null = no coupling
   void *wlu = nullptr, *wlw = nullptr;

@@ -352,8 +352,10 @@ static int launch_steps(umpc_batch_t *h, int K, int nsub, RolloutArrays io, cons
     // offsets within 31 bits (either plant); UMPC_NO_ASM_STEP=1 forces the C++ / assembly-loop kernel
     static const bool no_asm = getenv("UMPC_NO_ASM_STEP") != nullptr;
     // (32-bit lane offsets inside one array: the largest is ctrl, 127 rows; the kernel's workspace pointer is the row it
-    // parks D, E, c in, so the 559-row workspace does not count)
-    const bool fits = (size_t)UMPC_CTRL_ROWS * (size_t)h->B * 4 < ((size_t)1 << 31);
+    // parks D, E, c in, so the 559-row workspace does not count; the lane stream's four-word groups reach WS_WIDE_ROWS rows
+    // and a wave's 1 KB behind that pointer, an unsigned 32-bit lane offset)
+    const bool fits = (size_t)UMPC_CTRL_ROWS * (size_t)h->B * 4 < ((size_t)1 << 31) &&
+                      (size_t)umpcasm::WS_WIDE_ROWS * (size_t)h->B * 4 + 64 * 16 < ((size_t)1 << 32);
     if (!no_asm && h->step_kernel != 1 && fits && K >= 1 && h->prm.maxIter >= 1) {
       umpcasm::StepArgs pa;
       umpcasm::StepParams &p = pa.p;
@@ -519,7 +521,15 @@ umpc_batch_t *umpcBatchCreate(const umpc_batch_params_t *prm, int B, int dtype) 
   }
   umpc_batch *h = new umpc_batch;
   h->prm = *prm; h->B = B; h->global_B = B; h->dtype = dtype; h->ws = nullptr;
-  e = hipMalloc(&h->ws, (size_t)umpc::WS_ROWS * (size_t)B * (dtype == UMPC_F64 ? 8 : 4));
+  // [WS_ROWS][B]; the fp32 lane stream also keeps four-word groups [group][lane][4] behind row WS_DS (asmstep.py WIDE ROWS):
+  // WS_WIDE_ROWS rows of B words, and 64 lanes x 16 B more, so that the last wave of a batch that is no multiple of 64 could
+  // not leave the allocation even with every lane unmasked
+  size_t ws_bytes = (size_t)umpc::WS_ROWS * (size_t)B * (dtype == UMPC_F64 ? 8 : 4);
+  if (dtype == UMPC_F32) {
+    const size_t wide = ((size_t)umpcasm::WS_DS + (size_t)umpcasm::WS_WIDE_ROWS) * (size_t)B * 4 + 64 * 16;
+    if (wide > ws_bytes) ws_bytes = wide;
+  }
+  e = hipMalloc(&h->ws, ws_bytes);
   if (e != hipSuccess) { fail(e, "umpcBatchCreate: workspace"); delete h; return nullptr; }
   return h;
 }

@@ -678,6 +678,7 @@ VECTOR = {
     "v_and_b32": _bitop(lambda a, b: a & b),
     "v_or_b32": _bitop(lambda a, b: a | b),
     "v_lshrrev_b32": _bitop(lambda a, b: b >> (a & u64(31))),
+    "v_lshlrev_b32": _bitop(lambda a, b: (b << (a & u64(31))) & u64(0xFFFFFFFF)),
     "v_mul_u32_u24": _bitop(lambda a, b: ((a & u64(0xFFFFFF)) * (b & u64(0xFFFFFF))) & u64(0xFFFFFFFF)),
     "v_bfe_u32": lambda mc, t: mc.write(t[1], (mc.bits(t[2]) >> u32(t[3] & 31)) & u32((1 << t[4]) - 1)),
     "v_cvt_f32_i32": lambda mc, t: mc.wf(t[1], mc.bits(t[2]).view(np.int32).astype(f32)),
@@ -720,5 +721,6 @@ for _op in ("lt", "le", "gt", "ge", "eq", "nlt", "neq", "u"):
     VECTOR["v_cmp_%s_f32" % _op] = VECTOR["v_cmp_%s_f32_e64" % _op] = _cmp("f32")
 OPS = dict(SALU, **VECTOR)
 for _m in ("ds_read_b32", "ds_read_b64", "ds_read_b128", "ds_write_b32", "ds_write_b64", "ds_write_b128", "ds_min_f32",
-           "global_load_dword", "global_load_dwordx2", "global_load_dwordx4", "global_store_dword", "global_store_dwordx2"):
+           "global_load_dword", "global_load_dwordx2", "global_load_dwordx4", "global_store_dword", "global_store_dwordx2",
+           "global_store_dwordx4"):
     OPS[_m] = _ds if _m.startswith("ds_") else _global

@@ -2,7 +2,8 @@
 """Builds robobee3d_amd/variants/libumpc_<name>.so from the current sources with generator switches taken from the
 environment (asmgen.SWITCHES), for timing step-kernel variants next to the shipped library in one session (select with UMPC_LIB).
 usage: UMPC_ASM64_TIMING=1 tools/build_variant.py timing64
-       UMPC_VARIANT_DEFS="-DUMPC_SCALING_ITERS=1" tools/build_variant.py ruiz1     (extra compiler flags, timing diagnostics)"""
+       UMPC_VARIANT_DEFS="-DUMPC_SCALING_ITERS=1" tools/build_variant.py ruiz1     (extra compiler flags, timing diagnostics)
+       tools/build_variant.py narrow narrow_rows=1     (the lane stream with x, y, z on their public rows every step, asmstep.StepGen)"""
 import os
 import subprocess
 import sys
@@ -20,7 +21,8 @@ clean = {k: v for k, v in os.environ.items() if k not in asmgen.generator_switch
 subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from robobee3d_amd import _lib; _lib.build()" % ROOT],
                check=True, env=clean)
 hdr = os.path.join(vdir, "umpc_step_asm.h")
-asmstep.write(hdr)
+narrow = dict(a.split("=", 1) for a in sys.argv[2:]).get("narrow_rows", "")
+asmstep.write(hdr, narrow_rows={"": False, "1": True}[narrow])
 obj = os.path.join(vdir, name + ".o")
 csrc = os.path.join(ROOT, "robobee3d_amd", "csrc")
 subprocess.run(["hipcc"] + _lib.HIPCC_FLAGS + os.environ.get("UMPC_VARIANT_DEFS", "").split() + ["-DUMPC_STEP_ASM_HEADER=\"%s\"" % hdr, "-c", "-o", obj, _lib.SRC], check=True, cwd=csrc)
