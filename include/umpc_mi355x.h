@@ -850,7 +850,7 @@ int umpcBatchScoreSensitivity(umpc_batch_t *h, const void *score, const int32_t 
  * w = 32, 16, 8, 4, 2, 1 every lane becomes (itself) + (lane ^ w). A row is a function of the group's member list alone;
  * raw sums ADD over the blocks of a sharded job.
  * Not built: an MFMA Gram product (its order of accumulation is undocumented: no mirror could follow it); Welch averaging
- * over time segments; cross-spectra and coherence; peak interpolation between bins.
+ * over time segments; peak interpolation between bins (cross-spectra and coherence: umpcBatchCrossSpectrum, below).
  * Refused (-1, umpcLastError) BEFORE any launch: h NULL; basis, sums, wsum, freq_hz, power, spec, order, offset or gspec
  * NULL; K outside 1..64; signal outside 0..2; state_hist NULL for UMPC_SPEC_EP / ES, out_hist NULL for UMPC_SPEC_U; both or
  * neither of ref_tab and ref (UMPC_SPEC_EP / ES); count, first, ref_first or basis_first < 0; count > 2^31 - 5; nrows < 0;
@@ -929,6 +929,85 @@ int umpcBatchProject(umpc_batch_t *h, const void *state_hist, const void *ref_ta
                      long long first, long long count, long long ref_first, int after,
                      const int32_t *order, const int32_t *offset, int G,
                      const double *weights /* device, [M][B] */, int M, double *proj, void *stream);
+
+/* Transfer estimates: how the closed loop maps an input onto an output across a band, per grid cell. umpcBatchResponse fits
+ * ONE frequency the caller knows on a pure sine task; umpcBatchSpectrum keeps the power of one signal. A cell's draws are
+ * independent records of the same closed loop: averaged over them, the cross-periodogram of an input x and an output y
+ * gives the H1 estimate of the transfer function at every frequency of the basis, and the coherence, which says where that
+ * estimate can be trusted -- a single record has coherence 1 identically, so only the cell can provide it. A broadband
+ * reference per draw (a random-phase multisine or noise in the table of umpcBatchSetRefTrajectory), random pushes per step
+ * (umpcBatchSetImpulses) or an attitude reference each yield the whole Bode curve of every cell, with an error bar per
+ * frequency, from ONE launch and one scoring pass. All four calls are pure functions of their arguments, take only B and the
+ * dtype from the handle, are asynchronous on `stream` and allocate nothing; everything is fp64 on the device except the
+ * loads; every product, sum, quotient and root is a separate IEEE operation (no fused multiply-add); no atomics.
+ *
+ * Pairs, 3 channels each, channel c of x against channel c of y:
+ *   UMPC_XS_TRACK  x = pdes, reference-table rows 0..2, slice ref_first + i;  y = p, state rows 0..2, slice first + i + after
+ *   UMPC_XS_ATT    x = sdes, reference-table rows 6..8;                        y = s, state rows 9..11
+ *   UMPC_XS_PUSH   x = dv_world, rows 0..2 of imp_tab [..][6][B] (the table of umpcBatchSetImpulses), slice imp_first + i;
+ *                  y = p - pdes as UMPC_SPEC_EP forms it: against ref_tab, or against the constant ref (exactly ONE of the two),
+ *                  the difference in the handle's dtype with one rounding, then widened exactly
+ * UMPC_XS_TRACK and UMPC_XS_ATT need ref_tab and refuse ref: a constant reference has no spectrum. imp_tab is read by
+ * UMPC_XS_PUSH alone. basis [W][1 + 2 K] DOUBLE on the device is umpcBatchSpectrum's (score.py spectrum_basis), step i reads
+ * row basis_first + i, 1 <= K <= UMPC_SPEC_MAX_K.
+ *
+ * xsums [2 + 6 (2 + 2 K)][B] DOUBLE, in/out: umpcBatchCrossSpectrum ADDS into it; umpcBatchCrossSpectrumInit writes zeros.
+ *   0  n, steps that entered        1  skipped steps
+ *   then six blocks of 2 + 2 K rows in the layout of umpcBatchSpectrum's channels (sum w v, sum w v v, then C_j, S_j per
+ *   frequency), in the order x0, x1, x2, y0, y1, y2
+ * A step enters for a robot when every word it reads for BOTH signals is finite (6 words; 9 for UMPC_XS_PUSH against a table;
+ * the constant reference counts); otherwise row 1 counts it and its value is +0 in every product of both signals. The order
+ * of summation is umpcBatchSpectrum's: UMPC_SPEC_SLICES = 2 wavefronts per 64 robots, wavefront s folds steps s, s + 2, .. in
+ * order from +0, the partial sums are added in the order 0, 1 and the total is added to `xsums`. A robot's sums depend on its
+ * own columns, the basis rows and count alone -- not on how the frequencies are cut into tiles --: bit-equal from run to run,
+ * between a column block on a handle of its own and the same columns of the whole batch, and with the numpy mirror
+ * (score.py, cross_spectrum_sums_reference). On tables without a hole the y blocks of UMPC_XS_TRACK equal the channel blocks
+ * of umpcBatchSpectrum(UMPC_SPEC_EP) against a zero reference bit for bit. A chunked run calls umpcBatchCrossSpectrum once
+ * per chunk with basis_first advanced, as there.
+ *
+ * umpcBatchCrossSpectrumGroups: gx [G][3][2 + 4 K] DOUBLE, overwritten, on the tables of umpcBatchGroupIndex. wsum [1 + 2 K] is
+ * a HOST array (it travels in the launch arguments), the column sums of the nrows basis rows that were used, as for
+ * umpcBatchSpectrumPower. A member ENTERS when skipped == 0, n == nrows and n >= 2: one rule for all channels. Per member
+ * and signal channel the power kernel's mean removal: m = sum w v / W0, A_j = C_j - m Wc_j, B_j = S_j - m Ws_j. Per group and
+ * channel c: the members that enter, the members that do not, then per frequency j at 2 + 4 j the four sums over the members
+ * that enter, each term (4 (..)) / W0^2 so that Sxx / n is the averaged periodogram in umpcBatchSpectrumPower's units:
+ *   Sxx = sum (Ax Ax + Bx Bx)    Syy = sum (Ay Ay + By By)    Cxy = sum (Ax Ay + Bx By)    Qxy = sum (Bx Ay - Ax By)
+ * (Cxy, Qxy) is conj(X) Y with X = A - i B: a y that LAGS x has Qxy < 0, the sign convention of umpcBatchResponseFit's phase.
+ * Order of summation: umpcBatchSpectrumGroups' -- lane l of 64 adds members l, l + 64, .. of the list in order from +0, then
+ * for w = 32, 16, 8, 4, 2, 1 every lane becomes (itself) + (lane ^ w). A row is a function of the group's member list alone
+ * and bit-reproducible; raw sums ADD over the blocks of a sharded job (score.py, combine_cross_spectra).
+ *
+ * umpcBatchTransfer: tf [G][3][K][UMPC_TF_ROWS] DOUBLE from gx, overwritten; with M2 = Cxy Cxy + Qxy Qxy:
+ *   0  n, members that entered, or 0 when the row is refused     1  members that did not enter
+ *   2  Pxx = Sxx / n                                             3  Pyy = Syy / n
+ *   4  h_re = Cxy / Sxx                                          5  h_im = Qxy / Sxx                  (the H1 estimate)
+ *   6  gain = sqrt(M2) / Sxx                                     7  phase = atan2(Qxy, Cxy), negative: y lags x
+ *   8  coh = M2 / (Sxx Syy)                                      9  gain_h2 = Syy / sqrt(M2)
+ *  10  rel_err = sqrt((1 - coh) / ((2 n) coh))                  11  noise = Pyy (1 - coh)
+ * gain <= |H| <= gain_h2 brackets the bias of noise on the input and of noise on the output; rel_err is the normalised
+ * random error of the gain and the standard deviation of the phase in rad; noise is the output power the linear map leaves
+ * unexplained. A row is REFUSED when n < 2 (one record's coherence is identically 1), when one of the four sums is not
+ * finite, or when Sxx is not > 0: row 0 is then 0 and rows 2..11 are NaN. Rows 8..11 are NaN when Syy is not > 0. Nothing
+ * else is clamped: rounding may leave coh a hair above 1 (rel_err is then NaN), and an input with no power at a bin beyond
+ * rounding dust gives a meaningless row that Pxx reveals -- compare row 2 with the power the experiment put there. Every row
+ * but the phase is bit-identical to the mirror (score.py, transfer_rows_reference); the phase agrees to the rounding of atan2.
+ * Not built: the off-diagonal terms of the 3 x 3 (MIMO) transfer matrix; Welch averaging over time segments; a per-robot H
+ * shaped as a score; the pair from the error to the command.
+ * Refused (-1, umpcLastError) BEFORE any launch: h NULL; state_hist, basis, xsums, wsum, order, offset, gx or tf NULL; K
+ * outside 1..64; pair outside 0..2; UMPC_XS_TRACK / ATT without ref_tab or with ref; UMPC_XS_PUSH without imp_tab, or with both
+ * or neither of ref_tab and ref; count, first, ref_first, imp_first or basis_first < 0; count > 2^31 - 5; nrows < 0 or
+ * > 2^53; G < 1. count == 0 is a successful no-op. */
+#define UMPC_XS_TRACK 0
+#define UMPC_XS_ATT 1
+#define UMPC_XS_PUSH 2
+#define UMPC_TF_ROWS 12
+int umpcBatchCrossSpectrumInit(umpc_batch_t *h, int K, double *xsums, void *stream);
+int umpcBatchCrossSpectrum(umpc_batch_t *h, int pair, const void *state_hist, const void *ref_tab, const void *ref,
+                           const void *imp_tab, const double *basis, long long basis_first, int K, long long first,
+                           long long count, long long ref_first, long long imp_first, int after, double *xsums, void *stream);
+int umpcBatchCrossSpectrumGroups(umpc_batch_t *h, const double *xsums, const double *wsum /* host, [1 + 2 K] */, int K,
+                                 long long nrows, const int32_t *order, const int32_t *offset, int G, double *gx, void *stream);
+int umpcBatchTransfer(umpc_batch_t *h, const double *gx, int G, int K, double *tf, void *stream);
 
 /* Step-kernel choice. 0 (default): automatic. fp32: the all-assembly kernel (robobee3d_amd/asmstep.py: phase A, ADMM
  * loop, phase C and the plant as one generated gfx950 stream) whenever the call is inside its scope (maxIter >= 1 and

@@ -32,6 +32,7 @@ XMOM_ROWS, PROP_ROWS = 96, 80
 SENS_MAX_FACTORS, SENS_MAX_BINS = 6, 8
 SPEC_EP, SPEC_ES, SPEC_U, SPEC_ROWS, SPEC_MAX_K = 0, 1, 2, 12, 64
 GRAM_ROWS, GRAM_COLS, PROJ_ROWS, PROJ_MAX = 66, 64, 32, 4
+XS_TRACK, XS_ATT, XS_PUSH, TF_ROWS = 0, 1, 2, 12
 SPEC_SLICES = 2      # UMPC_SPEC_SLICES of csrc/umpc_spectrum.h: part of the order of summation of umpcBatchSpectrum
 NX, NC, NADATA = 45, 39, 48
 
@@ -50,6 +51,7 @@ EXPORTS = ["umpcInit", "umpcUpdate", "umpcS", "umpcLastStatus", "umpcRelease", "
            "umpcBatchFactorBins", "umpcBatchSensitivity", "umpcBatchSensitivityIndices", "umpcBatchScoreSensitivity",
            "umpcBatchSpectrumInit", "umpcBatchSpectrum", "umpcBatchSpectrumPower", "umpcBatchSpectrumGroups",
            "umpcBatchGram", "umpcBatchProject",
+           "umpcBatchCrossSpectrumInit", "umpcBatchCrossSpectrum", "umpcBatchCrossSpectrumGroups", "umpcBatchTransfer",
            "umpcLastError", "umpcKernelName", "umpcBatchKernelName", "wlConInit", "wlConUpdate", "wlconS", "umpcBatchWLUpdate", "umpcBatchSetWL", "umpcBatchModel",
            "umpcQPDefaultSettings", "umpcQPCreate", "umpcQPDestroy", "umpcQPSetMaxIter", "umpcQPSetCheckTermination", "umpcQPSetAdaptiveRho", "umpcQPUseTables", "umpcQPSetKernel", "umpcQPKernelName", "umpcQPSolve", "umpcQPGather", "umpcQPGatherUpdate",
            "umpcP5fStep", "umpcP5fStepU", "umpcP5fLinearise", "umpcP5fTick", "umpcNAssemble", "umpcNExtract"]
@@ -330,6 +332,12 @@ def lib():
                                     C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchProject.argtypes = [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchCrossSpectrumInit.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchCrossSpectrum.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_longlong, C.c_int] + [C.c_longlong] * 4 + \
+                                            [C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchCrossSpectrumGroups.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_longlong, C.c_void_p,
+                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.umpcBatchTransfer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.umpcBatchTaskTable.argtypes = [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 5
         L.umpcBatchSetStepKernel.argtypes = [C.c_void_p, C.c_int]
         L.umpcBatchSetGlobalBatch.argtypes = [C.c_void_p, C.c_longlong]

@@ -295,6 +295,7 @@ class BatchUprightMPC:
         self._hist = hist  # keep alive: the library stores the pointers
         # where the record starts: the clock, the slice of a reference trajectory, the statistics accumulated before it
         self._hist_t0, self._hist_ref0, self._hist_stats0 = self.time_ms, self.ref_cursor, self.stats.clone()
+        self._hist_imp0 = self.impulse_cursor      # (the slice of the table of set_impulses the first recorded step adds)
 
     def rewind_history(self, cursor=0):
         """Reuse the tables of record_history from step `cursor` on (a chunked long run: read the full tables out, rewind,
@@ -307,6 +308,7 @@ class BatchUprightMPC:
                                                _ptr(hist["info"]), steps, int(cursor)))
         step_ms = int(self.prm.nsub) * float(self.prm.dtsim)
         self._hist_t0, self._hist_ref0 = self.time_ms - int(cursor) * step_ms, self.ref_cursor - int(cursor)
+        self._hist_imp0 = self.impulse_cursor - int(cursor)
         self._hist_stats0 = self.stats.clone()
 
     @property
@@ -1138,6 +1140,102 @@ class BatchUprightMPC:
             self._check(self.L.umpcBatchSpectrumGroups(self.h, _ptr(power), _ptr(spec), _ptr(order), _ptr(offset), G, K,
                                                        _ptr(gspec), self._stream()))
         return gspec
+
+    def transfer(self, freq_hz, index, pair="track", window="hann", first=0, count=None, after=False, ref_table=None, ref_first=0,
+                 impulses=None, imp_first=None, sums=None, basis=None, basis_first=0, rows=True):
+        """The transfer function of every grid cell from an input x to an output y over the recorded steps first .. first +
+        count - 1 of the step history, at the K <= 64 frequencies freq_hz [K] in Hz: the H1 estimate, the coherence and the
+        random error per frequency, from the cell's draws as independent records of one closed loop (umpcBatchCrossSpectrum /
+        umpcBatchCrossSpectrumGroups / umpcBatchTransfer; rows: robobee3d_amd/score.py TF_*, GX_*). pair "track": x = pdes, y = p;
+        "att": x = sdes, y = s -- both read the reference TABLE (ref_table, else that of set_reference_trajectory): a constant
+        reference has no spectrum --; "push": x = dv_world of the impulse table (`impulses` [steps, 6, B], default the table of
+        set_impulses, read at slice imp_first + step; imp_first defaults to the impulse cursor at the start of the record plus
+        `first`), y = p - pdes against the reference resolved as score() does. index = group_index(group, G). Returns (tf, gx,
+        sums): tf [G, 3, K, 12] float64 -- per cell, channel and frequency the draws that entered (0 when the row is refused:
+        fewer than two, or no input power), the draws that did not (a skipped step), Pxx, Pyy, h_re, h_im, gain, phase
+        (negative: y lags x, as in frequency_response), coh, gain_h2 (gain <= |H| <= gain_h2), rel_err (the normalised random
+        error of the gain = the standard deviation of the phase in rad) and the unexplained output power --, gx [G, 3, 2 + 4 K]
+        the raw cell sums (they add over shards: score.combine_cross_spectra, then transfer_rows), sums [2 + 6 (2 + 2 K), B]
+        float64 the raw projections. freq_hz, window, first, count, after, ref_table, ref_first, basis, basis_first and sums
+        are those of spectrum(): a chunked run passes the basis of the WHOLE window, basis_first = the steps already run, the
+        sums back in and rows=False (tf and gx are None) until the last chunk. Nothing of the tables' size is allocated."""
+        from . import score as S
+        pr = S._cross_pair(pair)
+        order, offset, G = self._group_index_arg("transfer", index)
+        if G < 1:
+            raise ValueError("transfer: G >= 1")
+        hist, first, count = self._history_window("transfer", first, count)
+        freq = np.ascontiguousarray(np.atleast_1d(np.asarray(freq_hz, np.float64)))
+        if freq.ndim != 1 or not 1 <= len(freq) <= _lib.SPEC_MAX_K:
+            raise ValueError("transfer: freq_hz must hold 1 to %d frequencies" % _lib.SPEC_MAX_K)
+        K = len(freq)
+        nu = S.response_nu(freq, int(self.prm.nsub), float(self.prm.dtsim))
+        if not np.all((nu > 0.0) & (nu < 0.5)):
+            raise ValueError("transfer: every frequency must lie strictly between 0 and half the step rate")
+        reftab, rfirst = self._scoring_reference("transfer", first, count, ref_table, ref_first)
+        imptab, ifirst = None, 0
+        if pr == _lib.XS_PUSH:
+            imptab = getattr(self, "_imptab", None) if impulses is None else impulses
+            if imptab is None:
+                raise RuntimeError("transfer: pair 'push' needs an impulse table (set_impulses, or impulses=)")
+            if (imptab.dim() != 3 or tuple(imptab.shape[1:]) != (6, self.B) or imptab.dtype != self.dtype
+                    or imptab.device != self.state.device or not imptab.is_contiguous()):
+                raise ValueError("impulses must be a contiguous [steps, 6, %d] tensor of the handle's dtype on its device" % self.B)
+            ifirst = self._hist_imp0 + first if imp_first is None else int(imp_first)
+            if ifirst < 0 or ifirst + count > int(imptab.shape[0]):
+                raise ValueError("transfer: the impulse table does not cover the steps asked for")
+        elif reftab is None:
+            raise RuntimeError("transfer: pair '%s' needs a reference table (set_reference_trajectory, or ref_table=): a constant "
+                               "reference has no spectrum" % S.XS_PAIRS[pr])
+        basis_first = int(basis_first)
+        if basis is None:
+            if basis_first != 0 or sums is not None:
+                raise ValueError("transfer: a chunked run (sums or basis_first given) needs the basis of the whole window")
+            host = S.spectrum_basis(nu, max(count, 1), window)
+            basis = torch.as_tensor(host).to(self.device)
+        else:
+            if (basis.dim() != 2 or int(basis.shape[1]) != 1 + 2 * K or basis.dtype != torch.float64
+                    or basis.device != self.state.device or not basis.is_contiguous()):
+                raise ValueError("basis must be a contiguous [W, %d] float64 tensor on the handle's device" % (1 + 2 * K))
+            if basis_first < 0 or basis_first + count > int(basis.shape[0]):
+                raise ValueError("transfer: the basis does not cover the steps asked for")
+            host = None
+        nsum = S.cross_spectrum_sum_rows(K)
+        fresh = sums is None
+        with torch.cuda.device(self.device):
+            if fresh:
+                sums = torch.empty((nsum, self.B), dtype=torch.float64, device=self.device)
+                self._check(self.L.umpcBatchCrossSpectrumInit(self.h, K, _ptr(sums), self._stream()))
+            elif (tuple(sums.shape) != (nsum, self.B) or sums.dtype != torch.float64 or sums.device != self.state.device
+                  or not sums.is_contiguous()):
+                raise ValueError("sums must be a contiguous [%d, %d] float64 tensor on the handle's device" % (nsum, self.B))
+            self._check(self.L.umpcBatchCrossSpectrum(self.h, pr, _ptr(hist["state"]), _ptr(reftab),
+                                                      _ptr(self.ref) if pr == _lib.XS_PUSH and reftab is None else None,
+                                                      _ptr(imptab), _ptr(basis), basis_first, K, first, count, rfirst, ifirst,
+                                                      int(bool(after)), _ptr(sums), self._stream()))
+            tf = gx = None
+            if rows:
+                # the rows the sums hold: this call's alone, or with `sums` passed in everything from row 0
+                lo, n = (basis_first, count) if fresh else (0, basis_first + count)
+                wsum = S.spectrum_wsum(basis.cpu().numpy() if host is None else host, lo, n)
+                gx = torch.empty((G, 3, 2 + 4 * K), dtype=torch.float64, device=self.device)
+                self._check(self.L.umpcBatchCrossSpectrumGroups(self.h, _ptr(sums), wsum.ctypes.data_as(C.POINTER(C.c_double)), K, n,
+                                                                _ptr(order), _ptr(offset), G, _ptr(gx), self._stream()))
+                tf = self.transfer_rows(gx)
+        return tf, gx, sums
+
+    def transfer_rows(self, gx):
+        """tf [G, 3, K, 12] float64 from the cell sums gx [G, 3, 2 + 4 K] of transfer() (umpcBatchTransfer alone): for tables
+        combined over the shards of a job or the column blocks of a cell (score.combine_cross_spectra)."""
+        if (gx.dim() != 3 or int(gx.shape[1]) != 3 or gx.dtype != torch.float64 or gx.device != self.state.device
+                or not gx.is_contiguous() or int(gx.shape[0]) < 1 or int(gx.shape[2]) < 6 or (int(gx.shape[2]) - 2) % 4 != 0
+                or (int(gx.shape[2]) - 2) // 4 > _lib.SPEC_MAX_K):
+            raise ValueError("gx must be a contiguous [G, 3, 2 + 4 K] float64 tensor on the handle's device, 1 <= K <= 64 (transfer())")
+        G, K = int(gx.shape[0]), (int(gx.shape[2]) - 2) // 4
+        tf = torch.empty((G, 3, K, _lib.TF_ROWS), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.L.umpcBatchTransfer(self.h, _ptr(gx), G, K, _ptr(tf), self._stream()))
+        return tf
 
     def task_table(self, steps, tasks=None, t_ms=None, **params):
         """[steps, 9, B] tensor for set_reference_trajectory: the generators of set_task evaluated PER ROBOT on the device

@@ -1,7 +1,7 @@
-// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchSpectrumGroups) and their
+// libumpc_mi355x.so, scoring: the entry points on recorded rollouts (umpcBatchScoreInit .. umpcBatchTransfer) and their
 // host launchers. The kernels are the stand-alone ones of umpc_score.h, umpc_ensemble.h, umpc_quantile.h, umpc_bootstrap.h,
-// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h, umpc_sensitivity.h, umpc_spectrum.h and umpc_gram.h: nothing
-// here reads the step path or a generated header.
+// umpc_band.h, umpc_response.h, umpc_dispersion.h, umpc_propagator.h, umpc_sensitivity.h, umpc_spectrum.h, umpc_gram.h and
+// umpc_transfer.h: nothing here reads the step path or a generated header.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -19,6 +19,7 @@
 #include "umpc_sensitivity.h" // per-step, per-group binned sums over the drawn inputs and their correlation ratios (umpcBatchSensitivity ..)
 #include "umpc_spectrum.h" // per-robot projections onto a temporal basis, periodograms and their per-group sums (umpcBatchSpectrum ..)
 #include "umpc_gram.h"     // per-group Gram matrix of the error trajectories (fp64 MFMA) and weighted sums over a group's draws (umpcBatchGram ..)
+#include "umpc_transfer.h" // per-robot projections of an input and an output, per-group cross-spectra, transfer function and coherence (umpcBatchCrossSpectrum ..)
 
 // UMPC_SCORE_NT=1 reads the tables with non-temporal loads (A/B timing, tools/time_score.py)
 static bool score_nt() {
@@ -31,6 +32,14 @@ static bool score_nt() {
 static int spec_kt() {
   static const int v = [] { const char *e_ = getenv("UMPC_SPEC_KT"); return e_ && atoi(e_) == 16 ? 16 : 8; }();
   return v;
+}
+
+// UMPC_XS_KT=8 runs the sums kernel of umpcBatchCrossSpectrum with tiles of 8 frequencies instead of 4 (A/B timing,
+// tools/time_transfer.py: 4 is the faster one at the shape of record; the sums do not depend on it). Read at every call, so
+// that one process can run both.
+static int xs_kt() {
+  const char *e_ = getenv("UMPC_XS_KT");
+  return e_ && atoi(e_) == 8 ? 8 : 4;
 }
 
 // ---- what the entry points on the recorded tables share (umpcBatchScore .. umpcBatchResponse) ----------------------------
@@ -411,6 +420,37 @@ static int launch_spectrum_groups(umpc_batch_t *h, const void *power, const void
   return launch_status("umpcBatchSpectrumGroups");
 }
 
+// x and y of a pair as the kernel reads them (umpc_transfer.h): the tracking and the attitude pair read two tables as they
+// are, the push pair the impulse table and p - pdes
+template <typename T>
+static int launch_cross_spectrum(umpc_batch_t *h, int pair, const ScoreWindow &w, const void *imp_tab, long long imp_first,
+                                 const double *basis, long long basis_first, int K, double *xsums, void *stream) {
+  const size_t B = (size_t)h->B;
+  const umpc::ScoreArgs<T> t = score_args<T>(h, w, 0.0, 0, nullptr);
+  umpc::XsArgs<T> a;
+  const bool push = pair == UMPC_XS_PUSH, att = pair == UMPC_XS_ATT;
+  a.x = push ? (const T *)imp_tab + (size_t)imp_first * 6 * B : t.reftab + (size_t)(att ? 6 : 0) * B;
+  a.xstride = push ? 6 : 9;
+  a.y = t.state + (size_t)(att ? 9 : 0) * B;
+  a.reftab = push ? t.reftab : nullptr;
+  a.ref = push ? t.ref : nullptr;
+  a.basis = basis + (size_t)basis_first * (1 + 2 * (size_t)K);
+  a.sums = xsums;
+  a.B = h->B; a.count = (int)w.count; a.K = K;
+  const int kt = xs_kt();
+  const dim3 grid((unsigned)((h->B + 63) / 64), (unsigned)((K + kt - 1) / kt)), block(64, umpc::kSpecSlices);
+  const hipStream_t s = (hipStream_t)stream;
+  const int form = !push ? umpc::kXsTwoTables : a.reftab ? umpc::kXsPushTable : umpc::kXsPushConst;
+#define UMPC_XS_FORM(F)                                                                                                 \
+  case F:                                                                                                               \
+    if (kt == 8) hipLaunchKernelGGL((umpc::umpc_xspec_kernel<T, F, 8>), grid, block, 0, s, a);                            \
+    else hipLaunchKernelGGL((umpc::umpc_xspec_kernel<T, F, 4>), grid, block, 0, s, a);                                    \
+    break;
+  switch (form) { UMPC_XS_FORM(0) UMPC_XS_FORM(1) UMPC_XS_FORM(2) }
+#undef UMPC_XS_FORM
+  return launch_status("umpcBatchCrossSpectrum");
+}
+
 // (the window of launch_dispersion; one block per cell, whatever G and the window)
 template <typename T>
 static int launch_gram(umpc_batch_t *h, const ScoreWindow &w, const int32_t *order, const int32_t *offset, int G, const double *scale,
@@ -777,6 +817,61 @@ int umpcBatchSpectrumGroups(umpc_batch_t *h, const void *power, const void *spec
   if (check_groups(fn, G) || check_freqs(fn, K)) return -1;
   return h->dtype == UMPC_F32 ? launch_spectrum_groups<float>(h, power, spec, order, offset, G, K, gspec, stream)
                               : launch_spectrum_groups<double>(h, power, spec, order, offset, G, K, gspec, stream);
+}
+
+int umpcBatchCrossSpectrumInit(umpc_batch_t *h, int K, double *xsums, void *stream) {
+  const char *fn = "umpcBatchCrossSpectrumInit";
+  if (!h || !xsums) return refuse(fn, "bad argument (h and xsums must be given)");
+  if (check_freqs(fn, K)) return -1;
+  const hipError_t e = hipMemsetAsync(xsums, 0, sizeof(double) * (2 + 6 * (2 + 2 * (size_t)K)) * (size_t)h->B, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail(e, fn);
+}
+int umpcBatchCrossSpectrum(umpc_batch_t *h, int pair, const void *state_hist, const void *ref_tab, const void *ref, const void *imp_tab,
+                           const double *basis, long long basis_first, int K, long long first, long long count, long long ref_first,
+                           long long imp_first, int after, double *xsums, void *stream) {
+  const char *fn = "umpcBatchCrossSpectrum";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (pair < UMPC_XS_TRACK || pair > UMPC_XS_PUSH) return refuse(fn, "bad argument (pair is UMPC_XS_TRACK, UMPC_XS_ATT or UMPC_XS_PUSH)");
+  if (!state_hist || !basis || !xsums) return refuse(fn, "bad argument (state_hist, basis and xsums must be given)");
+  if (check_freqs(fn, K)) return -1;
+  const bool push = pair == UMPC_XS_PUSH;
+  const ScoreWindow w = {state_hist, nullptr, nullptr, ref_tab, ref, first, count, ref_first, after};
+  if (push) {
+    if (!imp_tab) return refuse(fn, "UMPC_XS_PUSH needs imp_tab (the input is read from it)");
+    if (check_one_reference(fn, w)) return -1;
+  } else if (!ref_tab || ref) {
+    return refuse(fn, "UMPC_XS_TRACK and UMPC_XS_ATT need ref_tab and no ref (the input is the reference per step: a constant one has no spectrum)");
+  }
+  if (count < 0 || first < 0 || ref_first < 0 || imp_first < 0 || basis_first < 0)
+    return refuse(fn, "bad argument (count, first, ref_first, imp_first, basis_first >= 0)");
+  if (count > 0x7fffffffLL - 2 * umpc::kSpecSlices) return refuse(fn, "count too large for one call (2^31 - 5 steps at the most)");
+  if (count == 0) return 0;
+  return h->dtype == UMPC_F32 ? launch_cross_spectrum<float>(h, pair, w, imp_tab, imp_first, basis, basis_first, K, xsums, stream)
+                              : launch_cross_spectrum<double>(h, pair, w, imp_tab, imp_first, basis, basis_first, K, xsums, stream);
+}
+int umpcBatchCrossSpectrumGroups(umpc_batch_t *h, const double *xsums, const double *wsum, int K, long long nrows, const int32_t *order,
+                                 const int32_t *offset, int G, double *gx, void *stream) {
+  const char *fn = "umpcBatchCrossSpectrumGroups";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!xsums || !wsum || !order || !offset || !gx) return refuse(fn, "bad argument (xsums, wsum, order, offset and gx must be given)");
+  if (check_groups(fn, G) || check_freqs(fn, K)) return -1;
+  if (nrows < 0 || nrows > (1LL << 53)) return refuse(fn, "bad argument (0 <= nrows <= 2^53)");
+  umpc::XsGroupArgs a;
+  for (int j = 0; j < 1 + 2 * umpc::kSpecMaxK; ++j) a.wsum[j] = j < 1 + 2 * K ? wsum[j] : 0.0;
+  a.sums = xsums; a.order = order; a.offset = offset; a.gx = gx;
+  a.nrows = (double)nrows; a.B = h->B; a.K = K;
+  const dim3 grid((unsigned)G, 3u, (unsigned)((K + umpc::kXsGroupTile - 1) / umpc::kXsGroupTile));
+  hipLaunchKernelGGL(umpc::umpc_xspec_groups_kernel, grid, dim3(64), 0, (hipStream_t)stream, a);
+  return launch_status(fn);
+}
+int umpcBatchTransfer(umpc_batch_t *h, const double *gx, int G, int K, double *tf, void *stream) {
+  const char *fn = "umpcBatchTransfer";
+  if (!h) return refuse(fn, "bad argument (no handle)");
+  if (!gx || !tf) return refuse(fn, "bad argument (gx and tf must be given)");
+  if (check_groups(fn, G) || check_freqs(fn, K)) return -1;
+  const long long rows = (long long)G * 3 * K;
+  hipLaunchKernelGGL(umpc::umpc_transfer_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gx, rows, K, tf);
+  return launch_status(fn);
 }
 
 int umpcBatchGram(umpc_batch_t *h, const void *state_hist, const void *ref_tab, const void *ref, long long first, long long count,

@@ -1585,6 +1585,203 @@ def combine_spectra(parts):
     return total
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Transfer estimates (umpcBatchCrossSpectrumInit / umpcBatchCrossSpectrum / umpcBatchCrossSpectrumGroups / umpcBatchTransfer):
+# per robot the projections of an input x and an output y onto the basis of the spectrum; per group the auto- and
+# cross-periodograms summed over the draws; from those the H1 transfer function, the coherence and the random error
+# ----------------------------------------------------------------------------------------------------------------------
+XS_TRACK, XS_ATT, XS_PUSH = 0, 1, 2
+XS_PAIRS = ("track", "att", "push")       # pdes -> p, sdes -> s, dv_world of the impulse table -> p - pdes
+XS_CHANNELS = 6                           # blocks of the sums: x0 x1 x2 y0 y1 y2, each in the layout of a spectrum channel
+# group rows, per (group, channel): members that enter, members that do not, then (Sxx, Syy, Cxy, Qxy) per frequency
+GX_N, GX_SKIPPED, GX_FIRST = 0, 1, 2
+GX_SXX, GX_SYY, GX_CXY, GX_QXY = range(4)
+TF_ROWS = 12
+(TF_N, TF_SKIPPED, TF_PXX, TF_PYY, TF_H_RE, TF_H_IM, TF_GAIN, TF_PHASE, TF_COH, TF_GAIN_H2, TF_REL_ERR, TF_NOISE) = range(12)
+TF_ROW_NAMES = ("n", "skipped", "pxx", "pyy", "h_re", "h_im", "gain", "phase", "coh", "gain_h2", "rel_err", "noise")
+
+
+def cross_spectrum_sum_rows(K):
+    """rows of the sums of umpcBatchCrossSpectrum for K frequencies: 2 + 6 (2 + 2 K)"""
+    K = int(K)
+    if not 1 <= K <= SPEC_MAX_K:
+        raise ValueError("1 <= K <= %d frequencies" % SPEC_MAX_K)
+    return 2 + XS_CHANNELS * (2 + 2 * K)
+
+
+def cross_spectrum_identity(K, B):
+    """The sums no step has entered (umpcBatchCrossSpectrumInit): zeros [2 + 6 (2 + 2 K), B] float64."""
+    return np.zeros((cross_spectrum_sum_rows(K), int(B)))
+
+
+def _cross_pair(pair):
+    if pair in XS_PAIRS:
+        return XS_PAIRS.index(pair)
+    if pair in (XS_TRACK, XS_ATT, XS_PUSH):
+        return int(pair)
+    raise ValueError("pair is one of %s" % (XS_PAIRS,))
+
+
+def cross_spectrum_sums_reference(pair, state_hist, ref, impulses, basis, basis_first, first, count, ref_first, imp_first, after,
+                                  dtype=np.float64, sums=None):
+    """umpcBatchCrossSpectrum in numpy, IN THE DEVICE'S ORDER OF SUMMATION: the sums [2 + 6 (2 + 2 K), B] float64. pair "track"
+    (x = pdes, reference rows 0..2; y = p, state rows 0..2), "att" (x = sdes, reference rows 6..8; y = s, state rows 9..11) or
+    "push" (x = dv_world, rows 0..2 of impulses [.., 6, B], slice imp_first + i; y = p - pdes formed in `dtype` with one
+    rounding). state_hist [.., 18, B] is read at slice first + i + after; ref is a table [.., 9, B] read at slice ref_first +
+    i -- "track" and "att" take nothing else: a constant reference has no spectrum -- or, for "push" alone, one constant
+    reference [9, B]. basis, basis_first and the order of summation are spectrum_sums_reference's; the blocks of the sums
+    are x0 x1 x2 y0 y1 y2, each in the layout of a spectrum channel. A step enters for a robot when every word it reads for
+    BOTH signals is finite; otherwise row 1 counts it and its value is +0 in every product of both signals. Passing `sums`
+    back in accumulates. Elementwise IEEE operations in the kernel's order: the kernel's bits."""
+    pr = _cross_pair(pair)
+    basis = np.asarray(basis, np.float64)
+    first, count, ref_first, imp_first = int(first), int(count), int(ref_first), int(imp_first)
+    after, basis_first = int(bool(after)), int(basis_first)
+    if basis.ndim != 2 or basis.shape[1] < 3 or basis.shape[1] % 2 != 1:
+        raise ValueError("cross_spectrum_sums_reference: basis must be [W, 1 + 2 K]")
+    K = (basis.shape[1] - 1) // 2
+    rows = cross_spectrum_sum_rows(K)
+    if count < 0 or first < 0 or ref_first < 0 or imp_first < 0 or basis_first < 0 or basis_first + count > basis.shape[0]:
+        raise ValueError("cross_spectrum_sums_reference: bad argument")
+    if ref is None:
+        raise ValueError("cross_spectrum_sums_reference: a reference must be given")
+    src, ref = np.asarray(state_hist, dtype), np.asarray(ref, dtype)
+    if pr == XS_PUSH:
+        if impulses is None:
+            raise ValueError("cross_spectrum_sums_reference: pair 'push' needs the impulse table")
+        imp = np.asarray(impulses, dtype)
+    elif ref.ndim != 3:
+        raise ValueError("cross_spectrum_sums_reference: pairs 'track' and 'att' need a reference table (a constant reference has no spectrum)")
+    B = src.shape[-1]
+    sm = cross_spectrum_identity(K, B) if sums is None else np.array(sums, np.float64)
+    if sm.shape != (rows, B):
+        raise ValueError("cross_spectrum_sums_reference: sums must be [%d, %d]" % (rows, B))
+    chan = 2 + 2 * K
+    total = None
+    with np.errstate(invalid="ignore", over="ignore"):
+        for s in range(SPEC_SLICES):
+            part = np.zeros((rows, B))
+            for i in range(s, count, SPEC_SLICES):
+                if pr == XS_PUSH:
+                    x = imp[imp_first + i, 0:3]
+                    y = src[first + i + after, 0:3]
+                    r = (ref[ref_first + i] if ref.ndim == 3 else ref)[0:3]
+                    ok, d = np.isfinite(x).all(0) & np.isfinite(y).all(0) & np.isfinite(r).all(0), y - r
+                else:
+                    y0, r0 = (0, 0) if pr == XS_TRACK else (9, 6)
+                    x = ref[ref_first + i, r0:r0 + 3]
+                    d = src[first + i + after, y0:y0 + 3]
+                    ok = np.isfinite(x).all(0) & np.isfinite(d).all(0)
+                v = np.where(ok, np.concatenate((x, d)).astype(np.float64), 0.0)            # [6, B]
+                row = basis[basis_first + i]
+                part[SSUM_N] += ok
+                part[SSUM_SKIPPED] += ~ok
+                for c in range(XS_CHANNELS):
+                    at = SSUM_CHANNEL + c * chan
+                    t = row[0] * v[c]
+                    part[at + SSUM_WY] += t
+                    part[at + SSUM_WYY] += t * v[c]
+                    part[at + SSUM_BINS:at + chan] += v[c][None, :] * row[1:, None]
+            total = part if total is None else total + part
+        sm = sm + total
+    return sm
+
+
+def cross_spectrum_groups_reference(xsums, wsum, nrows, order, offset):
+    """umpcBatchCrossSpectrumGroups in numpy, IN THE DEVICE'S ORDER OF OPERATIONS: gx [G, 3, 2 + 4 K] float64 from the sums
+    [2 + 6 (2 + 2 K), B], the window's column sums wsum [1 + 2 K] (spectrum_wsum), the number of basis rows they were taken
+    over and the tables of group_index. A member enters when skipped == 0, n == nrows and n >= 2 -- one rule for all
+    channels. Per member and signal channel the mean removal of spectrum_power_reference: m = sum wv / W0, A_j = C_j - m Wc_j,
+    B_j = S_j - m Ws_j. Per group and channel c: the members that enter, those that do not, then at 2 + 4 j the sums over the
+    members that enter of (4 (Ax Ax + Bx Bx)) / W0^2, (4 (Ay Ay + By By)) / W0^2, (4 (Ax Ay + Bx By)) / W0^2 and
+    (4 (Bx Ay - Ax By)) / W0^2: Sxx, Syy, Cxy, Qxy -- (Cxy, Qxy) is conj(X) Y with X = A - iB, so a y that lags x has Qxy < 0.
+    Order of summation: spectrum_groups_reference's (lane l of 64 adds members l, l + 64, .. from +0, then the tree)."""
+    sm, wsum = np.asarray(xsums, np.float64), np.asarray(wsum, np.float64)
+    order, offset = np.asarray(order), np.asarray(offset)
+    G, nrows = len(offset) - 1, int(nrows)
+    if sm.ndim != 2 or wsum.ndim != 1 or wsum.shape[0] < 3 or wsum.shape[0] % 2 != 1:
+        raise ValueError("cross_spectrum_groups_reference: sums must be [2 + 6 (2 + 2 K), B] and wsum [1 + 2 K]")
+    K = (wsum.shape[0] - 1) // 2
+    if G < 1 or nrows < 0 or sm.shape[0] != cross_spectrum_sum_rows(K):
+        raise ValueError("cross_spectrum_groups_reference: bad argument")
+    chan = 2 + 2 * K
+    w0 = wsum[0]
+    w02 = w0 * w0
+    n, skipped = sm[SSUM_N], sm[SSUM_SKIPPED]
+    enters = (skipped == 0.0) & (n == float(nrows)) & (n >= 2.0)
+    out = np.zeros((G, 3, 2 + 4 * K))
+    lanes = np.arange(64)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for c in range(3):
+            xs = sm[SSUM_CHANNEL + c * chan:SSUM_CHANNEL + (c + 1) * chan]
+            ys = sm[SSUM_CHANNEL + (3 + c) * chan:SSUM_CHANNEL + (4 + c) * chan]
+            mx, my = xs[SSUM_WY] / w0, ys[SSUM_WY] / w0
+            wc, ws = wsum[1::2][:, None], wsum[2::2][:, None]
+            ax, bx = xs[SSUM_BINS::2] - mx * wc, xs[SSUM_BINS + 1::2] - mx * ws                 # [K, B]
+            ay, by = ys[SSUM_BINS::2] - my * wc, ys[SSUM_BINS + 1::2] - my * ws
+            four = np.stack(((4.0 * (ax * ax + bx * bx)) / w02, (4.0 * (ay * ay + by * by)) / w02,
+                             (4.0 * (ax * ay + bx * by)) / w02, (4.0 * (bx * ay - ax * by)) / w02), 1)   # [K, 4, B]
+            for g in range(G):
+                mem = order[offset[g]:offset[g + 1]]
+                ok = enters[mem]
+                terms = np.where(ok[None, None, :], four[:, :, mem], 0.0).reshape(4 * K, len(mem))
+                part = np.zeros((4 * K, 64))
+                for m0 in range(0, len(mem), 64):
+                    t = terms[:, m0:m0 + 64]
+                    part[:, :t.shape[1]] = part[:, :t.shape[1]] + t
+                for w in (32, 16, 8, 4, 2, 1):
+                    part = part + part[:, lanes ^ w]
+                out[g, c, GX_N], out[g, c, GX_SKIPPED] = ok.sum(), len(mem) - ok.sum()
+                out[g, c, GX_FIRST:] = part[:, 0]
+    return out
+
+
+def combine_cross_spectra(parts):
+    """The group table of a whole job from the tables gx [G, 3, 2 + 4 K] of its blocks of robots, or of the column blocks a
+    cell is split over: every column is a raw sum, so the tables add (counts exactly; the sums to the rounding of one more
+    addition per part). numpy arrays or torch tensors; the result is of the first part's kind and the parts are not
+    modified. transfer_rows_reference / BatchUprightMPC.transfer_rows turn the combined table into rows."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("combine_cross_spectra: no parts")
+    total = parts[0].clone() if hasattr(parts[0], "clone") else np.array(parts[0], np.float64)
+    for p in parts[1:]:
+        total = total + p
+    return total
+
+
+def transfer_rows_reference(gx):
+    """umpcBatchTransfer in numpy fp64, in the kernel's operation order: tf [G, 3, K, 12] (rows TF_*) from gx [G, 3, 2 + 4 K].
+    With M2 = Cxy Cxy + Qxy Qxy: Pxx = Sxx / n, Pyy = Syy / n, the H1 estimate h = (Cxy / Sxx, Qxy / Sxx), gain = sqrt(M2) /
+    Sxx, phase = atan2(Qxy, Cxy) (negative: y lags x), coh = M2 / (Sxx Syy), gain_h2 = Syy / sqrt(M2), rel_err = sqrt((1 -
+    coh) / ((2 n) coh)), noise = Pyy (1 - coh). Refused (row 0 = 0, rows 2..11 NaN) when n < 2, a sum is not finite or Sxx is
+    not > 0; rows 8..11 are NaN when Syy is not > 0. Nothing else is clamped: rounding may leave coh a hair above 1. Every
+    row but the phase is the kernel's bit for bit; the phase to the rounding of atan2."""
+    gx = np.asarray(gx, np.float64)
+    if gx.ndim != 3 or gx.shape[1] != 3 or gx.shape[2] < 6 or (gx.shape[2] - 2) % 4 != 0 or (gx.shape[2] - 2) // 4 > SPEC_MAX_K:
+        raise ValueError("transfer_rows_reference: gx must be [G, 3, 2 + 4 K] with 1 <= K <= %d" % SPEC_MAX_K)
+    G, K = gx.shape[0], (gx.shape[2] - 2) // 4
+    n = np.repeat(gx[:, :, GX_N, None], K, 2)                                                    # [G, 3, K]
+    four = gx[:, :, GX_FIRST:].reshape(G, 3, K, 4)
+    sxx, syy, cxy, qxy = (four[..., k] for k in range(4))
+    tf = np.full((G, 3, K, TF_ROWS), np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        refused = ~(n >= 2.0) | ~np.isfinite(four).all(-1) | ~(sxx > 0.0)
+        noy = refused | ~(syy > 0.0)
+        m2 = cxy * cxy + qxy * qxy
+        mag = np.sqrt(m2)
+        pyy, coh = syy / n, m2 / (sxx * syy)
+        rest = 1.0 - coh
+        tf[..., TF_N] = np.where(refused, 0.0, n)
+        tf[..., TF_SKIPPED] = gx[:, :, GX_SKIPPED, None]
+        for row, val in ((TF_PXX, sxx / n), (TF_PYY, pyy), (TF_H_RE, cxy / sxx), (TF_H_IM, qxy / sxx), (TF_GAIN, mag / sxx),
+                         (TF_PHASE, np.arctan2(qxy, cxy))):
+            tf[..., row] = np.where(refused, np.nan, val)
+        for row, val in ((TF_COH, coh), (TF_GAIN_H2, syy / mag), (TF_REL_ERR, np.sqrt(rest / ((2.0 * n) * coh))), (TF_NOISE, pyy * rest)):
+            tf[..., row] = np.where(noy, np.nan, val)
+    return tf
+
+
 # ---- trajectory modes (umpcBatchGram / umpcBatchProject) ------------------------------------------------------------------------
 GRAM_ROWS, GRAM_COLS, PROJ_ROWS, PROJ_MAX = 66, 64, 32, 4
 # Gram table, per group [66, 64]: rows 0..63 the matrix over member slots (slot i = order[offset[g] + i]); row GR_COUNTS the steps
