@@ -10,6 +10,12 @@ reference is itself 1.2e-4 / 1.4e-5 from fp64 there), multi-call sequences (erro
 the warm start), and comparisons against the FP64 oracle (the fp32 reference itself is 0.9e-5 / 3.4e-3 / 0.9e-5 from
 the fp64 evaluation of the same algorithm on these vectors: tests/test_oracle_golden.py).
 fp64 kernel vs fp64 oracle: 1e-9 relative.
+
+Which kernel these tests run: those that do not call `set_step_kernel` run "auto", and at their batch sizes (12 .. 512 robots;
+"auto" takes the quad form for B <= 16 384 in fp32, B <= 4 096 in fp64) that is the QUAD form of the assembly path --
+umpc_rollout_asm_quad_kernel / umpc_rollout_kernel<double, LDSF, ASM64, QUAD>; the achieved figures above are the quad form's.
+They are the record for "auto". The record per form (lane, quad, C++; fp32 and fp64; the same fixtures, branches and closed
+loops, each test asserting its kernel by name) is tests/test_step_forms.py.
 """
 import numpy as np
 import pytest
@@ -637,9 +643,11 @@ def test_fp64_assembly_loop_and_cpp_loop_agree(torch_cuda, margin):
 
 
 def test_assembly_kernel_ragged_batches_and_monte_carlo(torch_cuda, oracle_built):
-    """The all-assembly kernel with exec-masked lanes (B = 1, 63, 65, 131: the last wave is partial) and with
-    per-robot inertia / thrust gain (config 5 inputs) in fp32, RK4 plant: partial batches are bit-identical slices of
-    a larger one; the Monte-Carlo rollout matches the fp64 oracle within the fp32 closed-loop band."""
+    """The all-assembly kernel as "auto" dispatches it -- the QUAD form at these sizes (umpc_rollout_asm_quad_kernel: whole
+    lane quads, the last wave holds fewer of them) -- on ragged batches (B = 1, 63, 65, 131) and with per-robot inertia /
+    thrust gain (config 5 inputs) in fp32, RK4 plant: partial batches are bit-identical slices of a larger one; the
+    Monte-Carlo rollout matches the fp64 oracle within the fp32 closed-loop band. The lane form's exec-masked partial wave
+    and the same checks on every pinned form: tests/test_step_forms.py."""
     torch = torch_cuda
     from robobee3d_amd.batch import BatchUprightMPC, hover_initial_conditions, monte_carlo_draws
     from robobee3d_amd import _lib
