@@ -217,7 +217,29 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.run(cmd, check=True, cwd=CSRC, stderr=None if verbose else subprocess.DEVNULL)
     build_ext(verbose=verbose)
+    build_isaprobe(force=force, verbose=verbose)
     return SO_PATH
+
+
+def build_isaprobe(force=False, verbose=False):
+    """libumpc_isaprobe.so: the instruction probes of isaprobe.py (test infrastructure: one kernel per instruction form the
+    generators emit), compiled with the product's flags -- the float mode of the kernels is the product's -- and linked
+    into a library of its own, next to the product's so that it travels with the tree. No part of libumpc_mi355x.so.
+    The generated unit names HIPCC_FLAGS in its text, so other flags are another file and the library is built again.
+    A unit that does not compile raises, like any other: the streams' correctness gate is held to the device by this library,
+    and a build that quietly lacked it would leave that unchecked."""
+    from . import isaprobe
+    src = isaprobe.write()
+    out = isaprobe.SO_PATH
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(src):
+        return out
+    cmd = ["hipcc"] + HIPCC_FLAGS + ["-shared", "-o", out, os.path.relpath(src, CSRC)]
+    if verbose:
+        print(" ".join(cmd))
+    p = subprocess.run(cmd, cwd=CSRC, stderr=subprocess.PIPE)
+    if p.returncode != 0:
+        raise RuntimeError("hipcc failed: %s\n%s" % (" ".join(cmd), p.stderr.decode()[-4000:]))
+    return out
 
 
 EXT_SRC = os.path.join(HERE, "csrc", "uprightmpc2py_ext.cpp")

@@ -2518,12 +2518,13 @@ STRIDE = 4096
 PBASE = 0x00007E0080000000
 
 
-def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None, lanes=1, hits=False):
+def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None, lanes=1, hits=False, approx=None):
     """arrays: name -> float32 / int32 numpy vector indexed by ROW (one robot), or None for a null pointer; ints /
     floats: the StepParams scalars (ints without `stride`). Runs the whole kernel; arrays are updated in place.
     Returns the executed instruction count (pseudo-instructions excluded).
     lanes > 1 (lane form only): that many lanes of ONE wavefront -- the row arrays are C-contiguous [rows][lanes] then,
-    and scalar branches are taken for the wavefront as on the device. hits: simulate.last_hits[k] = executions of ins[k]."""
+    and scalar branches are taken for the wavefront as on the device. hits: simulate.last_hits[k] = executions of ins[k].
+    approx: isasim.Machine's source of the approximate instructions' results (None: correctly rounded)."""
     import numpy as np
     from . import isasim
     base_of = {n: 0x00007F0080000000 + (k << 36) for k, n in enumerate(PTRS + ["impulse"])}
@@ -2556,7 +2557,7 @@ def simulate(ins, arrays, ints, floats, max_exec=3000000, ptr_xform=None, lanes=
     assert all(arrays[n].flags.c_contiguous for n in PTRS + ["impulse"] if arrays.get(n) is not None)
     m = isasim.Machine(ins, lanes, regions=regions, sgpr={S_PARAM: PBASE & 0xFFFFFFFF, S_PARAM + 1: PBASE >> 32},
                        vgpr={0: 4 * np.arange(lanes)}, lds=np.zeros((lanes, NLDS), np.uint32), max_exec=max_exec,
-                       quad=_quad() if lanes == 1 else None)
+                       quad=_quad() if lanes == 1 else None, approx=approx)
     if hits:
         m.hits = np.zeros(len(ins), np.int64)
     isasim.run(m)

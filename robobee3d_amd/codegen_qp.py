@@ -766,7 +766,8 @@ def write():
     files = generate()
     for rel, src in files.items():
         asmtext.write_if_changed(os.path.join(csrc, rel), src)
-    keep = {os.path.basename(r) for r in files if r.startswith("gen/")}
+    from . import isaprobe
+    keep = {os.path.basename(r) for r in files if r.startswith("gen/")} | {os.path.basename(isaprobe.SRC)}   # (not ours)
     for fn in os.listdir(os.path.join(csrc, "gen")):
         if fn not in keep:
             os.remove(os.path.join(csrc, "gen", fn))

@@ -2,7 +2,7 @@
 asmquad64, asmqp, tools/asmx.py): the correctness gate every generated stream passes before it reaches a GPU.
 
 A stream is a list of tuples (mnemonic, operands..., [VOP3P modifier dict]) as the generators emit them. The Machine
-runs it on `lanes` lanes (1, 2 or 4) of one wavefront:
+runs it on `lanes` lanes (1, 2, 4, or up to a whole wavefront of 64) of one wavefront:
   * VGPRs and AGPRs as uint32 bit patterns, shape (lanes, 256), poisoned (a NaN in fp32 and in fp64) at entry, per-lane
     EXEC, the SGPR file with VCC as s[106:107] (a lane mask, one bit per modelled lane), SCC;
   * global memory as data: regions (base, element stride in bytes, numpy array); every access must land on an element of
@@ -15,8 +15,18 @@ runs it on `lanes` lanes (1, 2 or 4) of one wavefront:
 Pseudo-instructions: ("kill", "vN") poisons a register; ("quad_begin"[, name]) .. ("quad_end"[, registers]) runs the
 one-lane stream on the four lanes of a quad (see Quad); labels are not executed and not counted.
 
-Floating point: fp32 fma as an fp64 product and sum rounded to fp32, fp64 fma exact (Fraction); min / max return the
-other operand when one is NaN (the hardware's IEEE mode)."""
+Floating point: what tests/test_isa_probe.py measured on the MI355X, instruction form by instruction form (DESIGN.md 4,
+"What the interpreter is held to"), in the float mode of the build (fp32 denormals kept, IEEE mode):
+  * fp32 fma (v_fma / v_fmac / v_fmaak / v_pk_fma) is fused: the exact fp64 product, a sum rounded to odd where it is inexact
+    and lies on an fp32 tie, one rounding to fp32 (before: fp64 sum, then fp32 -- two roundings);
+  * fp64 fma exact (Fraction): a finite product never overflows against an infinite addend, an exact overflow is an infinity;
+  * v_min / v_max (fp32, fp64, DPP): the other operand for a quiet NaN, a signalling NaN comes back quieted, +0 lies above
+    -0 whatever the operand order; v_min3 / v_max3 are the two-operand instruction twice;
+  * v_med3_f32 is min3 when an operand is a NaN, else the median with -0 below +0 (before: a sort, NaN largest);
+  * v_rcp_f32, v_rsq_f32, v_sqrt_f32, v_rcp_f64, v_rsq_f64 are APPROXIMATE on the device (1 ulp in fp32, denormal operands
+    and results flushed; about 2^-25 relative in fp64): modelled as correctly rounded unless Machine(approx=...) supplies
+    the device's own results;
+  * a quad_perm DPP control permutes every quad of the modelled lanes alike (1, 2, 4 or a whole wavefront)."""
 import functools
 import re
 from fractions import Fraction
@@ -98,12 +108,56 @@ def _srcs(t, k):
     return frozenset((kind, lo + h) for h in sels)
 
 
+@functools.lru_cache(maxsize=None)
+def _quad_perm_of(dpp):
+    return tuple(int(c) for c in dpp[dpp.index("[") + 1:dpp.index("]")].split(","))
+
+
+def _quad_perm(dpp, lanes, exec_):
+    """source lane of every lane under the quad_perm control `dpp`: lane 4q + k reads lane 4q + perm[k] (every quad of the
+    wavefront alike); with fewer than four modelled lanes the control must stay inside them"""
+    ln = np.arange(lanes)
+    src = (ln & ~3) + np.array(_quad_perm_of(dpp))[ln & 3]
+    assert (src < lanes).all(), "DPP read outside the modelled lanes: %r" % (dpp,)
+    if (exec_ & ~exec_[src]).any():
+        raise AssertionError("DPP read of a masked-off lane: %r" % (dpp,))
+    return src
+
+
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    return x, x.view(u32 if x.dtype == f32 else u64)
+
+
+def _minmax(a, b, is_max):
+    """v_max / v_min, fp32 or fp64, in IEEE mode (every kernel here runs in it): +0 lies above -0 whatever the operand order;
+    a quiet NaN operand gives the other operand; a signalling NaN operand comes back quieted, the first one first"""
+    (a, ab), (b, bb) = _bits(a), _bits(b)
+    r = np.maximum(a, b) if is_max else np.minimum(a, b)
+    eq = a == b
+    if eq.any():                          # equal operands differ in the sign of a zero at the most
+        r = np.where(eq, (ab & bb if is_max else ab | bb).view(a.dtype), r)
+    nan = (a != a) | (b != b)
+    if nan.any():
+        r = np.where(b != b, a, np.where(a != a, b, r))
+        qbit = ab.dtype.type(0x00400000 if a.dtype == f32 else 0x0008000000000000)
+        for x, xb in ((b, bb), (a, ab)):
+            r = np.where((x != x) & ((xb & qbit) == 0), (xb | qbit).view(a.dtype), r)
+    return r
+
+
 def _fmax(a, b):
-    return np.where(b != b, a, np.where(a != a, b, np.where(b > a, b, a)))
+    return _minmax(a, b, True)
 
 
 def _fmin(a, b):
-    return np.where(b != b, a, np.where(a != a, b, np.where(b < a, b, a)))
+    return _minmax(a, b, False)
+
+
+def _med3(a, b, c):
+    """v_med3_f32: min3 when an operand is a NaN (the ISA's text); else the median, with -0 below +0 as in v_min / v_max"""
+    r = _fmax(_fmin(a, b), _fmin(_fmax(a, b), c))
+    return np.where((a != a) | (b != b) | (c != c), _fmin(_fmin(a, b), c), r)
 
 
 def _imm(t, k):
@@ -122,12 +176,21 @@ _WAITABLE = ("ds_read", "global_load", "s_load")
 _T1_READ = ("ds_write", "ds_min", "global_store", "s_cmp", "s_cbranch", "s_branch", "v_fmac")     # t[1] is a source
 
 
+def _lds_word_of(byte):
+    """word of a lane's slice at LDS byte address `byte` (an int, or an int array over lanes): 1024 * (word // 4) + 16 * lane
+    + 4 * (word % 4); the lane bits are not decoded (Machine.lds_word)"""
+    return (byte // 1024) * 4 + (byte % 16) // 4
+
+
 class Machine:
     def __init__(self, ins, lanes=1, regions=(), sgpr=None, vgpr=None, lds=None, max_exec=3000000, quad=None, log=None,
-                 V=None, A=None):
+                 V=None, A=None, approx=None):
         self.ins, self.lanes = ins, lanes
+        self.approx = approx           # (mnemonic, operand bits [lanes]) -> result bits [lanes] for the APPROX instructions
         self.V = np.full((lanes, 256), POISON, u32) if V is None else V
         self.A = np.full((lanes, 256), POISON, u32) if A is None else A
+        # (isaprobe.WideMachine puts a Python int of more than 64 bits, or a uint64 array [lanes], into an entry of S: bits,
+        # d, half, s64 and wmask must go on reading an entry as a value that broadcasts, not as a 32-bit int)
         self.S = [0] * 128
         for r, val in (sgpr or {}).items():
             self.S[r] = val & 0xFFFFFFFF
@@ -193,11 +256,7 @@ class Machine:
         else:
             b = (self.V if k == "v" else self.A)[:, lo].copy()
             if dpp is not None:
-                qp = [int(c) for c in dpp[dpp.index("[") + 1:dpp.index("]")].split(",")][:self.lanes]
-                for ln in range(self.lanes):
-                    if self.exec[ln] and not self.exec[qp[ln]]:
-                        raise AssertionError("DPP read of a masked-off lane: %r" % (dpp,))
-                b = b[qp]
+                b = b[_quad_perm(dpp, self.lanes, self.exec)]
         if ab:
             b = b & u32(0x7FFFFFFF)
         return b ^ u32(0x80000000) if neg else b
@@ -263,7 +322,7 @@ class Machine:
         """word of lane ln's slice: a lane reaches only its own LDS words, so the lane bits of the address ((byte % 1024)
         // 16: the 16 * lane of v1, which registers derived from v1 before a quad section do not carry) are not decoded"""
         byte = int(self.V[ln, _decode(base)[1]]) + off
-        w = (byte // 1024) * 4 + (byte % 16) // 4
+        w = _lds_word_of(byte)
         if w >= self.lds.shape[1]:
             raise AddressFault("%r touches LDS byte 0x%x, outside the lane's slice" % (self.ins[self.pc], byte))
         return ln, w
@@ -375,7 +434,7 @@ class Machine:
         name = t[1] if len(t) > 1 else None
         spec = self.quad[name]
         q = Machine(self.ins, 4, lds=np.tile(self.lds, (4, 1)), max_exec=self.max_exec,
-                    V=np.tile(self.V, (4, 1)), A=np.tile(self.A, (4, 1)))
+                    V=np.tile(self.V, (4, 1)), A=np.tile(self.A, (4, 1)), approx=self.approx)
         q.V[:, LANE_LDS_VGPR] += 16 * np.arange(4, dtype=u32)
         q.S, q.scc, q.regions, q.pend, q.labels, q._use = self.S, self.scc, self.regions, self.pend, self.labels, self._use
         for _ in q.run(self.pc + 1):
@@ -543,8 +602,33 @@ def _f32op(op, dpp=False):
     return f
 
 
+_DEN32 = np.uint64(np.array(2.0 ** -126).view(np.uint64) - 1)
+
+
 def _fma32(a, b, c):
-    return (a.astype(f64) * b.astype(f64) + c.astype(f64)).astype(f32)
+    """fused fp32 multiply-add of arrays of one shape, rounded once. The fp64 product of two fp32 numbers is exact, the fp64
+    sum s need not be; it rounds to fp32 as the exact sum does unless it lies half way between two fp32 numbers (dropped
+    bits 1000...; below 2^-126 the last place of fp32 lies higher: every such lane is looked at). There the sum is
+    rounded TO ODD first: where it is inexact -- its error from an error-free two-sum -- an even significand moves one
+    place towards the exact sum; fp64 rounded to odd rounds to fp32 like the exact value (53 >= 24 + 2 bits)."""
+    return _fma32_of(a.astype(f64) * b.astype(f64), c.astype(f64))
+
+
+def _fma32_of(p, c):
+    """the exact fp64 product p and the addend c as fp64 -> fp32 [lanes]"""
+    s = p + c
+    sb = s.view(np.int64)
+    u = sb & 0x7FFFFFFFFFFFFFFF
+    cand = ((u & 0x1FFFFFFF) == 0x10000000) | ((u - 1).view(u64) < _DEN32)
+    if cand.any():
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        fix = cand & np.isfinite(s) & np.isfinite(err) & (err != 0) & ((sb & 1) == 0)
+        if fix.any():
+            s = s.copy()
+            up = (err > 0) == (s > 0)         # the exact sum is larger in magnitude than s
+            s.view(np.int64)[fix] += np.where(up, 1, -1)[fix]
+    return s.astype(f32)
 
 
 def _fmac(dpp=False):
@@ -555,7 +639,7 @@ def _fmac(dpp=False):
 
 
 def _nanless(red):
-    """min3 / max3: NaN operands are dropped (np.fmin / np.fmax: a NaN only where every operand is one)"""
+    """min3 / max3: the two-operand instruction twice (quiet NaN operands are dropped: a NaN only where every operand is one)"""
     return lambda a, b, c: red(red(a, b), c)
 
 
@@ -565,11 +649,44 @@ def _f64op(op):
     return f
 
 
+APPROX = ("v_rcp_f32", "v_rsq_f32", "v_sqrt_f32", "v_rcp_f64", "v_rsq_f64")     # the hardware's are approximations
+
+
+def _approx32(m, op):
+    """a transcendental fp32 instruction: Machine.approx (the device's own results, tests/test_stream_replay.py) where one
+    is given, the correctly rounded value otherwise"""
+    exact = _f32op(op)
+
+    def f(mc, t):
+        if mc.approx is None:
+            return exact(mc, t)
+        mc.write(t[1], np.asarray(mc.approx(m, mc.bits(t[2])), u32))
+    return f
+
+
+def _approx64(m, op):
+    exact = _f64op(op)
+
+    def f(mc, t):
+        if mc.approx is None:
+            return exact(mc, t)
+        b = np.asarray(mc.approx(m, np.ascontiguousarray(mc.d(t[2])).view(u64)), u64)
+        mc.write(t[1], (b & u64(0xFFFFFFFF)).astype(u32))
+        mc.write(t[1], (b >> u64(32)).astype(u32), 1)
+    return f
+
+
 def _fma64(a, b, c):
     out = a * b + c
+    fused = np.isfinite(a) & np.isfinite(b) & np.isinf(c)      # the product is not rounded: it cannot overflow against c
+    out = np.where(fused, c, out)
     for ln in range(len(a)):
         if np.isfinite(a[ln]) and np.isfinite(b[ln]) and np.isfinite(c[ln]):
-            out[ln] = float(Fraction(float(a[ln])) * Fraction(float(b[ln])) + Fraction(float(c[ln])))
+            r = Fraction(float(a[ln])) * Fraction(float(b[ln])) + Fraction(float(c[ln]))
+            try:
+                out[ln] = float(r) if r else out[ln]       # (an exact zero keeps the sign of the fp64 evaluation)
+            except OverflowError:
+                out[ln] = np.inf if r > 0 else -np.inf
     return out
 
 
@@ -584,7 +701,7 @@ def _pk(kind):
             ng = d["neg_hi"] if hi else d["neg_lo"]
             vals = [mc.half(x, sel[q]) * (-1 if ng[q] else 1) for q, x in enumerate(srcs)]
             if kind == "fma":
-                res.append((vals[0] * vals[1] + vals[2]).astype(f32))
+                res.append(_fma32_of(vals[0] * vals[1], vals[2]))
             elif kind == "mul":
                 res.append(vals[0].astype(f32) * vals[1].astype(f32))
             else:
@@ -625,7 +742,19 @@ def _ds(mc, t):
     read = m.startswith("ds_read")
     base, reg = (t[2], t[1]) if read else (t[1], t[2])
     k, lo = _decode(reg)[:2]
-    for ln in mc.active():
+    lanes = mc.active()
+    if m != "ds_min_f32" and lanes:
+        # every active lane at the same word of its own slice (the kernels' layout): one copy for the wavefront
+        word = _lds_word_of(mc.V[:, _decode(base)[1]].astype(np.int64) + t[3])
+        w = int(word[lanes[0]])
+        if w + n <= mc.lds.shape[1] and (mc.full and (word == w).all() or not mc.full and (word[mc.exec] == w).all()):
+            rows = slice(0, mc.lanes) if mc.full else mc.exec
+            if read:
+                mc.V[rows, lo:lo + n] = mc.lds[:mc.lanes][rows, w:w + n]
+            else:
+                mc.lds[:mc.lanes][rows, w:w + n] = mc.V[rows, lo:lo + n]
+            lanes = ()
+    for ln in lanes:
         sl, w = mc.lds_word(base, t[3], ln)
         if read:
             mc.V[ln, lo:lo + n] = mc.lds[sl, w:w + n]
@@ -695,12 +824,12 @@ VECTOR = {
     "v_max_f32": _f32op(_fmax),
     "v_max_f32_dpp": _f32op(_fmax, True),
     "v_min_f32": _f32op(_fmin),
-    "v_max3_f32": _f32op(_nanless(np.fmax)),
-    "v_min3_f32": _f32op(_nanless(np.fmin)),
-    "v_med3_f32": _f32op(lambda a, b, c: np.sort(np.stack([a, b, c]), 0)[1]),
-    "v_rcp_f32": _f32op(lambda a: f32(1.0) / a),
-    "v_rsq_f32": _f32op(lambda a: (1.0 / np.sqrt(a.astype(f64))).astype(f32)),
-    "v_sqrt_f32": _f32op(lambda a: np.sqrt(a.astype(f64)).astype(f32)),
+    "v_max3_f32": _f32op(_nanless(_fmax)),
+    "v_min3_f32": _f32op(_nanless(_fmin)),
+    "v_med3_f32": _f32op(_med3),
+    "v_rcp_f32": _approx32("v_rcp_f32", lambda a: f32(1.0) / a),
+    "v_rsq_f32": _approx32("v_rsq_f32", lambda a: (1.0 / np.sqrt(a.astype(f64))).astype(f32)),
+    "v_sqrt_f32": _approx32("v_sqrt_f32", lambda a: np.sqrt(a.astype(f64)).astype(f32)),
     "v_pk_fma_f32": _pk("fma"),
     "v_pk_mul_f32": _pk("mul"),
     "v_pk_add_f32": _pk("add"),
@@ -711,8 +840,8 @@ VECTOR = {
     "v_add_f64": _f64op(lambda a, b: a + b),
     "v_max_f64": _f64op(_fmax),
     "v_min_f64": _f64op(_fmin),
-    "v_rcp_f64": _f64op(lambda a: 1.0 / a),
-    "v_rsq_f64": _f64op(lambda a: 1.0 / np.sqrt(a)),
+    "v_rcp_f64": _approx64("v_rcp_f64", lambda a: 1.0 / a),
+    "v_rsq_f64": _approx64("v_rsq_f64", lambda a: 1.0 / np.sqrt(a)),
     "v_cmp_nlt_f64": _cmp("f64"),
     "v_cmp_eq_i32_e64": _cmp("int"),
     "v_cmp_ne_u32": _cmp("int"),
