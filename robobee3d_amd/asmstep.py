@@ -68,8 +68,8 @@ S_INT = {"stride": 10, "K": 13, "maxIter": S_ITERS, "nsub": 5, "plant": 39}     
 S_F = {n: 64 + k for k, n in enumerate(FLOATS)}                      # s64..s95
 assert max(S_F.values()) <= 95
 S_STEP, S_SUB, S_RUIZ = 12, 15, 15          # loop counters: closed-loop step; plant substep / Ruiz pass (never nested)
-S_EXACT = 14                                # lane form, step start .. end of Ruiz (the ADMM counter is dead there): 1 = every
-                                            # Ruiz pass of this step runs the exact limit_scaling body (StepGen.ruiz)
+S_EXACT = 14                                # both forms, step start .. end of Ruiz (the ADMM counter is dead there): 1 = every
+                                            # Ruiz pass of this step runs the exact limit_scaling body (StepGen.ruiz, ruiz_quad)
 S_MBAD, S_MP0 = 62, 14                      # phase C masks: s[62:63]; s[14:15] (ADMM / Ruiz counters are dead there)
 S_M0, S_M1, S_M2, S_M3 = 30, 32, 34, 36     # lane masks (pairs)
 S_C = {"minscal": 16, "maxscal": 17, "c45": 18, "eps10": 19, "eps": 38, "rho": 6, "rinv": 7, "rmin": 8,
@@ -347,12 +347,16 @@ class Struct:
 # The generator
 # ----------------------------------------------------------------------------------------------------------
 class StepGen:
-    def __init__(self, N=3, perm=None, quad=False, exact_ruiz=False, narrow_rows=False):
+    def __init__(self, N=3, perm=None, quad=False, exact_ruiz=False, narrow_rows=False, scalar_rk4=False):
         """quad: one robot per lane QUAD (asmquad.py) -- every phase runs redundantly in the four lanes of a quad and the
         ADMM iterations from the second on split the unknowns over lanes 0..2; the stream of the latency-bound shapes
         (B = 1 drop-in, batches that cannot give every SIMD a wave).
-        exact_ruiz: the lane form with all ten Ruiz passes through the exact limit_scaling body and no speculation -- the
-        stream the shipped one must equal bit for bit (tests/test_ruiz_fast_path.py); never written to a header.
+        exact_ruiz: all ten Ruiz passes through the exact limit_scaling body and no speculation -- the stream the shipped
+        one must equal bit for bit (tests/test_ruiz_fast_path.py, tests/test_step_budget.py); never written to a header. In
+        the quad form it also keeps the EXEC-masked maxima of the passes (ruiz_quad).
+        scalar_rk4: the lane form with the RK4 substep of one v_mul / v_fma per element on the public order of the state
+        words -- the stream before the paired layout (plant), kept for the bit comparison and A/B builds; never written to
+        a header. The quad form integrates on the lane quad (_rk4_quad) and has no such loop to pack.
         narrow_rows: the lane form with x, y, z on their public rows of `ctrl` on every step of a launch, one one-word access
         each -- the stream before the four-word groups (WIDE ROWS above), kept for comparison (tests/test_wide_rows.py, A/B
         builds); never written to a header. The quad form is always narrow."""
@@ -363,11 +367,13 @@ class StepGen:
         self.lab = 20
         self.lab_spec = 500            # labels of the Ruiz speculation: a range of their own, every other label keeps its number
         self.quad = quad
-        self.speculate = not quad and not exact_ruiz      # Ruiz passes 2..10 without limit tests, one test per step (ruiz)
+        self.speculate = not exact_ruiz      # Ruiz passes 2..10 without limit tests, one test per step (ruiz, ruiz_quad)
         self.ruiz_span = self.restart_at = None           # instruction indices, for the interpreter's counts (simulate)
         self.nt = () if quad else ("nt",)      # cache policy of the streaming rows and of the parked workspace rows
         self.homes = asmgen.Homes(NRING, 0 if quad else XV_N, XV_B)     # the loop's ring and extra homes of L
         self.wide_iterates = not quad and not narrow_rows      # x, y, z between the steps of a launch in four-word groups
+        self.packed_rk4 = not quad and not scalar_rk4          # the RK4 substep on aligned register pairs (plant)
+        self.rk4_span = None                                   # instruction indices of one RK4 substep (the loop), for counts
         # instruction index ranges, for the counts of tests/test_wide_rows.py: every access of the public x, y, z rows of
         # `ctrl`, and every access of the groups of the in-launch iterates
         self.public_spans, self.group_spans = [], []
@@ -421,7 +427,7 @@ class StepGen:
         e("s_cselect_b32", sg(sstep), 1, 0)
         e("s_add_i32", sg(lo + 1), sg(lo + 1), sg(sstep))
 
-    def impulse(self, Y0, YS):
+    def impulse(self, Y0, YS, ymap=None):
         """Velocity impulse of this closed-loop step (umpcBatchSetImpulses): dq (v<Y0+12> .. v<Y0+17>) += slice S_STEP of the
         table, one IEEE add per component, after the last plant substep (the quad RK4 has handed back to the one-lane
         layout) and ahead of the state store. The slice address imp + S_STEP * impstep is formed here, in lane masks that
@@ -429,8 +435,10 @@ class StepGen:
         the step. The 64-bit add carries by an unsigned compare and a skipped increment (s_add_u32 / s_addc_u32 stay the
         mark of the `ref` advance, s_cmp_lt_u32 / s_cselect_b32 that of the history advances); the rows of the slice are reached by
         moving that scalar base, the lanes' offset stays v0. With a null table the step executes five scalar instructions
-        more and nothing else. The six words land in v<YS> .. v<YS+5>, free after the plant."""
+        more and nothing else. The six words land in v<YS> .. v<YS+5>, free after the plant. ymap: the register of state word i
+        (the plant's own order of the words, plant)."""
         e = self.e
+        ymap = ymap or (lambda i: Y0 + i)
         lab_off = self.label()
         lo, hi, st, oh = S_IMP, S_IMP + 1, S_IMP + 2, S_IMP + 3
         e("s_mov_b32", sg(S_TMP), IMP_OFF)
@@ -454,7 +462,7 @@ class StepGen:
             e("global_load_dword", v(YS + i), "v0", sp(lo))
         e("s_waitcnt", "vmcnt(0)")
         for i in range(6):
-            e("v_add_f32", v(Y0 + 12 + i), v(Y0 + 12 + i), v(YS + i))
+            e("v_add_f32", v(ymap(12 + i)), v(ymap(12 + i)), v(YS + i))
         e("label", lab_off)
 
     def load_rows(self, ptr, first_row, regs, voff=None):
@@ -1020,7 +1028,9 @@ class StepGen:
         crosses lanes but the nine input columns (their entries sit in the lanes of their ROWS: norms reduced by DPP,
         scalings fetched from the lane of the step) and the cost normalisation's sum / maximum (a four-lane butterfly; lane
         3 duplicates lane 0 up to there and is zeroed out of it). At the end every word goes back to its one-lane home in
-        all four lanes. Same operations per value as ruiz(); the sum of P_jj is associated per lane (rounding only)."""
+        all four lanes. Same operations per value as ruiz(); the sum of P_jj is associated per lane (rounding only).
+        Inside the passes EXEC stays full (lane masks are select operands), and passes 2..10 speculate as ruiz() does; with
+        exact_ruiz the passes are the earlier ones: EXEC-masked maxima, ten exact passes, no restart."""
         from . import asmquad, asmquad64
         e, pool, st, s = self.e, self.pool, self.st, self.s
         nx, nc = s.nx, s.nc
@@ -1052,10 +1062,16 @@ class StepGen:
         ET = [dead.pop() for _ in range(13)]
         DT = [dead.pop() for _ in range(15)]
         t, m7, acc, qn, ct, tt = (dead.pop() for _ in range(6))
+        m3 = (m7, dead.pop(), dead.pop())
         masks = (asmquad.S_L0, asmquad.S_L1, asmquad.S_L2)
         S_L3 = 98
+        # parent form (exact_ruiz): a lane's share of a maximum / the zeroing of lane 3 under an EXEC mask. Shipped form: EXEC
+        # stays full and the lane mask is the select operand of a v_cndmask -- a lane outside the mask keeps its word
+        masked = not self.speculate
         keep = sorted(set(range(self.VP, self.VP + nx + 1)) | set(range(self.VQ, self.VQ + st.nq + st.nq % 2)) |
                       set(range(self.VA, self.VA + st.na + st.na % 2)) | {cs, VE + nc})
+        if self.speculate:
+            self.finite_guard()           # on the one-lane layout, ahead of the section: the lane form's instructions
         e("quad_begin", "ruiz")
         e("s_mov_b64", sp(asmquad.S_EXEC), "exec")
         for ln, m in enumerate(masks + (S_L3,)):
@@ -1086,70 +1102,145 @@ class StepGen:
         e("s_mov_b64", "exec", sp(asmquad.S_EXEC))
         e("s_nop", 4)
         e("s_mov_b32", sg(S_RUIZ), 10)
-        top = self.label()
-        e("label", top)
-        # (a) row norms -> Et
         byrow, bycol = {}, {}
         for key in sorted(rp.slots):
             byrow.setdefault(key[0], []).append(key)
             bycol.setdefault(key[1], []).append(key)
-        for R in range(13):
-            self.maxabs(ET[R], [hostA[k] for k in byrow[R]])
-        self.limit(ET, rsq=True)
-        # (b) column norms from the untouched columns -> Dt
-        for C in range(15):
-            own = [k for k in bycol.get(C, []) if rp.kind[k] == "own"]
-            self.maxabs(DT[C], [hostP[C]] + [hostA[k] for k in own])
-            for k in [k for k in bycol.get(C, []) if rp.kind[k] != "own"]:
-                r = hostA[k]
-                e("v_max_f32_dpp", v(m7), "|%s|" % v(r), "|%s|" % v(r), asmquad.qperm(asmquad64.ROT1))
-                e("v_max_f32_dpp", v(m7), "|%s|" % v(r), v(m7), asmquad.qperm(asmquad64.ROT2))       # max over lanes 0..2
-                e("s_mov_b64", "exec", sp(masks[rp.kind[k]]))
-                e("v_max_f32", v(DT[C]), v(DT[C]), v(m7))
+
+        def ruiz_pass(track):
+            """one pass: the exact body (track None) or the speculative one (scalings), as in ruiz_pass of the lane form. The
+            shipped form counts the pass down itself (S_RUIZ), in a wait state its DPP reads need anyway."""
+            # (a) row norms -> Et
+            for R in range(13):
+                self.maxabs(ET[R], [hostA[k] for k in byrow[R]])
+            if track is None:
+                self.scalings(ET, None)
+            # (b) column norms from the untouched columns -> Dt
+            for C in range(15):
+                own = [k for k in bycol.get(C, []) if rp.kind[k] == "own"]
+                self.maxabs(DT[C], [hostP[C]] + [hostA[k] for k in own])
+                other = [k for k in bycol.get(C, []) if rp.kind[k] != "own"]
+                if masked:
+                    for k in other:
+                        r = hostA[k]
+                        e("v_max_f32_dpp", v(m7), "|%s|" % v(r), "|%s|" % v(r), asmquad.qperm(asmquad64.ROT1))
+                        e("v_max_f32_dpp", v(m7), "|%s|" % v(r), v(m7), asmquad.qperm(asmquad64.ROT2))       # max over lanes 0..2
+                        e("s_mov_b64", "exec", sp(masks[rp.kind[k]]))
+                        e("v_max_f32", v(DT[C]), v(DT[C]), v(m7))
+                        e("s_mov_b64", "exec", sp(asmquad.S_EXEC))
+                        e("s_nop", 4)
+                elif other:
+                    # the maxima over lanes 0..2 of the column's foreign entries, one per lane of the column register; every lane
+                    # selects its own, lane 3 keeps Dt (max(Dt, Dt)), and ONE maximum folds them in
+                    assert sorted(rp.kind[k] for k in other) == [0, 1, 2]
+                    for k in other:
+                        r, mk = hostA[k], m3[rp.kind[k]]
+                        e("v_max_f32_dpp", v(mk), "|%s|" % v(r), "|%s|" % v(r), asmquad.qperm(asmquad64.ROT1))
+                        e("v_max_f32_dpp", v(mk), "|%s|" % v(r), v(mk), asmquad.qperm(asmquad64.ROT2))
+                    for kk in range(3):
+                        e("v_cndmask_b32_e64", v(t), v(DT[C] if kk == 0 else t), v(m3[kk]), sp(masks[kk]))
+                    e("v_max_f32", v(DT[C]), v(DT[C]), v(t))
+            # (the speculative body folds all 28 norms into the running minimum / maximum at once: the row norms feed nothing
+            # ahead of the apply)
+            self.scalings(DT, None) if track is None else self.scalings(ET + DT, track)
+            # apply: A <- diag(Et) A diag(Dt), P <- Dt P Dt, q <- Dt q
+            for C in range(15):
+                for k in bycol.get(C, []):
+                    r = hostA[k]
+                    e("v_mul_f32", v(r), v(r), v(ET[k[0]]))
+                    if rp.kind[k] == "own":
+                        e("v_mul_f32", v(r), v(r), v(DT[C]))
+                    else:
+                        kk = rp.kind[k]
+                        e("v_mul_f32_dpp", v(r), v(DT[C]), v(r), asmquad.qperm([kk] * 4))
+                e("v_mul_f32", v(hostP[C]), v(hostP[C]), v(DT[C]))
+                e("v_mul_f32", v(hostP[C]), v(hostP[C]), v(DT[C]))
+                if C in hostQ:
+                    e("v_mul_f32", v(hostQ[C]), v(hostQ[C]), v(DT[C]))
+            # (c) cost normalisation: c_t = 1 / limit(max(mean_j P_jj, limit(|q|_inf)))
+            e("v_add_f32", v(acc), v(hostP[0]), v(hostP[1]))
+            for C in range(2, 15):
+                e("v_add_f32", v(acc), v(acc), v(hostP[C]))
+            if masked:
+                self.maxabs(qn, [hostQ[C] for C in sorted(hostQ)])
+                e("s_mov_b64", "exec", sp(S_L3))
+                e("v_mov_b32", v(acc), 0)
+                e("v_mov_b32", v(qn), 0)
                 e("s_mov_b64", "exec", sp(asmquad.S_EXEC))
                 e("s_nop", 4)
-        self.limit(DT, rsq=True)
-        # apply: A <- diag(Et) A diag(Dt), P <- Dt P Dt, q <- Dt q
-        for C in range(15):
-            for k in bycol.get(C, []):
-                r = hostA[k]
-                e("v_mul_f32", v(r), v(r), v(ET[k[0]]))
-                if rp.kind[k] == "own":
-                    e("v_mul_f32", v(r), v(r), v(DT[C]))
-                else:
-                    kk = rp.kind[k]
-                    e("v_mul_f32_dpp", v(r), v(DT[C]), v(r), asmquad.qperm([kk] * 4))
-            e("v_mul_f32", v(hostP[C]), v(hostP[C]), v(DT[C]))
-            e("v_mul_f32", v(hostP[C]), v(hostP[C]), v(DT[C]))
-            if C in hostQ:
-                e("v_mul_f32", v(hostQ[C]), v(hostQ[C]), v(DT[C]))
-        # (c) cost normalisation: c_t = 1 / limit(max(mean_j P_jj, limit(|q|_inf)))
-        e("v_add_f32", v(acc), v(hostP[0]), v(hostP[1]))
-        for C in range(2, 15):
-            e("v_add_f32", v(acc), v(acc), v(hostP[C]))
-        self.maxabs(qn, [hostQ[C] for C in sorted(hostQ)])
-        e("s_mov_b64", "exec", sp(S_L3))
-        e("v_mov_b32", v(acc), 0)
-        e("v_mov_b32", v(qn), 0)
-        e("s_mov_b64", "exec", sp(asmquad.S_EXEC))
-        e("s_nop", 4)
-        for perm_ in ([1, 0, 3, 2], [2, 3, 0, 1]):
-            e("v_add_f32_dpp", v(acc), v(acc), v(acc), asmquad.qperm(perm_))
-            e("v_max_f32_dpp", v(qn), v(qn), v(qn), asmquad.qperm(perm_))
-            e("s_nop", 1)
-        e("v_mul_f32", v(acc), sg(S_C["c45"]), v(acc))
-        self.limit([qn], rsq=False)
-        e("v_max_f32", v(acc), v(acc), v(qn))
-        self.limit([acc], rsq=False)
-        self.rcp_nr(ct, acc, tt)
-        for C in range(15):
-            e("v_mul_f32", v(hostP[C]), v(hostP[C]), v(ct))
-            if C in hostQ:
-                e("v_mul_f32", v(hostQ[C]), v(hostQ[C]), v(ct))
-        e("v_mul_f32", v(cs), v(cs), v(ct))
-        e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
-        e("s_cmp_gt_i32", sg(S_RUIZ), 0)
-        e("s_cbranch_scc1", top + "b")
+                for perm_ in ([1, 0, 3, 2], [2, 3, 0, 1]):
+                    e("v_add_f32_dpp", v(acc), v(acc), v(acc), asmquad.qperm(perm_))
+                    e("v_max_f32_dpp", v(qn), v(qn), v(qn), asmquad.qperm(perm_))
+                    e("s_nop", 1)
+                e("v_mul_f32", v(acc), sg(S_C["c45"]), v(acc))
+            else:
+                # lane 3 out by a select; a DPP read waits two states for a VALU write of its register, and every one of them
+                # here is an instruction the pass executes anyway
+                e("v_cndmask_b32_e64", v(acc), v(acc), 0, sp(S_L3))
+                k0 = len(e.ins)
+                self.maxabs(qn, [hostQ[C] for C in sorted(hostQ)])
+                assert len(e.ins) - k0 >= 2
+                e("v_cndmask_b32_e64", v(qn), v(qn), 0, sp(S_L3))
+                p1, p2 = asmquad.qperm([1, 0, 3, 2]), asmquad.qperm([2, 3, 0, 1])
+                e("v_add_f32_dpp", v(acc), v(acc), v(acc), p1)
+                e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
+                e("v_max_f32_dpp", v(qn), v(qn), v(qn), p1)
+                e("v_add_f32_dpp", v(acc), v(acc), v(acc), p2)
+                e("v_mul_f32", v(acc), sg(S_C["c45"]), v(acc))
+                e("v_max_f32_dpp", v(qn), v(qn), v(qn), p2)
+            self.limit([qn], rsq=False)
+            e("v_max_f32", v(acc), v(acc), v(qn))
+            self.limit([acc], rsq=False)
+            self.rcp_nr(ct, acc, tt)
+            for C in range(15):
+                e("v_mul_f32", v(hostP[C]), v(hostP[C]), v(ct))
+                if C in hostQ:
+                    e("v_mul_f32", v(hostQ[C]), v(hostQ[C]), v(ct))
+            e("v_mul_f32", v(cs), v(cs), v(ct))
+
+        if not self.speculate:
+            top = self.label()
+            e("label", top)
+            ruiz_pass(None)
+            e("s_sub_i32", sg(S_RUIZ), sg(S_RUIZ), 1)
+            e("s_cmp_gt_i32", sg(S_RUIZ), 0)
+            e("s_cbranch_scc1", top + "b")
+        else:
+            # The speculation of ruiz() on the quad: pass 1 through the exact body, passes 2..10 through the body without
+            # limit tests, one wave-wide range test, the step again with S_EXACT set where it fails. Lane 3 of a quad only
+            # mirrors lane 0 (its column norms lack the other lanes' share, its words go nowhere): the test leaves it out.
+            # Only the branch that leaves the exact body is an s_cbranch_scc1: the loop-backs behind it test the inverse.
+            track = (dead.pop(), dead.pop())
+            lab_x = self.label()
+            lab_spec, lab_f, lab_done = (self.label_spec() for _ in range(3))
+            first = len(e.ins)
+            e("label", lab_x)
+            ruiz_pass(None)
+            e("s_cmp_eq_u32", sg(S_EXACT), 0)
+            e("s_cbranch_scc1", lab_spec + "f")
+            e("s_cmp_lt_i32", sg(S_RUIZ), 1)                     # exact step: passes 2..10 through the body above
+            e("s_cbranch_scc0", lab_x + "b")
+            e("s_branch", lab_done + "f")
+            e("label", lab_spec)
+            for r in track:
+                e("v_mov_b32", v(r), 1.0)
+            e("label", lab_f)
+            ruiz_pass(track)
+            e("s_cmp_lt_i32", sg(S_RUIZ), 1)
+            e("s_cbranch_scc0", lab_f + "b")
+            e("v_cmp_lt_f32", "vcc", sg(S_C["minscal"]), v(track[0]))          # the lane masks are dead behind the last pass
+            e("v_cmp_ge_f32_e64", sp(masks[0]), sg(S_C["maxscal"]), v(track[1]))
+            e("s_and_b64", "vcc", "vcc", sp(masks[0]))
+            e("s_or_b64", "vcc", "vcc", sp(S_L3))
+            e("s_andn2_b64", "vcc", "exec", "vcc")               # SCC = some lane 0..2 of some quad is not clean
+            e("s_cbranch_scc0", lab_done + "f")
+            # cold: the step again, exact (the wait retires this attempt's T0 store ahead of the reload)
+            e("s_mov_b32", sg(S_EXACT), 1)
+            e("s_waitcnt", "vmcnt(0) lgkmcnt(0)")
+            self.restart_at = len(e.ins)
+            e("s_branch", self.lab_restart + "b")
+            e("label", lab_done)
+            self.ruiz_span = (first, len(e.ins))
         # ---- exit: every word back to its one-lane home in all four lanes (the hosts last: they are sources until then)
         e("s_nop", 1)
 
@@ -2055,11 +2146,26 @@ class StepGen:
         e("s_cmp_lt_i32", sg(S_INT["nsub"]), 1)
         e("s_cbranch_scc1", lab_end + "f")
         Y0, YS, KK, AC = pool.getn(18), pool.getn(18), pool.getn(18), pool.getn(18)
+        # PAIRED LAYOUT (lane form): where the plant keeps the 18 state words, in Y0 and in the RK4 loop's YS, KK, AC alike.
+        # A packed fp32 instruction costs the lone wave what a scalar one costs, so two equal IEEE operations on an aligned
+        # register pair halve their price and change no bit. Pairs: (p1, p2) and (v1, v2) -- the derivative of the first IS
+        # the second of the source state, so the combinations read it there and only p0 needs a move --, rows (1, 2) of every
+        # column of R (R skew(w) treats the rows alike), (wy, wz) (Ib w, and the last two of Ib^-1 (...)); then the singles,
+        # p0 | v0 | R00 R01 R02 | wx, two to a pair for the combinations. The permutation rides on the moves in from ST; the
+        # Euler step, the impulses and the state store go through ymap. Other forms keep the public order.
+        order = [1, 2, 13, 14, 4, 5, 7, 8, 10, 11, 16, 17, 0, 12, 3, 6, 9, 15] if self.packed_rk4 else list(range(18))
+        assert sorted(order) == list(range(18))
+        M = {w: k for k, w in enumerate(order)}
+        ymap = lambda i: Y0 + M[i]
         for i in range(18):
-            e("v_mov_b32", v(Y0 + i), v(ST[i]))
+            e("v_mov_b32", v(ymap(i)), v(ST[i]))
         Th, u1, u2, einc = g_(), g_(), g_(), g_()
-        Ib = [g_() for _ in range(3)]
-        Ibi = [g_() for _ in range(3)]
+        if self.packed_rk4:
+            ib12, ibi12 = pool.get2(), pool.get2()
+            Ib, Ibi = [g_(), ib12, ib12 + 1], [g_(), ibi12, ibi12 + 1]
+        else:
+            Ib = [g_() for _ in range(3)]
+            Ibi = [g_() for _ in range(3)]
         serr, seff, t = g_(), g_(), g_()
         lab_g, lab_g2, lab_i, lab_i2, lab_s, lab_s2 = [self.label() for _ in range(6)]
         # thrust gain (Monte-Carlo mass sweep), inertia, statistics
@@ -2143,8 +2249,8 @@ class StepGen:
         e("s_mov_b32", sg(S_SUB), sg(S_INT["nsub"]))
         top0 = self.label()
         e("label", top0)
-        R = lambda k: Y0 + 3 + k
-        wx, wy, wz = Y0 + 15, Y0 + 16, Y0 + 17
+        R = lambda k: ymap(3 + k)
+        wx, wy, wz = ymap(15), ymap(16), ymap(17)
         dd = [YS + k for k in range(6)]                      # ddq
         e("v_mul_f32", v(dd[0]), v(Th), v(R(6)))
         e("v_mul_f32", v(dd[1]), v(Th), v(R(7)))
@@ -2166,7 +2272,7 @@ class StepGen:
         e("v_mul_f32", v(dd[4]), v(b), v(Ibi[1]))
         e("v_mul_f32", v(dd[5]), "-" + v(hz), v(Ibi[2]))
         for i in range(3):
-            e("v_fmac_f32", v(Y0 + i), SF("h"), v(Y0 + 12 + i))            # p += h v (old v)
+            e("v_fmac_f32", v(ymap(i)), SF("h"), v(ymap(12 + i)))            # p += h v (old v)
         ax, ay, az, tt, ca, cb = [KK + k for k in range(6)]
         e("v_mul_f32", v(ax), SF("h"), v(wx))
         e("v_mul_f32", v(ay), SF("h"), v(wy))
@@ -2216,10 +2322,9 @@ class StepGen:
         for k in range(9):
             e("v_mov_b32", v(R(k)), v(Rn[k]))
         for i in range(6):
-            e("v_fmac_f32", v(Y0 + 12 + i), SF("h"), v(dd[i]))              # dq += h ddq
-        e("v_fmac_f32", v(serr), v(Y0), v(Y0))
-        e("v_fmac_f32", v(serr), v(Y0 + 1), v(Y0 + 1))
-        e("v_fmac_f32", v(serr), v(Y0 + 2), v(Y0 + 2))
+            e("v_fmac_f32", v(ymap(12 + i)), SF("h"), v(dd[i]))              # dq += h ddq
+        for i in range(3):
+            e("v_fmac_f32", v(serr), v(ymap(i)), v(ymap(i)))
         e("v_add_f32", v(seff), v(seff), v(einc))
         e("s_sub_i32", sg(S_SUB), sg(S_SUB), 1)
         e("s_cmp_gt_i32", sg(S_SUB), 0)
@@ -2233,6 +2338,39 @@ class StepGen:
         e("s_mov_b32", sg(S_SUB), sg(S_INT["nsub"]))
         top = self.label()
         e("label", top)
+        if self.packed_rk4:
+            self._rk4_packed(Y0, YS, KK, AC, M, Th, u1, u2, Ib, Ibi, a, b, two)
+        else:
+            self._rk4_scalar(vf, Y0, YS, KK, AC, two)
+        for i in range(3):
+            e("v_fmac_f32", v(serr), v(ymap(i)), v(ymap(i)))
+        e("v_add_f32", v(seff), v(seff), v(einc))
+        e("s_sub_i32", sg(S_SUB), sg(S_SUB), 1)
+        e("s_cmp_gt_i32", sg(S_SUB), 0)
+        e("s_cbranch_scc1", top + "b")
+        self.rk4_span = (asmtext.label_index(e.ins, top), len(e.ins))
+        e("label", lab_done)
+        self.impulse(Y0, YS, ymap)
+        # step history: both state loads of this step (phase A, phase C) are behind us and its only state store follows, so
+        # the base moves on by `statestep` bytes HERE -- the store fills slice k + 1, which the next step's loads read. The
+        # word is read from the second parameter block once per step (no SGPR is free for the whole kernel in the quad form).
+        e("s_load_dword", sg(S_TMP), sp(S_PBLK), OFF["statestep"])
+        e("s_waitcnt", "lgkmcnt(0)")
+        self.advance_ptr("state", S_TMP)
+        self.store_rows("state", 0, [ymap(i) for i in range(18)], voff)
+        e("s_cmp_eq_u64", sp(S_PTR["stats"]), 0)
+        e("s_cbranch_scc1", lab_s2 + "f")
+        self.store_rows("stats", 0, [serr, seff], voff)
+        e("label", lab_s2)
+        pool.free(Th, u1, u2, einc, *Ib, *Ibi, serr, seff, t, two, a, b)
+        for base in (Y0, YS, KK, AC):
+            pool.free_range(base, 18)
+        e("label", lab_end)
+
+    def _rk4_scalar(self, vf, Y0, YS, KK, AC, two):
+        """One RK4 substep on the public order of the state words: four vector fields of one instruction per element (vf of
+        plant) and the packed combinations. The loop of the quad form's dead tail and of StepGen(scalar_rk4=True)."""
+        e = self.e
         vf(Y0, AC)                                                             # k1
         for k in range(0, 18, 2):
             pk(e, "v_pk_fma_f32", YS + k, [PS(S_F["hh"]), P2(AC + k), P2(Y0 + k)])
@@ -2249,30 +2387,93 @@ class StepGen:
             pk(e, "v_pk_add_f32", AC + k, [P2(AC + k), P2(KK + k)])
         for k in range(0, 18, 2):
             pk(e, "v_pk_fma_f32", Y0 + k, [PS(S_F["h6"]), P2(AC + k), P2(Y0 + k)])
-        e("v_fmac_f32", v(serr), v(Y0), v(Y0))
-        e("v_fmac_f32", v(serr), v(Y0 + 1), v(Y0 + 1))
-        e("v_fmac_f32", v(serr), v(Y0 + 2), v(Y0 + 2))
-        e("v_add_f32", v(seff), v(seff), v(einc))
-        e("s_sub_i32", sg(S_SUB), sg(S_SUB), 1)
-        e("s_cmp_gt_i32", sg(S_SUB), 0)
-        e("s_cbranch_scc1", top + "b")
-        e("label", lab_done)
-        self.impulse(Y0, YS)
-        # step history: both state loads of this step (phase A, phase C) are behind us and its only state store follows, so
-        # the base moves on by `statestep` bytes HERE -- the store fills slice k + 1, which the next step's loads read. The
-        # word is read from the second parameter block once per step (no SGPR is free for the whole kernel in the quad form).
-        e("s_load_dword", sg(S_TMP), sp(S_PBLK), OFF["statestep"])
-        e("s_waitcnt", "lgkmcnt(0)")
-        self.advance_ptr("state", S_TMP)
-        self.store_rows("state", 0, [Y0 + i for i in range(18)], voff)
-        e("s_cmp_eq_u64", sp(S_PTR["stats"]), 0)
-        e("s_cbranch_scc1", lab_s2 + "f")
-        self.store_rows("stats", 0, [serr, seff], voff)
-        e("label", lab_s2)
-        pool.free(Th, u1, u2, einc, *Ib, *Ibi, serr, seff, t, two, a, b)
-        for base in (Y0, YS, KK, AC):
-            pool.free_range(base, 18)
-        e("label", lab_end)
+
+    def _rk4_packed(self, Y0, YS, KK, AC, M, Th, u1, u2, Ib, Ibi, a, b, two):
+        """One RK4 substep on the PAIRED LAYOUT (plant): every element goes through the instruction sequence of _rk4_scalar --
+        the same v_mul / v_fma with the same operands -- two elements to an instruction wherever the layout pairs them.
+        Per vector field 28 instructions instead of 39: dR 12 (rows 1, 2 packed, row 0 alone), thrust 3, Ib w 2, the cross
+        product 6, the last five 4 ((u2 - cy, -cz) . (1/Ib1, 1/Ib2) as one product: cy, cz are built in an aligned pair),
+        one move (dp0 = v0). (p1, p2)' = (v1, v2) of the SOURCE state is read there by the combinations: pair 0 of a
+        derivative vector does not exist, and the combinations of pair 0 run ahead of those of pair 1, which overwrite
+        (v1, v2) of YS. Ib[1:3] and Ibi[1:3] are aligned pairs."""
+        e, pool = self.e, self.pool
+        assert Ib[1] % 2 == 0 and Ib[2] == Ib[1] + 1 and Ibi[1] % 2 == 0 and Ibi[2] == Ibi[1] + 1
+        A2, B2, T = pool.get2(), pool.get2(), pool.get2()
+        PV = M[13]                     # the pair (v1, v2); (p1, p2) is pair 0
+        assert M[1] == 0 and M[2] == 1 and PV % 2 == 0 and M[14] == PV + 1
+
+        def pkm(mnem, dst, srcs, neg_lo, neg_hi):
+            e(mnem, vp2(dst), *[s_[0] for s_ in srcs],
+              dict(op_sel=[s_[1] for s_ in srcs], op_sel_hi=[s_[2] for s_ in srcs], neg_lo=list(neg_lo), neg_hi=list(neg_hi)))
+
+        def vf(src, dst):
+            y = lambda i: src + M[i]
+            d = lambda i: dst + M[i]
+            R = lambda r, c: 3 + r + 3 * c                  # state word of R[r][c] (column-major)
+            C = lambda base, c: base + M[R(1, c)]           # the pair of rows (1, 2) of column c
+            for c in range(3):
+                assert C(0, c) % 2 == 0 and M[R(2, c)] == M[R(1, c)] + 1
+            wx, wy, wz = y(15), y(16), y(17)
+            e("v_mov_b32", v(d(0)), v(y(12)))
+            # dR = R skew(w): row 0 ...
+            e("v_mul_f32", v(a), v(y(R(0, 2))), v(wy))
+            e("v_fma_f32", v(d(R(0, 0))), v(y(R(0, 1))), v(wz), "-" + v(a))
+            e("v_mul_f32", v(b), v(y(R(0, 0))), v(wz))
+            e("v_fma_f32", v(d(R(0, 1))), v(y(R(0, 2))), v(wx), "-" + v(b))
+            e("v_mul_f32", v(a), v(y(R(0, 1))), v(wx))
+            e("v_fma_f32", v(d(R(0, 2))), v(y(R(0, 0))), v(wy), "-" + v(a))
+            # ... and rows (1, 2), two to an instruction
+            pk(e, "v_pk_mul_f32", A2, [P2(C(src, 2)), PB(wy)])
+            pk(e, "v_pk_fma_f32", C(dst, 0), [P2(C(src, 1)), PB(wz), P2(A2)], [0, 0, 1])
+            pk(e, "v_pk_mul_f32", B2, [P2(C(src, 0)), PB(wz)])
+            pk(e, "v_pk_fma_f32", C(dst, 1), [P2(C(src, 2)), PB(wx), P2(B2)], [0, 0, 1])
+            pk(e, "v_pk_mul_f32", A2, [P2(C(src, 1)), PB(wx)])
+            pk(e, "v_pk_fma_f32", C(dst, 2), [P2(C(src, 0)), PB(wy), P2(A2)], [0, 0, 1])
+            # dv = Th R e3 - g e3
+            e("v_mul_f32", v(d(12)), v(Th), v(y(R(0, 2))))
+            pk(e, "v_pk_mul_f32", dst + PV, [PB(Th), P2(C(src, 2))])
+            e("v_subrev_f32", v(d(14)), sg(S_F["gpl"]), v(d(14)))
+            # dw = Ib^-1 (tau - w x Ib w); Ib w staged in place
+            hx, hy, hz = d(15), d(16), d(17)
+            assert hy % 2 == 0 and hz == hy + 1 and wy % 2 == 0 and wz == wy + 1
+            e("v_mul_f32", v(hx), v(Ib[0]), v(wx))
+            pk(e, "v_pk_mul_f32", hy, [P2(Ib[1]), P2(wy)])
+            e("v_mul_f32", v(a), v(wz), v(hy))
+            e("v_fma_f32", v(a), v(wy), v(hz), "-" + v(a))       # cx
+            e("v_mul_f32", v(T), v(wx), v(hz))
+            e("v_fma_f32", v(T), v(wz), v(hx), "-" + v(T))       # cy
+            e("v_mul_f32", v(T + 1), v(wy), v(hx))
+            e("v_fma_f32", v(T + 1), v(wx), v(hy), "-" + v(T + 1))     # cz
+            e("v_sub_f32", v(a), v(u1), v(a))
+            e("v_mul_f32", v(d(15)), v(a), v(Ibi[0]))
+            e("v_sub_f32", v(T), v(u2), v(T))
+            pkm("v_pk_mul_f32", hy, [P2(T), P2(Ibi[1])], [0, 0], [1, 0])     # ((u2 - cy) / Ib1, (-cz) / Ib2)
+
+        def combine(mnem, dstv, coef, kv, srcv, base):
+            """dstv = coef * K + base over the nine pairs (coef None: K + base); K = kv, pair 0 of it = (v1, v2) of srcv"""
+            for k in range(0, 18, 2):
+                K = P2(srcv + PV) if k == 0 else P2(kv + k)
+                B_ = base(k)
+                pk(e, mnem, dstv + k, [K, B_] if coef is None else [coef, K, B_])
+
+        hh, h, h6 = PS(S_F["hh"]), PS(S_F["h"]), PS(S_F["h6"])
+        vf(Y0, AC)                                                             # k1 (its pair 0 stays (v1, v2) of Y0)
+        combine("v_pk_fma_f32", YS, hh, AC, Y0, lambda k: P2(Y0 + k))
+        vf(YS, KK)                                                             # k2
+        for k in range(0, 18, 2):
+            K = P2(YS + PV) if k == 0 else P2(KK + k)
+            pk(e, "v_pk_fma_f32", AC + k, [PB(two), K, P2(Y0 + PV) if k == 0 else P2(AC + k)])
+            pk(e, "v_pk_fma_f32", YS + k, [hh, K, P2(Y0 + k)])
+        vf(YS, KK)                                                             # k3
+        for k in range(0, 18, 2):
+            K = P2(YS + PV) if k == 0 else P2(KK + k)
+            pk(e, "v_pk_fma_f32", AC + k, [PB(two), K, P2(AC + k)])
+            pk(e, "v_pk_fma_f32", YS + k, [h, K, P2(Y0 + k)])
+        vf(YS, KK)                                                             # k4
+        combine("v_pk_add_f32", AC, None, KK, YS, lambda k: P2(AC + k))
+        for k in range(0, 18, 2):
+            pk(e, "v_pk_fma_f32", Y0 + k, [h6, P2(AC + k), P2(Y0 + k)])
+        pool.free(A2, A2 + 1, B2, B2 + 1, T, T + 1)
 
 
     def _rk4_quad(self, Y0, YS, KK, AC, Th, u1, u2, einc, Ib, Ibi, serr, seff, a, b, two):
@@ -2439,13 +2640,13 @@ fmt = functools.partial(asmtext.fmt, hex_ints=asmtext.HEX_ABOVE_64)       # this
 PSEUDO = ("kill", "quad_begin", "quad_end")      # markers for the CPU interpreters, not instructions
 
 
-def write(path=None, N=3, perm=None, quad=False, narrow_rows=False):
+def write(path=None, N=3, perm=None, quad=False, narrow_rows=False, scalar_rk4=False):
     """quad: the one-robot-per-lane-quad stream (asmquad.py) -> csrc/umpc_step_asm_quad.h, macro UMPC_STEP_ASM_QUAD; it
     shares struct StepParams with the one-lane header, which must be included first.
-    narrow_rows (StepGen): only with a `path` of the caller's, for A/B builds (tools/build_variant.py)."""
-    assert not narrow_rows or (path and not quad), "the shipped headers carry the default streams"
+    narrow_rows, scalar_rk4 (StepGen): only with a `path` of the caller's, for A/B builds (tools/build_variant.py)."""
+    assert not (narrow_rows or scalar_rk4) or (path and not quad), "the shipped headers carry the default streams"
     path = path or os.path.join(HERE, "csrc", "umpc_step_asm_quad.h" if quad else "umpc_step_asm.h")
-    g = StepGen(N, perm, quad=quad, narrow_rows=narrow_rows)
+    g = StepGen(N, perm, quad=quad, narrow_rows=narrow_rows, scalar_rk4=scalar_rk4)
     ins = [t for t in g.program() if t[0] not in PSEUDO]
     if quad:
         head = ["// GENERATED by robobee3d_amd/asmstep.py (quad=True) + asmquad.py -- do not edit.", asmgen.switch_banner(),

@@ -205,6 +205,7 @@ class Machine:
         self.max_exec, self.quad, self.log = max_exec, quad or {}, log
         self.nexec = 0
         self.sections = {}             # quad section name -> executed instructions
+        self.in_quad = None            # the quad_begin tuple of the section this machine runs (run_quad), None outside one
         self.hits = None               # set to an int array [len(ins)] to count the executions of every instruction
         self.pend = {"vmcnt": [], "lgkmcnt": []}
         self.labels = {}
@@ -404,6 +405,12 @@ class Machine:
                     self.pc += 1
                     continue
                 if m == "quad_begin":
+                    if self.in_quad:
+                        # a section that branched back ahead of its own quad_begin (the Ruiz restart of asmstep.ruiz_quad):
+                        # the four lanes have run the one-lane stream again, each on its own registers, as on the device
+                        assert t == self.in_quad, ("a quad section entered from inside another", self.in_quad, t)
+                        self.pc += 1
+                        continue
                     self.run_quad(t)
                     continue
                 if m == "quad_end":
@@ -436,6 +443,7 @@ class Machine:
         q = Machine(self.ins, 4, lds=np.tile(self.lds, (4, 1)), max_exec=self.max_exec,
                     V=np.tile(self.V, (4, 1)), A=np.tile(self.A, (4, 1)), approx=self.approx)
         q.V[:, LANE_LDS_VGPR] += 16 * np.arange(4, dtype=u32)
+        q.in_quad = t
         q.S, q.scc, q.regions, q.pend, q.labels, q._use = self.S, self.scc, self.regions, self.pend, self.labels, self._use
         for _ in q.run(self.pc + 1):
             raise AssertionError("s_barrier inside a quad section")

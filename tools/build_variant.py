@@ -3,7 +3,8 @@
 environment (asmgen.SWITCHES), for timing step-kernel variants next to the shipped library in one session (select with UMPC_LIB).
 usage: UMPC_ASM64_TIMING=1 tools/build_variant.py timing64
        UMPC_VARIANT_DEFS="-DUMPC_SCALING_ITERS=1" tools/build_variant.py ruiz1     (extra compiler flags, timing diagnostics)
-       tools/build_variant.py narrow narrow_rows=1     (the lane stream with x, y, z on their public rows every step, asmstep.StepGen)"""
+       tools/build_variant.py narrow narrow_rows=1     (the lane stream with x, y, z on their public rows every step, asmstep.StepGen)
+       tools/build_variant.py scalar scalar_rk4=1      (the lane stream with the RK4 substep of one instruction per element)"""
 import os
 import subprocess
 import sys
@@ -21,8 +22,9 @@ clean = {k: v for k, v in os.environ.items() if k not in asmgen.generator_switch
 subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from robobee3d_amd import _lib; _lib.build()" % ROOT],
                check=True, env=clean)
 hdr = os.path.join(vdir, "umpc_step_asm.h")
-narrow = dict(a.split("=", 1) for a in sys.argv[2:]).get("narrow_rows", "")
-asmstep.write(hdr, narrow_rows={"": False, "1": True}[narrow])
+opts = dict(a.split("=", 1) for a in sys.argv[2:])
+assert set(opts) <= {"narrow_rows", "scalar_rk4"}, opts
+asmstep.write(hdr, **{k: {"": False, "0": False, "1": True}[v] for k, v in opts.items()})
 obj = os.path.join(vdir, name + ".o")
 csrc = os.path.join(ROOT, "robobee3d_amd", "csrc")
 subprocess.run(["hipcc"] + _lib.HIPCC_FLAGS + os.environ.get("UMPC_VARIANT_DEFS", "").split() + ["-DUMPC_STEP_ASM_HEADER=\"%s\"" % hdr, "-c", "-o", obj, _lib.SRC], check=True, cwd=csrc)
